@@ -55,6 +55,13 @@ kernel-only duration rocprofv3's kernel trace reports.  The dominant kernel
 (largest total time) and the next two are reported with their algorithmic
 bytes and ops per launch.
 
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K
+steps and prints the result line; the lines measured beside the headline
+(band_one_job_per_pass, latency_point, single_engine_one_worker_per_gpu, the
+roofline / device times, the CPU baseline) take runs of their own and are
+measured only with `--full` (null in a plain run's line).  `--dump-outputs
+DIR` writes the output tensors the timed engine returns (dump_outputs).
+
 Prints ONE JSON line on rank 0.  `--profile-only` runs just the profiled
 passes (for rocprofv3 kernel traces / PMC passes of exactly those launches).
 """
@@ -138,6 +145,14 @@ def parse():
                    help="--single-engine: GPU workers per GPU (default --workers-per-gpu; 1 = one Worker per GPU)")
     p.add_argument("--profile-only", action="store_true",
                    help="run only the profiled batch passes (rocprofv3 traces); prints their per-kernel table")
+    p.add_argument("--full", action="store_true",
+                   help="also measure the lines beside the headline: band_one_job_per_pass, latency_point, "
+                        "single_engine_one_worker_per_gpu, the per-launch roofline / device times and the CPU "
+                        "baseline (each can still be switched off by its own --no-* option); a plain run sets up, "
+                        "warms up, times the steps and prints the result line with those fields null")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write the output tensors the headline engine returns for each "
+                        "model's request as DIR/<model>_out<k>.npy (float32; dump_outputs)")
     return p.parse_args()
 
 
@@ -602,6 +617,7 @@ HOST_THREADS = {}
 HOST_THREAD_STATES = {}
 COALESCE = {}  # backend job coalescing over the last timed loop (coalescer.h)
 LAST_MODEL_IDX = []  # the model index of every job of the last timed closed loop (driver-reported)
+DUMPED = {}  # --dump-outputs: file -> shape of what was written
 
 
 def cgroup_cpu_stat():
@@ -775,7 +791,7 @@ def run_closed(engine, band_models, inputs, n_warm, n_timed, inflight, D):
     return D.max(t1 - t0), lat_us, worker_ids
 
 
-def single_engine_line(args, D, paths, sched, W, n_gpus, n_warm, n_timed, names=()):
+def single_engine_line(args, D, paths, sched, W, n_gpus, n_warm, n_timed, names=(), dump_dir=""):
     """ONE Band engine over n_gpus GPUs in this process: W GPU workers per GPU,
     worker w on GPU w % n_gpus (so round_robin's rotation alternates GPUs),
     one planner thread (band/engine.cc:681-713, band/planner.cc:268-293)"""
@@ -811,6 +827,8 @@ def single_engine_line(args, D, paths, sched, W, n_gpus, n_warm, n_timed, names=
         inflight = args.inflight * n_gpus if args.inflight else default_inflight(n_workers, args.job_batch)
         el, lat, wid = run_closed(e, bm, ins, n_warm, n_timed, inflight, Local())
         per_model = per_model_latency(lat, list(names), len(bm), LAST_MODEL_IDX)
+        if dump_dir:
+            DUMPED.update(dump_outputs(dump_dir, e, bm, ins, list(names), args.job_batch))
         e.close()
     finally:
         for k, v in saved.items():
@@ -868,6 +886,55 @@ def per_model_latency(lat_us, names, n_models, model_idx):
             key = names[m] if m < len(names) else str(m)
             out[key] = {"p50": round(float(np.percentile(v, 50)), 3), "p99": round(float(np.percentile(v, 99)), 3)}
     return out
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6  # of float32 over every file of one --dump-outputs run (limit: 64 MB)
+
+
+def dump_outputs(out_dir, engine, band_models, inputs, names, job_batch):
+    """--dump-outputs: what the timed engine returns to the caller of a
+    request, per model.  The native closed-loop driver reads every job's
+    outputs and drops them, and a model's request tensor is the same seeded
+    array in every job of every step, so after the timed steps the same
+    engine is sent one more pass's worth of requests per model
+    (`job_batch` of them in one vector RequestAsync, as the driver submits
+    them: request ring -> planner -> worker -> the batched pass -> output
+    copy) and each job's output tensors are read with Wait.  Written as
+    DIR/<model>_out<k>.npy, float32, shape (jobs kept,) + the tensor's dims;
+    the jobs kept are the first ones of the pass, as many as fit the size
+    budget.  Where one job's tensors alone exceed the budget, a tensor is
+    written as a fixed sample of its elements (flat indices drawn with
+    seed 5489, sorted).  Returns {file: shape}."""
+    from band_amd.engine import kBandOk
+    os.makedirs(out_dir, exist_ok=True)
+    n_req = max(1, job_batch)
+    outs = [[engine.CreateOutputTensor(m, k) for k in range(engine.GetNumOutputTensors(m))] for m in band_models]
+    per_job = sum(4 * o.data().size for mo in outs for o in mo)
+    keep = int(max(1, min(n_req, DUMP_BUDGET_BYTES // max(1, per_job))))
+    written = {}
+    for i, (m, mo) in enumerate(zip(band_models, outs)):
+        # (inputs beyond the first: zero tensors, as the driver submits them)
+        ins = [inputs[i]] + [engine.CreateInputTensor(m, k) for k in range(1, engine.GetNumInputTensors(m))]
+        for t in ins[1:]:
+            t.data()[...] = 0
+        handles = engine.RequestsAsync([m] * n_req, [ins] * n_req)
+        assert handles is not None, "dump-outputs: RequestAsync refused (%s)" % names[i]
+        jobs = [[] for _ in mo]
+        for j, h in enumerate(handles):
+            assert h >= 0 and engine.Wait(h, mo) == kBandOk, "dump-outputs: job %d of %s failed" % (j, names[i])
+            if j < keep:
+                for k, o in enumerate(mo):
+                    jobs[k].append(o.data().astype(np.float32))
+        for k, per in enumerate(jobs):
+            arr = np.stack(per)
+            base = "%s_out%d" % (names[i], k)
+            share = DUMP_BUDGET_BYTES * arr.nbytes // max(1, per_job * keep)
+            if per_job > DUMP_BUDGET_BYTES and arr.nbytes > share:
+                idx = np.sort(np.random.default_rng(5489).choice(arr.size, size=max(1, share // 4), replace=False))
+                arr = arr.reshape(-1)[idx]
+            np.save(os.path.join(out_dir, base + ".npy"), arr)
+            written[base + ".npy"] = list(arr.shape)
+    return written
 
 
 def main():
@@ -944,7 +1011,7 @@ def main():
         # headline: one process, one engine over all --gpus GPUs
         assert D.world == 1, "--single-engine runs in one process (no torchrun)"
         single = single_engine_line(args, D, paths, sched, args.single_engine_wpg or W, max(1, args.gpus), n_warm,
-                                    n_timed, names=[m[0] for m in models])
+                                    n_timed, names=[m[0] for m in models], dump_dir=args.dump_outputs)
         elapsed, lat_us, worker_ids = n_timed / single["value"], None, []
         jobs_per_worker = single["jobs_per_gpu"]
         subgraph_jobs = None
@@ -985,6 +1052,9 @@ def main():
         # every subgraph execution per worker (warm-up included): a split
         # model's GPU share is invisible in the last-subgraph counts above
         subgraph_jobs = [engine.GetWorkerJobCount(w) for w in range(n_cpu + W)]
+        if args.dump_outputs and D.rank == 0:
+            DUMPED.update(dump_outputs(args.dump_outputs, engine, band_models, inputs, [m[0] for m in models],
+                                       args.job_batch))
         engine.close()
         n_ranks = D.world
     all_lat = [x for part in D.gather((lat_us * 1e-6).tolist() if lat_us is not None else []) for x in part]
@@ -992,7 +1062,7 @@ def main():
     # Band's own semantics beside it: one job per ExecuteSubgraph (no job
     # batching), the same mix and scheduler over 8 GPU workers per GPU
     batch1 = None
-    if batching and not poisson and not args.no_batch1 and not args.single_engine:
+    if args.full and batching and not poisson and not args.no_batch1 and not args.single_engine:
         def band1_line(W1, n1):
             e1, bm1, in1 = make_engine(args, D, paths, sched, [DeviceFlag.kGPU] * W1, 0, W1, 1, seed_offset=D.rank)
             el1, lat1, _ = run_closed(e1, bm1, in1, max(n_warm // 4, 2 * W1 * M), n1, 2 * W1, D)
@@ -1017,8 +1087,8 @@ def main():
     # and engine shape with smaller passes and fewer requests in flight
     # (p99 near 3 ms at about 105k inf/s per GPU)
     latency_point = None
-    if (batching and not poisson and not args.single_engine and D.world == 1 and on_gpu and args.latency_point
-            and not args.no_batch1):
+    if (args.full and batching and not poisson and not args.single_engine and D.world == 1 and on_gpu
+            and args.latency_point and not args.no_batch1):
         jb2, pt2, inf2 = (int(v) for v in args.latency_point.split(","))
         pt_head = args.pass_target_us
         args.pass_target_us = pt2
@@ -1040,7 +1110,7 @@ def main():
     # W workers per GPU and with one worker per GPU (north_star's "One Worker
     # per GPU via worker_device_queue")
     single_1wpg = None
-    if D.world == 1 and W != 1 and not args.no_single_engine and not poisson and on_gpu and batching:
+    if args.full and D.world == 1 and W != 1 and not args.no_single_engine and not poisson and on_gpu and batching:
         # N = 1: the headline engine IS the single engine; north_star's one
         # GPU worker per GPU (worker_device_queue) is measured beside it
         single_1wpg = single_engine_line(args, D, paths, sched, 1, 1, n_warm, n_timed, names=[m[0] for m in models])
@@ -1053,13 +1123,13 @@ def main():
             except Exception as ex:  # the per-process line stays the headline
                 single = {"error": repr(ex)}
                 print("bench: single-engine line failed: %r" % (ex,), file=sys.stderr, flush=True)
-            if W != 1 and "error" not in single:
+            if args.full and W != 1 and "error" not in single:
                 single_1wpg = single_engine_line(args, D, paths, sched, 1, D.world, n_warm, n_timed * D.world,
                                                   names=[m[0] for m in models])
         D.barrier()
 
     roof, dev = None, None
-    if on_gpu and D.rank == 0 and not args.no_roofline:
+    if args.full and on_gpu and D.rank == 0 and not args.no_roofline:
         roof, dev, _ = profile_roofline(args, D, models, paths)
         # the same kernel-time figure at the pass size the timed loop really
         # ran (mean jobs per worker pass), not only at full B-job passes
@@ -1076,7 +1146,7 @@ def main():
                 dev["gpu_us_per_inference_at_mean_pass"] = dict(pass_batch=b_mean, us=dev["gpu_us_per_inference"])
 
     cpu = None
-    if D.rank == 0 and D.world == 1 and not args.no_cpu_baseline:
+    if args.full and D.rank == 0 and D.world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, models, paths, args.cpu_baseline_seconds)
 
     if D.rank == 0:
@@ -1154,6 +1224,8 @@ def main():
             "host": dict(hinfo, node=platform.node()),
             "host_threads_timed": host_threads,
             "backend_coalescing": dict(COALESCE) if not batching else None,
+            "full": args.full,
+            "outputs_dumped": dict(DUMPED) if args.dump_outputs else None,
         }
         print(json.dumps(line), flush=True)
     for path in paths:

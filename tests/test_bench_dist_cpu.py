@@ -68,8 +68,8 @@ def test_bench_two_ranks_gloo():
 
 
 def test_bench_c1_cpu_worker_line():
-    """C1: MobileNetV1 int8 on one Band CPU worker, fixed_worker"""
-    cmd = [sys.executable, "bench.py", "--device", "cpu", "--model", "mobilenet_v1_int8", "--size", "64",
+    """C1: MobileNetV1 int8 on one Band CPU worker, fixed_worker (--full: with the CPU baseline)"""
+    cmd = [sys.executable, "bench.py", "--full", "--device", "cpu", "--model", "mobilenet_v1_int8", "--size", "64",
            "--workers-per-gpu", "1", "--scheduler", "fixed_worker", "--cpu-threads", "2", "--steps", "8",
            "--warmup", "2", "--cpu-baseline-seconds", "0.5", "--jobs-per-step", "1"]
     r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
@@ -82,6 +82,47 @@ def test_bench_c1_cpu_worker_line():
     # both CPU modes through the Band harness, host facts recorded
     assert [m["workers"] for m in cb["modes"]] == [1, 1] and cb["host"]["nproc"] >= 1
     assert cb["oracle_scalar_port_1core"]["value"] > 0
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """a plain run (no --full) measures only the headline: --steps sets the
+    timed jobs, ms_per_step is their time per step, the lines beside the
+    headline are null; --dump-outputs writes the engine's output tensors as
+    float32 .npy, the same from run to run and equal to the oracle's for the
+    run's seeded request"""
+    import numpy as np
+
+    lines, dumps = [], []
+    for d in ("a", "b"):
+        cmd = [sys.executable, "bench.py", "--gpus", "1", "--device", "cpu", "--model", "mobilenet_v1_int8",
+               "--size", "64", "--workers-per-gpu", "1", "--scheduler", "fixed_worker", "--cpu-threads", "2",
+               "--steps", "3", "--warmup", "1", "--jobs-per-step", "2", "--dump-outputs", str(tmp_path / d)]
+        r = subprocess.run(cmd, cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(_json_line(r.stdout))
+        dumps.append({p.name: np.load(p) for p in sorted((tmp_path / d).iterdir())})
+    line = lines[0]
+    assert line["steps"] == 3 and line["jobs_timed"] == 3 * 2 and line["config"]["jobs_per_worker_rank0"] == [6]
+    assert abs(line["value"] - 6 / (line["ms_per_step"] * 3 / 1e3)) < 1e-6 * line["value"]
+    assert line["full"] is False
+    for key in ("cpu_baseline", "roofline", "band_one_job_per_pass", "latency_point",
+                "single_engine_one_worker_per_gpu"):
+        assert line[key] is None, key
+    assert list(dumps[0]) == ["mobilenet_v1_int8_out0.npy"] == list(line["outputs_dumped"])
+    got = dumps[0]["mobilenet_v1_int8_out0.npy"]
+    assert got.dtype == np.float32 and list(got.shape) == line["outputs_dumped"]["mobilenet_v1_int8_out0.npy"]
+    np.testing.assert_array_equal(got, dumps[1]["mobilenet_v1_int8_out0.npy"])
+    # the run's request: bench.py make_engine, rank 0
+    from band_amd import tflite_synth
+    from oracle.runner import OracleInterpreter
+    from oracle.tflite_fb import Model as OModel
+    om = OModel(tflite_synth.mobilenet_v1(np.int8, seed=0, size=64))
+    t_in = om.tensors[om.inputs[0]]
+    x = np.random.default_rng(5489).integers(-127, 128, t_in.shape).astype(np.int8)
+    ref = OracleInterpreter(om).run({om.inputs[0]: x})[om.outputs[0]]
+    assert got.shape[0] >= 1
+    for job in got:
+        np.testing.assert_array_equal(job.reshape(-1), ref.reshape(-1).astype(np.float32))
 
 
 def test_bench_single_engine_cpu_stand_ins():

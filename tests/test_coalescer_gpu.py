@@ -124,15 +124,22 @@ def test_engine_one_job_per_pass_coalesced_bit_exact(gpu_lib, monkeypatch, sync)
     CoalescerStats(reset=True)
     n_sub, per = 4, 24
     errors = []
+    # every submitter fills its request tensors first and all start together:
+    # the burst then arrives faster than two lanes serve it (filling a tensor
+    # between two requests made the interpreter the bottleneck, and whether
+    # two calls ever queued behind a busy lane a matter of host speed)
+    start = threading.Barrier(n_sub)
 
     def submit(tid):
         try:
-            t = e.CreateInputTensor(m, 0)
+            ts = [e.CreateInputTensor(m, 0) for _ in xs]
+            for t, x in zip(ts, xs):
+                t.data()[...] = x
             o = e.CreateOutputTensor(m, 0)
             hs = []
+            start.wait(timeout=60)
             for j in range(per):
-                t.data()[...] = xs[(tid + j) % 4]
-                hs.append(e.RequestAsync(m, [t]))
+                hs.append(e.RequestAsync(m, [ts[(tid + j) % 4]]))
             for j, h in enumerate(hs):
                 assert h >= 0
                 assert e.Wait(h, [o]) == kBandOk

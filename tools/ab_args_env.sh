@@ -8,7 +8,7 @@ for r in $(seq 1 $ROUNDS); do
   i=0
   for v in "$@"; do
     envs=${v%%--*}; args=${v#*--}
-    env $envs timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-roofline $args > $O/${TAG}_v${i}_r$r.json 2> $O/${TAG}_v${i}_r$r.err || exit $?
+    env $envs timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --no-roofline $args > $O/${TAG}_v${i}_r$r.json 2> $O/${TAG}_v${i}_r$r.err || exit $?
     echo "$TAG v$i ($v) round $r: $(python3 -c "import json;d=json.load(open('$O/${TAG}_v${i}_r$r.json'));h=d['host_threads_timed'];print(round(d['value']), round(d['p99_job_latency_ms'],2), h['worker_phases']['passes'])")"
     i=$((i+1))
   done

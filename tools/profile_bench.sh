@@ -20,7 +20,7 @@ O=$R/gpurun_out
 mkdir -p "$O"
 export BAND_HIP_TUNE_FILE=$O/${TAG}_tune.txt
 rm -f "$BAND_HIP_TUNE_FILE"
-ARGS="--steps 2000 --warmup 200 --workers-per-gpu 1 $*"
+ARGS="--full --steps 2000 --warmup 200 --workers-per-gpu 1 $*"
 timeout -k 10 300 python3 bench.py $ARGS > "$O/${TAG}_bench.json"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/${TAG}_trace" -o run -- \
   python3 bench.py $ARGS --no-graph --no-cpu-baseline --no-batch1 > "$O/${TAG}_bench_profiled.json" 2> "$O/${TAG}_trace.err"

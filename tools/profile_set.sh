@@ -32,10 +32,10 @@ W=$(mktemp -d /tmp/prof_XXXX)
 export BAND_HIP_TUNE_FILE=$O/${TAG}_tune.txt
 rm -f "$BAND_HIP_TUNE_FILE"
 step() { echo "$(date +%T) $*"; }
-timeout -k 10 500 python3 bench.py > "$O/${TAG}_bench_default.json" 2> "$O/${TAG}_bench_default.err" || exit $?
+timeout -k 10 500 python3 bench.py --full > "$O/${TAG}_bench_default.json" 2> "$O/${TAG}_bench_default.err" || exit $?
 step "0 default line done"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$W/${TAG}_full" -o run -- \
-  python3 bench.py --no-cpu-baseline --no-batch1 --no-graph --steps 8 --warmup 2 \
+  python3 bench.py --full --no-cpu-baseline --no-batch1 --no-graph --steps 8 --warmup 2 \
   > "$O/${TAG}_bench_traced.json" 2> "$O/${TAG}_full.err" || exit $?
 python3 tools/timeline_summary.py "$W/${TAG}_full/run_kernel_trace.csv" > "$O/${TAG}_timeline.txt" || exit $?
 step "1 traced graph-replay bench done"
@@ -68,6 +68,6 @@ for d in full po; do cp "$W/${TAG}_$d/run_kernel_stats.csv" "$O/${TAG}_${d}_kern
 rm -rf "$W"
 # the traffic file must sit under profiles/ for bench.py to report it
 cp "$O/${TAG}_pmc_traffic.json" profiles/ || exit $?
-timeout -k 10 500 python3 bench.py > "$O/${TAG}_bench_final.json" 2> "$O/${TAG}_bench_final.err" || exit $?
+timeout -k 10 500 python3 bench.py --full > "$O/${TAG}_bench_final.json" 2> "$O/${TAG}_bench_final.err" || exit $?
 step "7 final default line done"
 echo "profile $TAG done"

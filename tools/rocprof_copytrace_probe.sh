@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 O=gpurun_out; mkdir -p $O
 W=$(mktemp -d /tmp/ct_XXXX)
 env $VAR timeout -k 10 300 rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d "$W/t" -o run -- \
-  python3 bench.py --no-cpu-baseline --no-batch1 --no-roofline --steps 4 --warmup 1 "$@" > "$O/${TAG}.json" 2> "$O/${TAG}.err"
+  python3 bench.py --full --no-cpu-baseline --no-batch1 --no-roofline --steps 4 --warmup 1 "$@" > "$O/${TAG}.json" 2> "$O/${TAG}.err"
 rc=$?
 echo "$TAG ($VAR $*): rc=$rc" | tee -a "$O/${TAG}_summary.txt"
 grep -h "graphs\|SIGSEGV\|bh_graph_launch\|RunDirect\|TimeSubgraph" "$O/${TAG}.err" | head -5 >> "$O/${TAG}_summary.txt"

@@ -19,7 +19,7 @@ n=0
 for TR in "--kernel-trace" "--kernel-trace --memory-copy-trace"; do
   n=$((n + 1))
   timeout -k 10 400 rocprofv3 $TR --stats --output-format csv -d "$W/${TAG}_tr$n" -o run -- \
-    python3 bench.py --no-cpu-baseline --no-batch1 --steps 8 --warmup 2 \
+    python3 bench.py --full --no-cpu-baseline --no-batch1 --steps 8 --warmup 2 \
     > "$O/${TAG}_tr$n.json" 2> "$O/${TAG}_tr$n.err"
   rc=$?
   echo "run $n ($TR, roofline stage on): rc=$rc" >> "$S"
