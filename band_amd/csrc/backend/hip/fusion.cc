@@ -2,8 +2,10 @@
 // independent convs, the inverted-residual block, the fused chains (every
 // form timed on the real buffers, decisions cached per geometry / device and
 // in BAND_HIP_TUNE_FILE), glue-op epilogue folds.  Split from model_executor.cc.
+#include "backend/hip/chain_form.h"
 #include "backend/hip/executor_internal.h"
 #include <mutex>
+#include <optional>
 #include <unordered_map>
 
 namespace band {
@@ -249,47 +251,65 @@ double IrbModelCost(const bh_irb_params& q, int t, size_t lds) {
   return rounds * (work / nw + 8.0);  // + fixed per-workgroup latency
 }
 
-// Measured choices, shared by every executor of the process: one block
-// geometry is timed once per device.  Value: tile edge, or 0 = keep unfused.
+// Measured choices, shared by every executor of the process: one block or
+// chain geometry is timed once per device.  Value: an inverted-residual
+// block's tile edge (0 = keep unfused), a chain's Encode()d form.
+// BAND_HIP_TUNE_FILE: decisions persist across processes ("<key> <value>"
+// lines), so a profiled run replays exactly the launch sequence a timed run
+// chose (the profiler's per-dispatch overhead would otherwise bias a fresh
+// measurement).  Loaded on first use; a key's first decision is appended.
 std::mutex g_tune_mu;
 std::unordered_map<std::string, int> g_tune;
 
-// BAND_HIP_TUNE_FILE: decisions persist across processes ("<key> <tile>"
-// lines), so a profiled run replays exactly the launch sequence a timed run
-// chose (the profiler's per-dispatch overhead would otherwise bias a fresh
-// measurement).  Loaded once; new decisions are appended.
 const char* TuneFile() {
   const char* f = std::getenv("BAND_HIP_TUNE_FILE");
   return f && f[0] ? f : nullptr;
 }
-void LoadTuneFileLocked() {
+std::optional<int> TuneLookup(const std::string& key) {
+  std::lock_guard<std::mutex> lk(g_tune_mu);
   static bool loaded = false;
-  if (loaded) return;
+  FILE* fp = !loaded && TuneFile() ? std::fopen(TuneFile(), "r") : nullptr;
   loaded = true;
-  const char* path = TuneFile();
-  if (!path) return;
-  if (FILE* fp = std::fopen(path, "r")) {
-    char key[256];
-    int tile = 0;
-    while (std::fscanf(fp, "%255s %d", key, &tile) == 2) g_tune[key] = tile;
+  if (fp) {
+    char k[256];
+    int v = 0;
+    while (std::fscanf(fp, "%255s %d", k, &v) == 2) g_tune[k] = v;
     std::fclose(fp);
   }
+  auto it = g_tune.find(key);
+  return it == g_tune.end() ? std::nullopt : std::optional<int>(it->second);
 }
-void AppendTuneFileLocked(const std::string& key, int tile) {
-  const char* path = TuneFile();
-  if (!path) return;
-  if (FILE* fp = std::fopen(path, "a")) {
-    std::fprintf(fp, "%s %d\n", key.c_str(), tile);
+void TuneStore(const std::string& key, int value) {
+  std::lock_guard<std::mutex> lk(g_tune_mu);
+  FILE* fp = !g_tune.count(key) && TuneFile() ? std::fopen(TuneFile(), "a") : nullptr;
+  if (fp) {
+    std::fprintf(fp, "%s %d\n", key.c_str(), value);
     std::fclose(fp);
   }
+  g_tune[key] = value;
 }
+// BAND_HIP_TUNE_LOG=1: every measured form of every chain on stderr
+bool TuneLog() {
+  static const bool on = std::getenv("BAND_HIP_TUNE_LOG") != nullptr;
+  return on;
+}
+
+// The time to beat: fusion must win over the unfused launches by more than
+// 2 % to be taken, and a later candidate must beat the earlier ones.
+struct Fastest {
+  explicit Fastest(double unfused_us) : us(unfused_us * 0.98) {}
+  bool Offer(double t) {  // t <= 0: not measured
+    if (t <= 0 || t >= us) return false;
+    us = t;
+    return true;
+  }
+  double us;
+};
 
 // bumped whenever a chain form's LDS layout or parameter rules change, so a
 // tune file written by an older kernel tree is not replayed against this one
 // (11: column-reuse depthwise phase, every raster form re-measured)
 constexpr int kChainTuneVersion = 12;
-// chain choices from here up name a stage form (FuseChains)
-constexpr int kStageChoice = 100000;
 
 std::string IrbKey(int ordinal, const bh_irb_params& q) {
   char buf[256];
@@ -333,12 +353,7 @@ double HipModelExecutor::TimeLaunches(const std::vector<const Launch*>& ls, int 
 // bh_irb_i8 launch when the intermediates are private to the run.
 void HipModelExecutor::FuseBlocks(const HipModel& model, PreparedSubgraph* sg) {
   const TflModel& d = model.desc();
-  auto private_tensor = [&](int t, int only_consumer) {
-    if (consumers_[t].size() != 1 || consumers_[t][0] != only_consumer) return false;
-    if (sg->no_fuse.count(t) || sg->extra_d2h.count(t)) return false;
-    if (std::find(sg->outputs.begin(), sg->outputs.end(), t) != sg->outputs.end()) return false;
-    return std::find(d.outputs.begin(), d.outputs.end(), t) == d.outputs.end();
-  };
+  auto private_tensor = [&](int t, int only_consumer) { return PrivateTensor(d, *sg, t, only_consumer); };
   std::vector<Launch> out;
   const auto& L = sg->launches;
   for (size_t i = 0; i < L.size(); ++i) {
@@ -405,33 +420,18 @@ void HipModelExecutor::FuseBlocks(const HipModel& model, PreparedSubgraph* sg) {
       // Tile edge: measured on this device when possible (each feasible
       // tile, and the unfused launches, timed on the real buffers; the
       // winner is cached per block geometry), else the static model.
-      int tile = 0;
       bh_irb_params kq = q;
       if (tune_batch_ > 0) kq.batch = tune_batch_;  // a job-batch variant reuses its anchor's choice
       const std::string key = IrbKey(ordinal_, kq);
-      bool cached = false;
-      if (autotune_) {
-        std::lock_guard<std::mutex> lk(g_tune_mu);
-        LoadTuneFileLocked();
-        auto it = g_tune.find(key);
-        if (it != g_tune.end()) {
-          tile = it->second;
-          cached = true;
-        }
-      }
+      const std::optional<int> cached = autotune_ ? TuneLookup(key) : std::nullopt;
+      int tile = cached.value_or(0);
       if (!cached) {
-        double best_model = 1e300, best_us = 1e300;
+        double best_model = 1e300;
         int model_tile = 0;
-        bool measured = autotune_;
-        if (measured) {
-          std::vector<const Launch*> unfused;
-          if (E) unfused.push_back(E);
-          unfused.push_back(&D);
-          unfused.push_back(&P);
-          const double u = TimeLaunches(unfused, 10);
-          measured = u > 0;
-          best_us = u * 0.98;  // fusion must win by > 2% to be taken
-        }
+        std::vector<const Launch*> unfused = {&D, &P};
+        if (E) unfused.insert(unfused.begin(), E);
+        Fastest best(autotune_ ? TimeLaunches(unfused, 10) : -1.0);
+        const bool measured = best.us > 0;
         for (int t = 8; t >= 1; --t) {
           q.tile_h = q.tile_w = t;
           const size_t lds = bh_irb_lds_bytes(&q);
@@ -445,19 +445,11 @@ void HipModelExecutor::FuseBlocks(const HipModel& model, PreparedSubgraph* sg) {
             Launch F;
             F.kind = Launch::kIrb;
             F.irb = q;
-            const double us = TimeLaunches({&F}, 10);
-            if (us > 0 && us < best_us) {
-              best_us = us;
-              tile = t;
-            }
+            if (best.Offer(TimeLaunches({&F}, 10))) tile = t;
           }
         }
         if (!measured) tile = model_tile;
-        if (autotune_ && measured) {
-          std::lock_guard<std::mutex> lk(g_tune_mu);
-          if (!g_tune.count(key)) AppendTuneFileLocked(key, tile);
-          g_tune[key] = tile;
-        }
+        if (measured) TuneStore(key, tile);
       }
       q.tile_h = q.tile_w = tile;
       ok = tile > 0 && bh_irb_lds_bytes(&q) > 0;
@@ -493,26 +485,34 @@ void HipModelExecutor::FuseBlocks(const HipModel& model, PreparedSubgraph* sg) {
 // first conv's output is stored only when something besides the second conv
 // reads it (the next block's residual, a subgraph output).  Taken per run
 // geometry by on-device timing against the unfused launches, as FuseBlocks.
-// The tile form's constant block (bh_chain_tile_pack): built on the device
-// from the chain's filter / table pointers, owned by the subgraph.
-bool HipModelExecutor::PackChainTile(bh_chain_params* q, PreparedSubgraph* sg) {
+// The tile and stage forms' constant block (bh_chain_tile_pack): built on
+// the device from the chain's filter / table pointers.  Its layout depends on
+// the filters and on has_pw2 only, so *blob, packed for the first form of a
+// parameter set that asks, serves every later one.  false: `q`'s form takes
+// no block (each form has its own gate), or the block could not be built.
+bool HipModelExecutor::PackChainTile(bh_chain_params* q, std::shared_ptr<DeviceBlob>* blob) {
   const size_t nb = bh_chain_tile_blob_bytes(q);
   if (nb == 0 || ordinal_ < 0) return false;
-  auto blob = std::make_shared<DeviceBlob>(ordinal_, nb);
-  if (!blob->ok() || bh_chain_tile_pack(q, blob->ptr(), stream_) != 0 || bh_stream_sync(stream_) != 0) return false;
-  q->tile_blob = blob->ptr();
-  sg->consts.push_back(blob);
+  if (!*blob) {
+    auto b = std::make_shared<DeviceBlob>(ordinal_, nb);
+    if (!b->ok() || bh_chain_tile_pack(q, b->ptr(), stream_) != 0 || bh_stream_sync(stream_) != 0) return false;
+    *blob = std::move(b);
+  }
+  q->tile_blob = (*blob)->ptr();
   return true;
+}
+
+// t is read by op `only_consumer` alone and needed by nobody outside the run
+bool HipModelExecutor::PrivateTensor(const TflModel& d, const PreparedSubgraph& sg, int t, int only_consumer) const {
+  if (t < 0 || consumers_[t].size() != 1 || consumers_[t][0] != only_consumer) return false;
+  if (sg.no_fuse.count(t) || sg.extra_d2h.count(t)) return false;
+  if (std::find(sg.outputs.begin(), sg.outputs.end(), t) != sg.outputs.end()) return false;
+  return std::find(d.outputs.begin(), d.outputs.end(), t) == d.outputs.end();
 }
 
 void HipModelExecutor::FuseChains(const HipModel& model, PreparedSubgraph* sg) {
   const TflModel& d = model.desc();
-  auto private_tensor = [&](int t, int only_consumer) {
-    if (t < 0 || consumers_[t].size() != 1 || consumers_[t][0] != only_consumer) return false;
-    if (sg->no_fuse.count(t) || sg->extra_d2h.count(t)) return false;
-    if (std::find(sg->outputs.begin(), sg->outputs.end(), t) != sg->outputs.end()) return false;
-    return std::find(d.outputs.begin(), d.outputs.end(), t) == d.outputs.end();
-  };
+  auto private_tensor = [&](int t, int only_consumer) { return PrivateTensor(d, *sg, t, only_consumer); };
   std::vector<Launch> out;
   const auto& L = sg->launches;
   for (size_t i = 0; i < L.size(); ++i) {
@@ -547,186 +547,70 @@ void HipModelExecutor::FuseChains(const HipModel& model, PreparedSubgraph* sg) {
       out.push_back(L[i]);
       continue;
     }
-    // choice: 0 = unfused, 1/2/4 = px_blocks of the 3-launch form, 11/12/14
-    // = px_blocks of the 2-launch form (the second conv stays a launch),
-    // +100 = 16 waves per workgroup, +200 = persistent form, +300 = 8 waves
+    // `f` on this chain's parameters, with the constant block of its
+    // parameter set when it takes one; false: the form does not apply here
+    std::shared_ptr<DeviceBlob> blob3, blob2;
+    auto instantiate = [&](const ChainForm& f, bh_chain_params* q) {
+      if (f.launches == 3 ? !ok3 : !ok2) return false;
+      *q = f.launches == 3 ? c3 : c2;
+      Apply(f, q);
+      if (bh_chain_lds_bytes(q) == 0) return false;
+      return !(f.tile || f.stage) || PackChainTile(q, f.launches == 3 ? &blob3 : &blob2);
+    };
     char key[256];
     std::snprintf(key, sizeof(key), "ch%d:%d:%d:%dx%dx%d:s%dd%d:%d:%d:%d:%d:f%d%d%d%d", kChainTuneVersion, ordinal_,
-                  tune_batch_ > 0 ? tune_batch_ : D.dw.batch, D.dw.in_h,
-                  D.dw.in_w, D.dw.in_c, D.dw.stride_h, D.dw.dil_h, P1.conv.out_c, P1.conv.residual ? 1 : 0,
-                  ok3 ? c3.pw2.out_c : 0, ok3 && c3.pw1.output ? 1 : 0, no_tile_chain_, no_deep_chain_,
-                  no_split_chain_, no_stage_chain_);
-    int choice = force_chain_ ? (ok3 ? 4 : 14) : -1;
-    if (force_stage_chain_ && ok3) {
-      bh_chain_params q = c3;
-      q.px_blocks = 1;
-      q.waves = 8;
-      q.c_split = 2;
-      q.stage = 1;
-      if (bh_chain_lds_bytes(&q) > 0) choice = kStageChoice + 2 * 100 + 1 * 10 + 1;  // 1 block, 8 waves, 2 slices
-      q.stage = 2;
-      if (bh_chain_lds_bytes(&q) > 0) choice += 1000;  // ... with loader waves
-    }
-    if (force_tile_chain_) {
-      bh_chain_params q = ok3 ? c3 : c2;
-      q.tile = 1;
-      if (bh_chain_lds_bytes(&q) > 0) choice += 400;
-    }
-    if (force_deep_chain_) {
-      bh_chain_params q = ok3 ? c3 : c2;
-      q.px_blocks = 1;
-      q.deep = 1;
-      choice = bh_chain_lds_bytes(&q) > 0 ? (ok3 ? 1001 : 1011) : (ok3 ? 4 : 14);
-    }
-    if (autotune_ && choice < 0) {
-      std::lock_guard<std::mutex> lk(g_tune_mu);
-      LoadTuneFileLocked();
-      auto it = g_tune.find(key);
-      if (it != g_tune.end()) choice = it->second;
-    }
-    if (choice < 0) {
-      choice = 0;
-      bool measured = autotune_;
-      if (measured) {
-        std::vector<const Launch*> base = {&D, &P1};
-        if (ok3) base.push_back(P2);
-        const double u = TimeLaunches(base, 10);
-        const double u_p2 = ok3 ? TimeLaunches({P2}, 10) : 0.0;
-        measured = u > 0 && u_p2 >= 0;
-        // BAND_HIP_TUNE_LOG=1: every measured form of every chain on stderr
-        static const bool tune_log = std::getenv("BAND_HIP_TUNE_LOG") != nullptr;
-        if (tune_log) std::fprintf(stderr, "[chain-tune] %s unfused %.2f (pw2 %.2f)\n", key, u, u_p2);
-        double best = u * 0.98;  // fusion must win by > 2% to be taken
-        // (px_blocks, waves): 64 / 32 / 16 pixels per 4-wave workgroup, or
-        // 16 pixels over 16 waves (few-pixel, many-channel layers)
-        // {px_blocks, waves, persist}: the last is the persistent form
-        // (filters in LDS, 64-pixel blocks walked by one wave of workgroups)
-        // {.., tile}: the 2-D tile form (8 x 8 pixels, one LDS-DMA burst)
-        // {.., deep}: the deep-issue raster forms
-        // {.., tile 3 / 4}: runs of 2 / 4 tiles per workgroup, the constant
-        // block staged once per run
-        // {.., split}: the second 1x1's channel tiles over 2..4 workgroups
-        // per pixel block (3-launch form only; BAND_HIP_FUSION=nosplit: none)
-        const int forms[19][6] = {
-            {4, 4, 0, 0, 0, 0}, {2, 4, 0, 0, 0, 0}, {1, 4, 0, 0, 0, 0}, {1, 8, 0, 0, 0, 0},
-            {1, 16, 0, 0, 0, 0}, {4, 4, 1, 0, 0, 0}, {4, 4, 0, 1, 0, 0}, {4, 4, 0, 3, 0, 0},
-            {4, 4, 0, 4, 0, 0}, {2, 4, 0, 0, 1, 0}, {1, 4, 0, 0, 1, 0}, {1, 8, 0, 0, 1, 0},
-            {1, 4, 0, 0, 0, 2}, {1, 8, 0, 0, 0, 2}, {2, 4, 0, 0, 0, 2}, {1, 16, 0, 0, 0, 2},
-            {1, 4, 0, 0, 0, 3}, {1, 8, 0, 0, 0, 3}, {1, 4, 0, 0, 0, 4}};
-        // the stage forms (3-launch only): {px_blocks, waves, phase-C slices,
-        // stage (2: loader waves)}
-        const int stage_forms[16][4] = {{1, 4, 0, 1}, {1, 8, 0, 1}, {2, 4, 0, 1}, {2, 8, 0, 1}, {1, 8, 2, 1},
-                                        {2, 8, 2, 1}, {1, 8, 4, 1}, {1, 8, 8, 1}, {1, 8, 0, 2}, {2, 8, 0, 2},
-                                        {1, 4, 0, 2}, {1, 8, 2, 2}, {2, 8, 2, 2}, {1, 8, 3, 2}, {1, 8, 4, 2},
-                                        {1, 8, 8, 2}};
-        for (const auto& sf : stage_forms) {
-          if (no_stage_chain_ || !ok3 || !measured) break;
-          bh_chain_params q = c3;
-          q.px_blocks = sf[0];
-          q.waves = sf[1];
-          q.c_split = sf[2];
-          q.stage = sf[3];
-          if (bh_chain_lds_bytes(&q) == 0 || !PackChainTile(&q, sg)) continue;
+                  tune_batch_ > 0 ? tune_batch_ : D.dw.batch, D.dw.in_h, D.dw.in_w, D.dw.in_c, D.dw.stride_h, D.dw.dil_h,
+                  P1.conv.out_c, P1.conv.residual ? 1 : 0, ok3 ? c3.pw2.out_c : 0, ok3 && c3.pw1.output ? 1 : 0,
+                  no_tile_chain_, no_deep_chain_, no_split_chain_, no_stage_chain_);
+    const bool forced = forced_chain_ != ForcedChain::kNone;
+    const std::optional<int> cached = autotune_ && !forced ? TuneLookup(key) : std::nullopt;
+    ChainForm form = kUnfused;
+    if (forced) {
+      form = ForcedForm(forced_chain_, ok3 ? c3 : c2);
+    } else if (cached) {
+      Decode(*cached, &form);  // an integer no form encodes to (another kernel tree's tune file): unfused
+    } else {
+      std::vector<const Launch*> base = {&D, &P1};
+      if (ok3) base.push_back(P2);
+      double u = -1.0, u_p2 = 0.0;
+      if (autotune_) {
+        u = TimeLaunches(base, 10);
+        if (ok3) u_p2 = TimeLaunches({P2}, 10);
+        if (TuneLog()) std::fprintf(stderr, "[chain-tune] %s unfused %.2f (pw2 %.2f)\n", key, u, u_p2);
+      }
+      const bool measured = u > 0 && u_p2 >= 0;
+      Fastest best(u);
+      for (ChainForm f : kChainForms) {
+        if (!measured || FilteredOut(f, no_tile_chain_, no_deep_chain_, no_split_chain_, no_stage_chain_)) continue;
+        for (f.launches = 3; f.launches >= 2; --f.launches) {
           Launch F;
           F.kind = Launch::kChain;
-          F.chain = q;
+          if (!HasLaunches(f, f.launches) || !instantiate(f, &F.chain)) continue;
           const double us = TimeLaunches({&F}, 10);
-          if (tune_log)
-            std::fprintf(stderr, "[chain-tune]   form3 stage%d px%d w%d split%d: %.2f\n", sf[3], sf[0], sf[1], sf[2],
-                         us);
-          if (us > 0 && us < best) {
-            best = us;
-            choice = kStageChoice + (sf[3] - 1) * 1000 + sf[2] * 100 + sf[0] * 10 + (sf[1] == 8 ? 1 : 0);
-          }
-        }
-        for (const auto& pw : forms) {
-          if (pw[3] && no_tile_chain_) continue;
-          if (pw[4] && no_deep_chain_) continue;
-          if (pw[5] && no_split_chain_) continue;
-          for (int form = 0; form < 2 && measured; ++form) {
-            bh_chain_params q = form == 0 ? c3 : c2;
-            if (form == 0 ? !ok3 : !ok2) continue;
-            q.px_blocks = pw[0];
-            q.waves = pw[1];
-            q.persist = pw[2];
-            q.tile = pw[3];
-            q.deep = pw[4];
-            q.c_split = pw[5];
-            if (pw[5] > 1 && form != 0) continue;
-            if (bh_chain_lds_bytes(&q) == 0) continue;
-            if (q.tile && !PackChainTile(&q, sg)) continue;
-            Launch F;
-            F.kind = Launch::kChain;
-            F.chain = q;
-            const double us = TimeLaunches({&F}, 10);
-            const double total = us + (form == 1 && ok3 ? u_p2 : 0.0);
-            if (tune_log)
-              std::fprintf(stderr, "[chain-tune]   form%d px%d w%d persist%d tile%d deep%d split%d: %.2f\n", 3 - form,
-                           pw[0], pw[1], pw[2], pw[3], pw[4], pw[5], total);
-            if (us > 0 && total < best) {
-              best = total;
-              choice = (form == 0 ? 0 : 10) + pw[0] + (pw[1] == 16 ? 100 : 0) + (pw[1] == 8 ? 300 : 0) +
-                       (pw[2] ? 200 : 0) + (pw[3] == 1 ? 400 : 0) + (pw[3] == 3 ? 600 : 0) +
-                       (pw[3] == 4 ? 700 : 0) + (pw[4] ? 1000 : 0) + (pw[5] > 1 ? 2000 * (pw[5] - 1) : 0);
-            }
-          }
+          // the 2-launch form leaves the second 1x1 a launch of its own
+          const double total = us + (f.launches == 2 && ok3 ? u_p2 : 0.0);
+          if (TuneLog() && f.stage)
+            std::fprintf(stderr, "[chain-tune]   form3 stage%d px%d w%d split%d: %.2f\n", f.stage, f.px_blocks, f.waves,
+                         f.c_split, us);
+          else if (TuneLog())
+            std::fprintf(stderr, "[chain-tune]   form%d px%d w%d persist%d tile%d deep%d split%d: %.2f\n", f.launches,
+                         f.px_blocks, f.waves, f.persist, f.tile, f.deep, f.c_split, total);
+          if (best.Offer(us > 0 ? total : us)) form = f;
         }
       }
-      if (!measured) choice = ok3 ? 4 : 14;  // no device timing: the 3-launch form when it applies
-      if (measured && std::getenv("BAND_HIP_TUNE_LOG")) std::fprintf(stderr, "[chain-tune] %s -> %d\n", key, choice);
-      if (autotune_ && measured) {
-        std::lock_guard<std::mutex> lk(g_tune_mu);
-        if (!g_tune.count(key)) AppendTuneFileLocked(key, choice);
-        g_tune[key] = choice;
-      }
-    }
-    // choice: px_blocks, +10 for the 2-launch form, +100 for 16 waves,
-    // +200 for the persistent form, +300 for 8 waves, +400 for the tile
-    // form, +600 / +700 for runs of 2 / 4 tiles, +1000 for the deep-issue
-    // form, +2000 x (s - 1) for the s-way phase-C split; the stage form is
-    // kStageChoice + 1000 x (stage - 1) + 100 x slices + 10 x px_blocks + (8 waves)
-    int stage = choice >= kStageChoice ? 1 : 0;
-    int stage_split = 0, stage_px = 1, stage_waves = 4;
-    if (stage) {
-      int c = choice - kStageChoice;
-      stage = 1 + c / 1000;
-      c %= 1000;
-      stage_split = c / 100;
-      stage_px = (c / 10) % 10;
-      stage_waves = c % 10 ? 8 : 4;
-      choice = 1;  // a 3-launch form
-    }
-    const int c_split = choice >= 2000 ? choice / 2000 + 1 : 0;
-    choice %= 2000;
-    const int deep = choice >= 1000 ? 1 : 0;
-    choice %= 1000;
-    const bool three = choice > 0 && choice % 100 < 10;
-    if (choice == 0 || (three && !ok3) || (!three && !ok2)) {
-      out.push_back(L[i]);
-      continue;
+      if (measured && TuneLog()) std::fprintf(stderr, "[chain-tune] %s -> %d\n", key, Encode(form));
+      if (measured) TuneStore(key, Encode(form));
+      else form = ForcedForm(ForcedChain::kPlain, ok3 ? c3 : c2);  // no device timing: 3 launches when they apply
     }
     Launch F;
     F.kind = Launch::kChain;
     F.op_index = D.op_index;
-    F.chain = three ? c3 : c2;
-    F.chain.px_blocks = choice % 10;
-    F.chain.waves = choice >= 300 && choice < 400 ? 8 : (choice >= 100 && choice < 200 ? 16 : 4);
-    F.chain.persist = choice >= 200 && choice < 300 ? 1 : 0;
-    F.chain.tile = choice >= 400 && choice < 800 ? choice / 100 - 3 : 0;
-    F.chain.deep = deep;
-    F.chain.c_split = c_split;
-    if (stage) {
-      F.chain.px_blocks = stage_px;
-      F.chain.waves = stage_waves;
-      F.chain.c_split = stage_split;
-      F.chain.stage = stage;
-    }
-    // a choice read from a tune file written by another kernel tree may name
-    // a form these parameters do not admit: keep the unfused launches then
-    if (bh_chain_lds_bytes(&F.chain) == 0 || ((F.chain.tile || F.chain.stage) && !PackChainTile(&F.chain, sg))) {
+    if (form.launches == 0 || !instantiate(form, &F.chain)) {
       out.push_back(L[i]);
       continue;
     }
+    if (F.chain.tile_blob) sg->consts.push_back(form.launches == 3 ? blob3 : blob2);  // owned by the subgraph
+    const bool three = form.launches == 3;
     F.out_tensor = three ? P2->out_tensor : P1.out_tensor;
     F.kernel = F.chain.stage ? "chain_stage_kernel" : (F.chain.tile ? "chain_tile_kernel" : "chain_kernel");
     const bh_dwconv_params& dw = F.chain.dw;

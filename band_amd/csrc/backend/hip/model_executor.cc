@@ -290,13 +290,13 @@ absl::Status HipModelExecutor::EnsureMeta(const HipModel& model) {
   if (f && std::strcmp(f, "noadd") == 0) allow_add_ = false;
   if (f && std::strcmp(f, "nochain") == 0) allow_chain_ = false;
   if (f && std::strcmp(f, "nogroup") == 0) allow_group_ = false;
-  if (f && std::strcmp(f, "forcechain") == 0) force_chain_ = true;  // parity tests: every feasible chain
-  if (f && std::strcmp(f, "forcetile") == 0) force_chain_ = force_tile_chain_ = true;  // ... in the tile form
+  if (f && std::strcmp(f, "forcechain") == 0) forced_chain_ = ForcedChain::kPlain;  // parity tests: every feasible chain
+  if (f && std::strcmp(f, "forcetile") == 0) forced_chain_ = ForcedChain::kTile;  // ... in the tile form
   if (f && std::strcmp(f, "notile") == 0) no_tile_chain_ = true;  // A-B: the raster chain forms only
   if (f && std::strcmp(f, "nodeep") == 0) no_deep_chain_ = true;  // A-B: without the deep-issue forms
   if (f && std::strcmp(f, "nosplit") == 0) no_split_chain_ = true;  // A-B: without the phase-C split forms
-  if (f && std::strcmp(f, "forcedeep") == 0) force_deep_chain_ = true;  // parity tests: deep form wherever it fits
-  if (f && std::strcmp(f, "forcestage") == 0) force_chain_ = force_stage_chain_ = true;  // parity: ... stage form
+  if (f && std::strcmp(f, "forcedeep") == 0) forced_chain_ = ForcedChain::kDeep;  // ... in the deep form
+  if (f && std::strcmp(f, "forcestage") == 0) forced_chain_ = ForcedChain::kStage;  // ... in the stage form
   if (f && std::strcmp(f, "nostage") == 0) no_stage_chain_ = true;  // A-B: without the stage forms
   const char* at = std::getenv("BAND_HIP_AUTOTUNE");
   if (at && at[0] == '0') autotune_ = false;

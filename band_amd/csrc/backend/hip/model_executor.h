@@ -24,6 +24,7 @@
 #include <string>
 #include <vector>
 
+#include "backend/hip/chain_form.h"
 #include "backend/hip/coalescer.h"
 #include "backend/hip/cpu_kernels.h"
 #include "backend/hip/device.h"
@@ -202,7 +203,8 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   bool TryFuseResidualAdd(const HipModel& model, int conv_op, PreparedSubgraph* sg, Launch* l);
   void FuseBlocks(const HipModel& model, PreparedSubgraph* sg);
   // dw3x3 -> conv1x1 [+ADD] [-> conv1x1] runs into one bh_chain_i8 launch
-  bool PackChainTile(bh_chain_params* q, PreparedSubgraph* sg);
+  bool PackChainTile(bh_chain_params* q, std::shared_ptr<DeviceBlob>* blob);
+  bool PrivateTensor(const TflModel& d, const PreparedSubgraph& sg, int t, int only_consumer) const;
   void FuseChains(const HipModel& model, PreparedSubgraph* sg);
   // 8-bit unary table ops into the producing conv / FC / depthwise epilogue;
   // CONCATENATION with outer size 1 elided (producers write their slices)
@@ -267,13 +269,12 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   bool allow_add_ = true;
   bool allow_chain_ = true;   // BAND_HIP_FUSION=nochain
   bool allow_group_ = true;   // BAND_HIP_FUSION=nogroup: one launch per conv
-  bool force_chain_ = false;  // BAND_HIP_FUSION=forcechain
-  bool force_tile_chain_ = false;  // BAND_HIP_FUSION=forcetile: every feasible chain in the tile form
+  // BAND_HIP_FUSION=forcechain / forcetile / forcedeep / forcestage (parity
+  // tests): every feasible chain fused, in the named form where that fits
+  ForcedChain forced_chain_ = ForcedChain::kNone;
   bool no_tile_chain_ = false;     // BAND_HIP_FUSION=notile: the tuner skips the tile form
   bool no_deep_chain_ = false;     // BAND_HIP_FUSION=nodeep: the tuner skips the deep-issue forms
   bool no_split_chain_ = false;    // BAND_HIP_FUSION=nosplit: the tuner skips the phase-C split forms
-  bool force_deep_chain_ = false;  // BAND_HIP_FUSION=forcedeep: every feasible chain in the deep form
-  bool force_stage_chain_ = false; // BAND_HIP_FUSION=forcestage: every chain the stage form takes, in it (parity)
   bool no_stage_chain_ = false;    // BAND_HIP_FUSION=nostage: the tuner skips the stage forms
   bool autotune_ = true;  // BAND_HIP_AUTOTUNE=0: pick fused tiles by the static model
   std::map<SubgraphKey, std::unique_ptr<PreparedSubgraph>> subgraphs_;

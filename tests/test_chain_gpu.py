@@ -8,7 +8,10 @@ against the oracle running the TFLite ops one by one.  Bit-exact:
 * executor level: the C3 mix models at 224x224 with every feasible chain
   forced (BAND_HIP_FUSION=forcechain), one-job and job-batched passes.
 """
+import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -358,3 +361,52 @@ def test_chain_tile_ragged_models(gpu_lib, monkeypatch, arch, size):
             got = ex.GetJobSlotView(key, o, 3, s_).GetData()
             np.testing.assert_array_equal(got, refs[s_][o].reshape(got.shape), err_msg="%s slot %d" % (arch, s_))
     ex._model_ref = m
+
+
+_TUNE_CHILD = """
+import json, sys
+import numpy as np
+sys.path.insert(0, %r)
+from band_amd import DeviceFlag, HipModel, HipModelExecutor, SubgraphKey, tflite_synth as S
+from oracle.runner import OracleInterpreter
+from oracle.tflite_fb import Model as OModel
+buf = S.mobilenet_v2(np.int8, size=96)
+om = OModel(buf)
+x = np.random.default_rng(96).integers(-128, 128, om.tensors[om.inputs[0]].shape).astype(np.int8)
+ref = OracleInterpreter(om).run({om.inputs[0]: x})
+m = HipModel(45)
+assert m.FromBuffer(buf).ok()
+ex = HipModelExecutor(45, 1, DeviceFlag.kGPU)
+assert ex.PrepareSubgraph(m).ok()
+key = SubgraphKey(45, 1)
+print("KERNELS " + json.dumps([r["kernel"] for r in ex.ProfileSubgraph(key, iters=1)]))
+ex.GetTensorView(key, om.inputs[0]).GetData()[...] = x
+assert ex.ExecuteSubgraph(key).ok()
+for o in om.outputs:
+    got = ex.GetTensorView(key, o).GetData()
+    np.testing.assert_array_equal(got, ref[o].reshape(got.shape))
+print("BITEXACT")
+"""
+
+
+def test_chain_tune_file_replay(gpu_lib, tmp_path):
+    """BAND_HIP_TUNE_FILE end to end, in two fresh processes sharing one file:
+    the first tunes MobileNetV2 at 96 x 96 (layers 48 / 24 / 12 / 6 / 3: ragged
+    against 8 x 8 tiles and 16-pixel blocks) and writes its decisions, the
+    second replays every one of them - the same kernel sequence, the file
+    left byte for byte as it was - and both are bit-exact against the oracle"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    tune = tmp_path / "tune.txt"
+    env = {k: v for k, v in os.environ.items() if k not in ("BAND_HIP_FUSION", "BAND_HIP_AUTOTUNE")}
+    env["BAND_HIP_TUNE_FILE"] = str(tune)
+    kernels, files = [], []
+    for run in range(2):  # the second starts only after the first has passed
+        r = subprocess.run([sys.executable, "-c", _TUNE_CHILD % root], env=env, capture_output=True, text=True,
+                           timeout=300)
+        assert r.returncode == 0, "process %d:\n%s" % (run + 1, r.stderr[-3000:])
+        assert "BITEXACT" in r.stdout
+        kernels.append([json.loads(ln[8:]) for ln in r.stdout.splitlines() if ln.startswith("KERNELS ")][0])
+        files.append(tune.read_bytes())
+    assert any(ln.startswith(b"ch12:") for ln in files[0].splitlines()), files[0][:400]
+    assert kernels[1] == kernels[0]
+    assert files[1] == files[0]
