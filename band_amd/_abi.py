@@ -86,6 +86,17 @@ class MeanParams(ctypes.Structure):
         (n, c_int32) for n in ("multiplier", "shift", "bias")] + [("input", c_void_p), ("output", c_void_p)]
 
 
+class DetectionParams(ctypes.Structure):
+    _fields_ = [(n, c_int) for n in ("batch", "num_boxes", "num_classes", "num_classes_with_background",
+                                     "max_detections")] + [
+        (n, ctypes.c_float) for n in ("score_threshold", "iou_threshold", "scale_y", "scale_x", "scale_h",
+                                      "scale_w")] + [
+        ("box_type", c_int), ("score_type", c_int), ("box_scale", ctypes.c_float), ("score_scale", ctypes.c_float),
+        ("box_zp", c_int32), ("score_zp", c_int32)] + [
+        (n, c_void_p) for n in ("box_encodings", "class_scores", "anchors", "out_boxes", "out_classes",
+                                "out_scores", "out_num", "scratch")]
+
+
 class ChainParams(ctypes.Structure):
     _fields_ = [("dw", DwConvParams), ("pw1", ConvParams), ("pw2", ConvParams), ("has_pw2", c_int),
                 ("px_blocks", c_int), ("waves", c_int), ("persist", c_int), ("tile", c_int),
@@ -239,6 +250,8 @@ KERNEL_SYMBOLS = {
     "bh_irb_lds_bytes": (c_size_t, [ctypes.POINTER(IrbParams)]),
     "bh_chain_i8": (c_int, [ctypes.POINTER(ChainParams), c_void_p]),
     "bh_mean": (c_int, [ctypes.POINTER(MeanParams), c_void_p]),
+    "bh_detection_scratch_bytes": (c_size_t, [c_int, c_int]),
+    "bh_detection_postprocess": (c_int, [ctypes.POINTER(DetectionParams), c_void_p]),
     "bh_chain_lds_bytes": (c_size_t, [ctypes.POINTER(ChainParams)]),
     "bh_chain_tile_lds_bytes": (c_size_t, [ctypes.POINTER(ChainParams)]),
     "bh_chain_tile_launch": (c_int, [ctypes.POINTER(ChainParams), c_void_p]),

@@ -272,8 +272,12 @@ inline bool MeanArgs(const TflModel& m, const TflOperator& op, long* outer, long
   return *reduce > 0 && out.num_elements() == static_cast<size_t>(*outer * *inner);
 }
 
-// TFLite_Detection_PostProcess in the form the host kernel implements
-inline bool DetectionSupported(const TflModel& m, const TflOperator& op, CpuDetectionParams* p) {
+// TFLite_Detection_PostProcess in the form the host kernel and the device
+// kernels (kernels/detection.hip) implement.  batch: the images of a
+// job-batch variant (the leading dimension of the op's tensors; the anchors
+// are shared) - without it only one image is accepted.
+inline bool DetectionSupported(const TflModel& m, const TflOperator& op, CpuDetectionParams* p,
+                               int* batch = nullptr) {
   if (op.builtin != kTflCustom || op.custom_code != "TFLite_Detection_PostProcess") return false;
   if (op.inputs.size() != 3 || op.outputs.size() != 4) return false;
   for (int t : op.inputs)
@@ -288,11 +292,13 @@ inline bool DetectionSupported(const TflModel& m, const TflOperator& op, CpuDete
   if (!f.Parse(op.custom_options, op.custom_options_size)) return false;
   if (f.Number("use_regular_nms", 0) != 0 || f.Number("max_classes_per_detection", 1) != 1) return false;
   const int n = an.shape.empty() ? 0 : an.shape[0];
-  if (n <= 0 || be.num_elements() != static_cast<size_t>(n) * 4 || cs.num_elements() % n) return false;
+  if (n <= 0 || be.num_elements() == 0 || be.num_elements() % (static_cast<size_t>(n) * 4)) return false;
+  const size_t images = be.num_elements() / (static_cast<size_t>(n) * 4);
+  if ((images != 1 && !batch) || images > (1u << 16) || cs.num_elements() % (images * n)) return false;
   CpuDetectionParams d{};
   d.num_boxes = n;
   d.num_classes = static_cast<int>(f.Number("num_classes", 0));
-  d.num_classes_with_background = static_cast<int>(cs.num_elements() / n);
+  d.num_classes_with_background = static_cast<int>(cs.num_elements() / (images * n));
   d.max_detections = static_cast<int>(f.Number("max_detections", 0));
   // options are read with AsFloat (float), detection_postprocess.cc Init()
   d.score_threshold = static_cast<float>(f.Number("nms_score_threshold", 0));
@@ -304,8 +310,12 @@ inline bool DetectionSupported(const TflModel& m, const TflOperator& op, CpuDete
   if (d.num_classes <= 0 || d.num_classes > d.num_classes_with_background || d.max_detections <= 0) return false;
   for (int k = 0; k < 4; ++k)
     if (m.tensors[op.outputs[k]].type != DataType::kFloat32) return false;
-  if (m.tensors[op.outputs[0]].num_elements() != static_cast<size_t>(d.max_detections) * 4) return false;
+  const size_t rows = images * static_cast<size_t>(d.max_detections);
+  if (m.tensors[op.outputs[0]].num_elements() != rows * 4 || m.tensors[op.outputs[1]].num_elements() != rows ||
+      m.tensors[op.outputs[2]].num_elements() != rows || m.tensors[op.outputs[3]].num_elements() != images)
+    return false;
   if (p) *p = d;
+  if (batch) *batch = static_cast<int>(images);
   return true;
 }
 

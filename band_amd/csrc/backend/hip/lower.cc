@@ -627,14 +627,102 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
   }
 }
 
+bool HipModelExecutor::DequantFoldsIntoDetection(const TflModel& d, const PreparedSubgraph& sg, int oi) const {
+  if (device_flag_ != DeviceFlag::kGPU || !gpu_detection_ || !allow_fusion_) return false;
+  const TflOperator& op = d.ops[oi];
+  if (op.builtin != kTflDequantize || op.inputs.empty() || op.inputs[0] < 0 || op.outputs.empty()) return false;
+  const TflTensor& in = d.tensors[op.inputs[0]];
+  const int t = op.outputs[0];
+  // the byte maximum is the float maximum only for an increasing dequantisation
+  if (t < 0 || !IsQ8(in.type) || !HasQ(in) || !(Scale(in) > 0.0f) || d.tensors[t].type != DataType::kFloat32)
+    return false;
+  if (consumers_[t].size() != 1) return false;
+  const int j = consumers_[t][0];
+  if (!std::binary_search(sg.ops.begin(), sg.ops.end(), j)) return false;
+  int batch = 1;
+  const TflOperator& det = d.ops[j];
+  if (!DetectionSupported(d, det, nullptr, &batch) || (det.inputs[0] != t && det.inputs[1] != t)) return false;
+  if (sg.no_fuse.count(t) || sg.extra_d2h.count(t)) return false;
+  if (std::find(sg.outputs.begin(), sg.outputs.end(), t) != sg.outputs.end()) return false;
+  return std::find(d.outputs.begin(), d.outputs.end(), t) == d.outputs.end();
+}
+
+absl::Status HipModelExecutor::LowerDetectionGpu(const HipModel& model, int oi, PreparedSubgraph* sg, Launch* L) {
+  const TflModel& d = model.desc();
+  const TflOperator& op = d.ops[oi];
+  CpuDetectionParams c{};
+  int batch = 1;
+  if (!gpu_detection_ || !DetectionSupported(d, op, &c, &batch))
+    return absl::InternalError("unsupported custom op " + op.custom_code);
+  bh_detection_params& p = L->detg;
+  p = bh_detection_params{};
+  p.batch = batch;
+  p.num_boxes = c.num_boxes;
+  p.num_classes = c.num_classes;
+  p.num_classes_with_background = c.num_classes_with_background;
+  p.max_detections = c.max_detections;
+  p.score_threshold = c.score_threshold;
+  p.iou_threshold = c.iou_threshold;
+  p.scale_y = c.scale_y; p.scale_x = c.scale_x; p.scale_h = c.scale_h; p.scale_w = c.scale_w;
+  double bytes = 0;
+  // box encodings / class scores: the float tensor, or the 8-bit input of
+  // the DEQUANTIZE that produces it when that op was folded away
+  auto source = [&](int t, int* type, float* scale, int32_t* zp, const void** ptr) -> absl::Status {
+    int src = t;
+    const int prod = producer_[t];
+    if (prod >= 0 && DequantFoldsIntoDetection(d, *sg, prod)) {
+      src = d.ops[prod].inputs[0];
+      const TflTensor& q = d.tensors[src];
+      *type = q.type == DataType::kInt8 ? 1 : 2;
+      *scale = Scale(q);
+      *zp = Zp(q);
+    }
+    void* dev = nullptr;
+    RETURN_STATUS_IF(DevicePtr(model, src, sg, &dev));
+    *ptr = dev;
+    bytes += static_cast<double>(meta_[src]->bytes);
+    return absl::OkStatus();
+  };
+  RETURN_STATUS_IF(source(op.inputs[0], &p.box_type, &p.box_scale, &p.box_zp, &p.box_encodings));
+  RETURN_STATUS_IF(source(op.inputs[1], &p.score_type, &p.score_scale, &p.score_zp, &p.class_scores));
+  void* anchors = nullptr;
+  void* outs[4];
+  RETURN_STATUS_IF(DevicePtr(model, op.inputs[2], sg, &anchors));
+  for (int k = 0; k < 4; ++k) {
+    RETURN_STATUS_IF(DevicePtr(model, op.outputs[k], sg, &outs[k]));
+    bytes += static_cast<double>(meta_[op.outputs[k]]->bytes);
+  }
+  bytes += 16.0 * c.num_boxes;
+  p.anchors = static_cast<const float*>(anchors);
+  p.out_boxes = static_cast<float*>(outs[0]);
+  p.out_classes = static_cast<float*>(outs[1]);
+  p.out_scores = static_cast<float*>(outs[2]);
+  p.out_num = static_cast<float*>(outs[3]);
+  // the kernels' scratch, sized here and owned by the subgraph; every pass
+  // rewrites what it reads of it
+  auto scratch = std::make_shared<DeviceBlob>(ordinal_, bh_detection_scratch_bytes(batch, c.num_boxes));
+  if (!scratch->ok()) return absl::InternalError("HBM scratch allocation failed");
+  sg->consts.push_back(scratch);
+  p.scratch = scratch->ptr();
+  L->kind = Launch::kDetectionGpu;
+  L->kernel = "detection_postprocess_kernel";
+  L->alg_bytes = bytes;
+  return absl::OkStatus();
+}
+
 absl::Status HipModelExecutor::Lower(const HipModel& model, int oi, PreparedSubgraph* sg) {
   const TflModel& d = model.desc();
   const TflOperator& op = d.ops[oi];
   std::string why;
   const bool cpu = device_flag_ == DeviceFlag::kCPU;
-  if (!(cpu ? CpuSupports(d, op, &why) : GpuSupports(d, op, &why)))
+  if (!(cpu ? CpuSupports(d, op, &why) : GpuSupportsHere(d, op, &why)))
     return absl::InternalError("HIP backend cannot run op " + std::to_string(oi) + " (" +
                                TflBuiltinName(op.builtin) + ") on " + ToString(device_flag_) + ": " + why);
+  if (DequantFoldsIntoDetection(d, *sg, oi)) {
+    // the detection kernels read the 8-bit tensor: no launch, no float tensor
+    sg->fused_tensors.insert(op.outputs[0]);
+    return absl::OkStatus();
+  }
   auto T = [&](int i) -> const TflTensor& { return d.tensors[i]; };
   const TflTensor& in = T(op.inputs[0]);
   const TflTensor& out = T(op.outputs[0]);
@@ -862,8 +950,10 @@ absl::Status HipModelExecutor::Lower(const HipModel& model, int oi, PreparedSubg
     L.kind = Launch::kPool;
     L.kernel = "pool_kernel";
     L.alg_bytes = static_cast<double>(in.num_elements() + out.num_elements());
+  } else if (op.builtin == kTflCustom && !cpu) {
+    RETURN_STATUS_IF(LowerDetectionGpu(model, oi, sg, &L));
   } else if (op.builtin == kTflCustom) {
-    // TFLite_Detection_PostProcess (CPU worker only: CpuSupports)
+    // TFLite_Detection_PostProcess on the CPU worker (CpuSupports)
     CpuDetectionParams& p = L.det;
     if (!DetectionSupported(d, op, &p)) return absl::InternalError("unsupported custom op " + op.custom_code);
     void* scores = nullptr;

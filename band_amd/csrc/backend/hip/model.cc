@@ -2,6 +2,8 @@
 
 #include <cstdio>
 
+#include "backend/hip/executor_internal.h"
+
 namespace band {
 namespace hip {
 
@@ -50,11 +52,12 @@ absl::Status HipModel::FromBuffer(const char* buffer, size_t buffer_size) {
   return s.ok() ? s : absl::InternalError("Cannot load from buffer.");
 }
 
-absl::Status HipModel::CloneWithJobBatch(int batch, std::unique_ptr<HipModel>* out) const {
+absl::Status HipModel::CloneWithJobBatch(int batch, std::unique_ptr<HipModel>* out, bool gpu_detection) const {
   if (!initialized_) return absl::InternalError("job batching: model not loaded");
   if (batch < 1) return absl::InternalError("job batching: batch must be >= 1");
   for (const TflOperator& op : desc_.ops) {
-    if (op.builtin == kTflCustom) return absl::InternalError("job batching: CUSTOM op " + op.custom_code);
+    if (op.builtin == kTflCustom && !(gpu_detection && ex::DetectionSupported(desc_, op, nullptr)))
+      return absl::InternalError("job batching: CUSTOM op " + op.custom_code);
     if (op.builtin == kTflConcatenation && op.options.valid() && !op.outputs.empty()) {
       const int rank = static_cast<int>(desc_.tensors[op.outputs[0]].shape.size());
       int axis = op.options.Int(0, 0);

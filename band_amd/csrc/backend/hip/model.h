@@ -33,7 +33,10 @@ class HipModel : public interface::IModel {
   // non-constant tensor must have dim 0 == 1 and no op may mix the batch
   // axis (CONCATENATION on axis 0, CUSTOM ops); otherwise an error says why.
   // The copy keeps this model's serial, so device weights stay shared.
-  absl::Status CloneWithJobBatch(int batch, std::unique_ptr<HipModel>* out) const;
+  // gpu_detection: the caller runs TFLite_Detection_PostProcess on the device
+  // (a kGPU executor with BAND_HIP_GPU_DETECTION=1), whose kernels take a
+  // batch of images over one anchor table; CUSTOM ops of that form pass.
+  absl::Status CloneWithJobBatch(int batch, std::unique_ptr<HipModel>* out, bool gpu_detection = false) const;
 
  private:
   absl::Status Load(std::vector<uint8_t>&& bytes);

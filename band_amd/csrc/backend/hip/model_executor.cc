@@ -63,6 +63,7 @@ HipModelExecutor::HipModelExecutor(ModelId model_id, WorkerId worker_id, DeviceF
   if (const char* d = std::getenv("BAND_HIP_DIRECT_IO")) direct_io_ = d[0] != '0';
   if (const char* c = std::getenv("BAND_HIP_COALESCE")) coalesce_max_ = std::atoi(c);
   if (const char* c = std::getenv("BAND_HIP_COALESCE_LANES")) coalesce_lanes_ = std::max(1, std::atoi(c));
+  if (const char* dt = std::getenv("BAND_HIP_GPU_DETECTION")) gpu_detection_ = dt[0] == '1';
 }
 
 HipModelExecutor::~HipModelExecutor() {
@@ -96,6 +97,7 @@ std::unique_ptr<HipModelExecutor> HipModelExecutor::MakeLane() {
   // lane's stream (from the members' views, or from the variants' mirrors)
   lane->direct_io_ = true;
   lane->autotune_ = autotune_;
+  lane->gpu_detection_ = gpu_detection_;
   return lane;
 }
 
@@ -263,6 +265,12 @@ bool HipModelExecutor::CpuSupports(const TflModel& m, const TflOperator& op, std
   return GpuSupports(m, op, why);
 }
 
+bool HipModelExecutor::GpuSupportsHere(const TflModel& m, const TflOperator& op, std::string* why) const {
+  int batch = 1;
+  if (gpu_detection_ && DetectionSupported(m, op, nullptr, &batch)) return true;
+  return GpuSupports(m, op, why);
+}
+
 absl::Status HipModelExecutor::EnsureMeta(const HipModel& model) {
   if (!meta_.empty()) return absl::OkStatus();
   const TflModel& d = model.desc();
@@ -338,7 +346,7 @@ absl::StatusOr<ModelSpec> HipModelExecutor::InvestigateModelSpec(interface::IMod
       continue;
     }
     for (int i = 0; i < num_ops; ++i)
-      if (!GpuSupports(d, d.ops[i], nullptr)) unsupported[flag].insert(i);
+      if (!GpuSupportsHere(d, d.ops[i], nullptr)) unsupported[flag].insert(i);
     // Placement at a CPU-only boundary: a DEQUANTIZE whose every consumer
     // only the CPU runs (TFLite_Detection_PostProcess's inputs) is declared
     // unsupported here too, so the model analyzer puts it on the CPU side and
@@ -615,6 +623,7 @@ absl::Status HipModelExecutor::EnqueueLaunch(const Launch& l) {
                           stream_);
       break;
     case Launch::kDetectionPost: return absl::InternalError(std::string(l.kernel) + " is a CPU-worker op");
+    case Launch::kDetectionGpu: rc = bh_detection_postprocess(&l.detg, stream_); break;
     case Launch::kMean: {
       bh_mean_params q{};
       q.outer = l.mean.outer;

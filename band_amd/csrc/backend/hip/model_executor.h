@@ -45,7 +45,8 @@ struct Launch {
     kResizeBilinearU8,
     kDetectionPost,  // CPU-only TFLite_Detection_PostProcess
     kMean,           // CPU-only MEAN
-    kConvGroup       // independent small convs in one dispatch (GroupConvs)
+    kConvGroup,      // independent small convs in one dispatch (GroupConvs)
+    kDetectionGpu    // TFLite_Detection_PostProcess on the device (BAND_HIP_GPU_DETECTION=1)
   } kind;
   int op_index = -1;
   int out_tensor = -1;  // tensor this launch materialises (after epilogue fusions)
@@ -74,6 +75,7 @@ struct Launch {
   float lo = 0.f, hi = 0.f, beta = 1.f;
   int depth = 0;
   CpuDetectionParams det{};
+  bh_detection_params detg{};  // kDetectionGpu
   CpuMeanParams mean{};
   const void* table = nullptr;  // kLutU8 / kLutF32: 256-entry device table
   long count = 0;               // kLut* / kQuantF32: elements
@@ -187,6 +189,10 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   static bool GpuSupports(const TflModel& model, const TflOperator& op, std::string* why);
   // The kCPU worker's set: the GPU set plus host-only ops (float graphs).
   static bool CpuSupports(const TflModel& model, const TflOperator& op, std::string* why);
+  // This executor's kGPU set: GpuSupports, plus TFLite_Detection_PostProcess
+  // (DetectionSupported) when the executor was built with
+  // BAND_HIP_GPU_DETECTION=1.
+  bool GpuSupportsHere(const TflModel& model, const TflOperator& op, std::string* why) const;
 
  private:
   friend class JobCoalescer;
@@ -226,6 +232,12 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
                                   PreparedSubgraph* sg, Launch* l);
   absl::Status LowerGlue(const HipModel& model, int op_index, void* in_ptr, void* out_ptr, const std::string& ckey,
                          PreparedSubgraph* sg, Launch* l);
+  // TFLite_Detection_PostProcess on the device: one bh_detection_postprocess launch
+  absl::Status LowerDetectionGpu(const HipModel& model, int op_index, PreparedSubgraph* sg, Launch* l);
+  // op_index is an 8-bit DEQUANTIZE whose float output only the device
+  // detection op of this subgraph reads (as box encodings or class scores)
+  // and nobody else needs: the detection kernels read the bytes instead
+  bool DequantFoldsIntoDetection(const TflModel& d, const PreparedSubgraph& sg, int op_index) const;
   absl::Status Enqueue(PreparedSubgraph* sg);
   // Enqueue's three parts: host->device inputs, the launches, device->host
   // outputs (and intermediates a later subgraph reads)
@@ -277,6 +289,11 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   bool no_split_chain_ = false;    // BAND_HIP_FUSION=nosplit: the tuner skips the phase-C split forms
   bool no_stage_chain_ = false;    // BAND_HIP_FUSION=nostage: the tuner skips the stage forms
   bool autotune_ = true;  // BAND_HIP_AUTOTUNE=0: pick fused tiles by the static model
+  // BAND_HIP_GPU_DETECTION=1, latched at construction (lanes and job-batch
+  // variants take their parent's): TFLite_Detection_PostProcess is in this
+  // executor's kGPU set.  Off by default: the reference places the op on
+  // the CPU worker, and so does this backend unless asked.
+  bool gpu_detection_ = false;
   std::map<SubgraphKey, std::unique_ptr<PreparedSubgraph>> subgraphs_;
   int ordinal_ = -1;
   bh_stream_t stream_ = nullptr;

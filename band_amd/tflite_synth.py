@@ -820,13 +820,33 @@ def _mnv2_trunk(g, x, out_stride=32, tap_expansion_at=None):
     return x, taps
 
 
-def ssd_mobilenet_v2(dtype=np.int8, seed=1, size=224, batch=1, classes=91):
+def ssd_anchors(maps, min_scale=0.2, max_scale=0.95):
+    """normalised (ycenter, xcenter, h, w) for SSD feature maps [(h, w,
+    anchors per cell)], cell-major then anchor, as the predictors' RESHAPE
+    lays them out; scales spread linearly over the maps, aspect ratios cycled
+    (TF object-detection API's multiple-grid anchor generator, simplified)"""
+    ratios = (1.0, 2.0, 0.5, 3.0, 1.0 / 3.0, 1.0)
+    out = []
+    for i, (h, w, per_cell) in enumerate(maps):
+        scale = min_scale + (max_scale - min_scale) * i / max(1, len(maps) - 1)
+        for y in range(h):
+            for x in range(w):
+                for a in range(per_cell):
+                    r = ratios[a % len(ratios)]
+                    s = scale * (1.15 if a == len(ratios) - 1 else 1.0)
+                    out.append(((y + 0.5) / h, (x + 0.5) / w, s / np.sqrt(r), s * np.sqrt(r)))
+    return np.array(out, np.float32)
+
+
+def ssd_mobilenet_v2(dtype=np.int8, seed=1, size=224, batch=1, classes=91, postprocess=False):
     """SSD-MobileNetV2 (TF object-detection API layout): feature maps at
     layer_15/expansion_output (14x14x576) and the 1280-channel head (7x7),
     four extra 1x1 -> 3x3 s2 feature layers, 1x1 box / class predictors,
-    RESHAPE + CONCATENATION of all anchors, LOGISTIC class scores.  The
-    TFLite_Detection_PostProcess custom op (CPU NMS) is left out: outputs are
-    box encodings [1,N,4] and class scores [1,N,classes]."""
+    RESHAPE + CONCATENATION of all anchors, LOGISTIC class scores.  By
+    default the TFLite_Detection_PostProcess custom op is left out: outputs
+    are box encodings [1,N,4] and class scores [1,N,classes].  postprocess:
+    the real model's tail - DEQUANTIZE of both, then the custom op over
+    ssd_anchors (class 0 is the background; 10 detections)."""
     g = _graph(dtype, seed, "ssd_mobilenet_v2_%s" % np.dtype(dtype).name)
     x = g.input([batch, size, size, 3])
     feat, taps = _mnv2_trunk(g, x, tap_expansion_at=13)
@@ -835,7 +855,7 @@ def ssd_mobilenet_v2(dtype=np.int8, seed=1, size=224, batch=1, classes=91):
     for c1, c3 in ((256, 512), (128, 256), (128, 256), (64, 128)):
         y = g.conv(g.conv(y, c1, k=1), c3, k=3, stride=2)
         maps.append(y)
-    boxes, scores = [], []
+    boxes, scores, grid = [], [], []
     for i, m in enumerate(maps):
         b, h, w, _ = g.meta[m][0]
         anchors = 3 if i == 0 else 6
@@ -843,8 +863,16 @@ def ssd_mobilenet_v2(dtype=np.int8, seed=1, size=224, batch=1, classes=91):
         cl = g.conv(m, anchors * classes, k=1, act="NONE")
         boxes.append(g.reshape(bx, [batch, h * w * anchors, 4]))
         scores.append(g.reshape(cl, [batch, h * w * anchors, classes]))
-    g.output(g.concat(boxes, axis=1))
-    g.output(g.logistic(g.concat(scores, axis=1)))
+        grid.append((h, w, anchors))
+    box_enc = g.concat(boxes, axis=1)
+    cls = g.logistic(g.concat(scores, axis=1))
+    if not postprocess:
+        g.output(box_enc)
+        g.output(cls)
+        return g.build()
+    for o in g.detection_postprocess(g.dequantize(box_enc), g.dequantize(cls), ssd_anchors(grid), classes - 1,
+                                     max_detections=10):
+        g.output(o)
     return g.build()
 
 

@@ -30,6 +30,8 @@
  *   bh_resize_bilinear_u8 <- RESIZE_BILINEAR uint8 (optimized_ops::ResizeBilinear, float path)
  *   bh_softmax_i8     <- SOFTMAX 8-bit      (optimized_ops::Softmax, lookup-table path)
  *   bh_mean           <- MEAN               (optimized_integer_ops::Mean / optimized_ops::Mean)
+ *   bh_detection_postprocess <- TFLite_Detection_PostProcess (custom; detection_postprocess.cc,
+ *                        fast NMS, one class per detection)
  *   (HARD_SWISH 8-bit runs as a bh_lut_u8 table of reference_ops::HardSwish)
  *   bh_zero_insert + bh_conv2d_i8 <- TRANSPOSE_CONV int8 (reference_integer_ops::TransposeConv)
  *   bh_conv2d_f32 / bh_fc_f32 / bh_eltwise_f32 / bh_pool_f32 / bh_unary_f32 / bh_softmax_f32
@@ -646,6 +648,41 @@ typedef struct {
   void* output;
 } bh_zero_insert_params;
 int bh_zero_insert(const bh_zero_insert_params* p, bh_stream_t s);
+
+/* TFLite_Detection_PostProcess, fast (class-agnostic) NMS with one class per
+ * detection (detection_postprocess.cc DecodeCenterSizeBoxes +
+ * MultiClassFastNMS), for `batch` images that share one anchor table.
+ * Two kernels: detection_score_kernel (per anchor the first maximum over the
+ * non-background classes, keyed as score descending / anchor ascending) and
+ * detection_nms_kernel (one workgroup per image: candidates compacted in
+ * anchor order, their boxes decoded in double, then at most max_detections
+ * rounds of "take the largest active key, suppress every active candidate
+ * whose IoU with it is > iou_threshold").  Outputs per image: boxes
+ * [max_detections][4] (ymin xmin ymax xmax), classes, scores, num (float);
+ * rows past num are zero.
+ * box_type / score_type: 0 float32, 1 int8, 2 uint8; an 8-bit input is
+ * dequantised as scale * (q - zero_point) (a DEQUANTIZE folded into the op:
+ * the maximum is taken over the bytes, scale > 0 required).
+ * scratch: bh_detection_scratch_bytes(batch, num_boxes) device bytes, fully
+ * rewritten by every call (no state survives a call). */
+typedef struct bh_detection_params {
+  int batch, num_boxes, num_classes, num_classes_with_background, max_detections;
+  float score_threshold, iou_threshold;
+  float scale_y, scale_x, scale_h, scale_w;
+  int box_type, score_type;
+  float box_scale, score_scale;
+  int32_t box_zp, score_zp;
+  const void* box_encodings;      /* [batch][num_boxes][4] */
+  const void* class_scores;       /* [batch][num_boxes][num_classes_with_background] */
+  const float* anchors;           /* [num_boxes][4] ycenter xcenter h w */
+  float* out_boxes;
+  float* out_classes;
+  float* out_scores;
+  float* out_num;                 /* [batch] */
+  void* scratch;
+} bh_detection_params;
+size_t bh_detection_scratch_bytes(int batch, int num_boxes);
+int bh_detection_postprocess(const bh_detection_params* p, bh_stream_t s);
 
 /* human-readable name of the last error set on this thread */
 const char* bh_last_error(void);
