@@ -237,6 +237,7 @@ KERNEL_SYMBOLS = {
     "bh_softmax_i8": (c_int, [ctypes.POINTER(SoftmaxParams), c_void_p]),
     "bh_zero_insert": (c_int, [ctypes.POINTER(ZeroInsertParams), c_void_p]),
     "bh_conv2d_f32": (c_int, [ctypes.POINTER(ConvF32Params), c_void_p]),
+    "bh_conv2d_f32_split": (c_int, [ctypes.POINTER(ConvF32Params)]),
     "bh_fc_f32": (c_int, [ctypes.POINTER(FcF32Params), c_void_p]),
     "bh_eltwise_f32": (c_int, [ctypes.POINTER(EltwiseF32Params), c_void_p]),
     "bh_pool_f32": (c_int, [ctypes.POINTER(PoolF32Params), c_void_p]),

@@ -468,7 +468,8 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
         all_fold = all_fold && folds;
       }
       std::set<int> subgraph_outputs(sg->outputs.begin(), sg->outputs.end());
-      if (all_fold && !subgraph_outputs.count(t) && !sg->no_fuse.count(t)) {
+      if (all_fold && !subgraph_outputs.count(t) && !sg->no_fuse.count(t) && !sg->extra_d2h.count(t)) {
+        sg->fused_tensors.insert(t);  // never materialised: a view of it re-lowers with the copy
         *emit = false;
         return absl::OkStatus();
       }

@@ -557,7 +557,9 @@ std::shared_ptr<interface::ITensorView> HipModelExecutor::GetTensorView(const Su
     return std::make_shared<HipTensorView>(m, const_cast<char*>(reinterpret_cast<const char*>(t.data)));
   if ((device_flag_ == DeviceFlag::kGPU || device_flag_ == DeviceFlag::kCPU) && sg->offset.count(index)) {
     // an intermediate of this subgraph: mirror it and copy it back on every run
-    auto buf = std::make_unique<PinnedBuffer>(m->bytes);
+    // (pinned for the GPU worker only, as the boundary mirrors are: a host
+    // executor must not need a device to show an intermediate)
+    auto buf = std::make_unique<PinnedBuffer>(m->bytes, device_flag_ == DeviceFlag::kGPU);
     if (!buf->ok()) return nullptr;
     char* data = buf->data();
     sg->host[index] = std::move(buf);

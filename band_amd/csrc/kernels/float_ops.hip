@@ -11,7 +11,13 @@
 
 namespace bh {
 
-__device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
+// TFLite's ActivationFunctionWithMinMax, std::min(std::max(v, lo), hi), in its
+// comparison order: a NaN v fails both comparisons and stays NaN (fminf /
+// fmaxf would return the bound), as the kCPU worker's ClampF does
+__device__ __forceinline__ float clampf(float v, float lo, float hi) {
+  const float t = v < lo ? lo : v;
+  return hi < t ? hi : t;
+}
 
 // CONV_2D as an implicit GEMM on VALU: an item = one output pixel x 4
 // output channels (items of one pixel are consecutive, so their float4
@@ -218,6 +224,16 @@ __global__ __launch_bounds__(256) void softmax_f32_kernel(const float* in, float
 
 inline unsigned blocks(long n, int per = 256) { return (unsigned)((n + per - 1) / per); }
 
+// split-K factor of conv_f32_kernel: split the reduction until ~1024
+// workgroups or 16 taps-channels per slice
+inline int conv_f32_split(const bh_conv_f32_params& p) {
+  const long total = (long)p.batch * p.out_h * p.out_w * ((p.out_c + 3) / 4);
+  const int K = p.k_h * p.k_w * p.in_c;
+  int ks = 1;
+  while (ks < 16 && (total * ks) / 256 < 1024 && K / (2 * ks) >= 16) ks *= 2;
+  return ks;
+}
+
 }  // namespace bh
 
 extern "C" int bh_conv2d_f32(const bh_conv_f32_params* pp, bh_stream_t s) {
@@ -239,15 +255,17 @@ extern "C" int bh_conv2d_f32(const bh_conv_f32_params* pp, bh_stream_t s) {
     BH_LAUNCH(bh::dwconv_f32_kernel, dim3(bh::blocks(total)), dim3(256), 0, (hipStream_t)s, p, dg, dw, dh,
                        total);
   } else {
-    // split the reduction until ~1024 workgroups or 16 taps-channels per slice
-    const int K = p.k_h * p.k_w * p.in_c;
-    int ks = 1;
-    while (ks < 16 && (total * ks) / 256 < 1024 && K / (2 * ks) >= 16) ks *= 2;
+    const int ks = bh::conv_f32_split(p);
     const long items_per_wg = 256 / ks;
     BH_LAUNCH(bh::conv_f32_kernel, dim3((unsigned)((total + items_per_wg - 1) / items_per_wg)), dim3(256),
                        0, (hipStream_t)s, p, dg, dw, dh, total, ks);
   }
   return bh_check_launch(p.depthwise ? "dwconv_f32_kernel" : "conv_f32_kernel");
+}
+
+extern "C" int bh_conv2d_f32_split(const bh_conv_f32_params* pp) {
+  if (!pp || pp->depthwise || pp->out_c <= 0 || pp->in_c <= 0) return 0;
+  return bh::conv_f32_split(*pp);
 }
 
 extern "C" int bh_fc_f32(const bh_fc_f32_params* pp, bh_stream_t s) {

@@ -521,6 +521,10 @@ typedef struct {
   const float* bias;    /* [out_c] or NULL */
 } bh_conv_f32_params;
 int bh_conv2d_f32(const bh_conv_f32_params* p, bh_stream_t s);
+/* Split-K factor (1, 2, 4, 8 or 16 slices of the filter taps per workgroup)
+ * bh_conv2d_f32 runs conv_f32_kernel with for these parameters; 0 for a
+ * depthwise or invalid block.  Pure host, no device call. */
+int bh_conv2d_f32_split(const bh_conv_f32_params* p);
 
 typedef struct {
   int rows, depth, units;

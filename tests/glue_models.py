@@ -103,6 +103,49 @@ def float_zoo(seed=13):
     return g.build()
 
 
+def float_edge_zoo(seed=29):
+    """float32 edges float_zoo leaves out: batch 2, float16 and float32
+    constants, a conv (two inputs) and an FC (bias -1) without bias, a 1x1
+    conv over 129 input channels (split-K with K % ks != 0), depth multiplier
+    3, stride 2 on an even size (asymmetric SAME padding), a SAME average
+    pool with clipped windows, MUL with a broadcast first operand, SUB of a
+    float16 constant, SQUARED_DIFFERENCE with a rank-1 float32 constant,
+    RSQRT, FC feeding a SOFTMAX with beta 3"""
+    from band_amd.tflite_synth import FGraph, act_options, conv_options
+    g = FGraph(seed=seed, name="float_edge_zoo")
+    mb, f32 = g.mb, np.float32
+    x = g.input([2, 8, 6, 5])
+    a = g.conv(x, 6, k=3, stride=2, act="RELU")                 # [2,4,3,6], pad 0 before / 1 after
+    b = g.dwconv(a, k=3, dm=3, act="RELU6")                     # 18 channels
+    c = g.conv(b, 129, k=1, act="NONE")
+    w32 = mb.tensor("w_f32", [7, 1, 1, 129], f32, data=g.rng.normal(0, np.sqrt(2.0 / 129), (7, 1, 1, 129)))
+    d = g._act([2, 4, 3, 7])
+    mb.op("CONV_2D", [c, w32], [d], OPT["Conv2DOptions"], conv_options("SAME", 1, "RELU_N1_TO_1"))
+    p = g.avgpool(d, (3, 3), stride=2, padding="SAME")          # [2,2,2,7], every window clipped
+    gate = g.logistic(g.avgpool(d, (4, 3)))                      # [2,1,1,7]
+    e = g._act([2, 4, 3, 7])
+    mb.op("MUL", [gate, d], [e], OPT["MulOptions"], act_options("NONE"))   # first operand broadcasts
+    shift = g._const(np.linspace(-0.2, 0.3, 7).reshape(1, 1, 1, 7), "shift")
+    s = g._act([2, 4, 3, 7])
+    mb.op("SUB", [e, shift], [s], OPT["SubOptions"], act_options("RELU_N1_TO_1"))
+    centre = mb.tensor("centre", [7], f32, data=np.linspace(-0.3, 0.4, 7))
+    q = g._act([2, 4, 3, 7])
+    mb.op(99, [s, centre], [q], OPT_SQDIFF, Table())
+    eps = mb.tensor("eps", [1], f32, data=[1e-3])
+    v = g._act([2, 4, 3, 7])
+    mb.op("ADD", [q, eps], [v], OPT["AddOptions"], act_options("NONE"))
+    r = g._act([2, 4, 3, 7])
+    mb.op(76, [v], [r])                                          # RSQRT
+    flat = g.reshape(g.maxpool(r, (2, 2), 2), [4, 14])           # [2,2,2,7] as 4 rows of 14
+    wfc = g._const(g.rng.normal(0, np.sqrt(1.0 / 14), (9, 14)), "fc_weights")
+    fc = g._act([4, 9])
+    mb.op("FULLY_CONNECTED", [flat, wfc, -1], [fc], OPT["FullyConnectedOptions"], act_options("NONE"))
+    g.output(g.softmax(fc, beta=3.0))
+    g.output(p)
+    g.output(r)
+    return g.build()
+
+
 def norm_zoo(with_mean=True):
     """The instance-norm / padding ops of the reference's magenta
     style-transfer model (band/test/data/magenta_...tflite): MIRROR_PAD
