@@ -56,15 +56,29 @@ class ChainCase:
             self.f_s, self.f_zp = RELU6_SCALE, -128
             self.wf, self.wf_s, self.bf = conv_w(ce2, cout, 1, y_s, self.f_s, cout)
 
+        # explicit per-channel (mult, shift) and (act_min, act_max) per stage
+        # ("dw" / "pw1" / "pw2") in place of the ones derived from the scales
+        # (directed cases); tensors and zero points are plain attributes
+        self.q, self.win = {}, {}
+
+    def _mults(self, stage, s_in, ws, n, s_out):
+        if stage in self.q:
+            m, s = self.q[stage]
+            return np.ascontiguousarray(m, np.int32), np.ascontiguousarray(s, np.int32)
+        return orc.conv_multipliers(s_in, ws, n, s_out, False)
+
+    def _window(self, stage, act, scale, zp):
+        return self.win[stage] if stage in self.win else orc.act_range(act, scale, zp, True)
+
     # --- oracle: ops one by one ------------------------------------------
     def oracle(self):
-        m, s = orc.conv_multipliers(self.e_s, self.wd_s, self.ce, self.d_s, False)
-        lo, hi = orc.act_range(3, self.d_s, self.d_zp, True)
+        m, s = self._mults("dw", self.e_s, self.wd_s, self.ce, self.d_s)
+        lo, hi = self._window("dw", 3, self.d_s, self.d_zp)
         d = orc.dwconv2d(self.e, self.wd, self.bd, dm=1, in_zp=self.e_zp, w_zp=0, out_zp=self.d_zp, mult=m, shift=s,
                          amin=lo, amax=hi, stride=(self.stride, self.stride), dilation=(self.dil, self.dil),
                          pad=self.pad, out_hw=(self.oh, self.ow))
-        m, s = orc.conv_multipliers(self.d_s, self.wp_s, self.cout, self.p_s, False)
-        lo, hi = orc.act_range(0, self.p_s, self.p_zp, True)
+        m, s = self._mults("pw1", self.d_s, self.wp_s, self.cout, self.p_s)
+        lo, hi = self._window("pw1", 0, self.p_s, self.p_zp)
         y = orc.conv2d(d, self.wp, self.bp, in_zp=self.d_zp, w_zp=0, out_zp=self.p_zp, mult=m, shift=s,
                        amin=lo, amax=hi, out_hw=(self.oh, self.ow))
         y_zp = self.p_zp
@@ -75,8 +89,8 @@ class ChainCase:
             y_zp = self.o_zp
         if not self.ce2:
             return y, None
-        m, s = orc.conv_multipliers(self.y_s, self.wf_s, self.ce2, self.f_s, False)
-        lo, hi = orc.act_range(3, self.f_s, self.f_zp, True)
+        m, s = self._mults("pw2", self.y_s, self.wf_s, self.ce2, self.f_s)
+        lo, hi = self._window("pw2", 3, self.f_s, self.f_zp)
         f = orc.conv2d(y, self.wf, self.bf, in_zp=y_zp, w_zp=0, out_zp=self.f_zp, mult=m, shift=s,
                        amin=lo, amax=hi, out_hw=(self.oh, self.ow))
         return y, f
@@ -99,7 +113,7 @@ class ChainCase:
             return int(lib.bh_conv_requant_fast_ok(m.ctypes.data_as(ctypes.c_void_p), sh.ctypes.data_as(ctypes.c_void_p),
                                                    n, k, int(np.abs(np.asarray(bias, np.int64)).max())))
 
-        def conv(w, oc, k, in_zp, ws, s_in, s_out, bias, out_zp, act):
+        def conv(stage, w, oc, k, in_zp, ws, s_in, s_out, bias, out_zp, act):
             q = _abi.ConvParams()
             kp, npd = ctypes.c_int(), ctypes.c_int()
             lib.bh_conv_packed_geometry(oc, k, ctypes.byref(kp), ctypes.byref(npd))
@@ -110,13 +124,13 @@ class ChainCase:
                                                 bias.ctypes.data_as(ctypes.c_void_p), in_zp, 0,
                                                 packed.ctypes.data_as(ctypes.c_void_p),
                                                 beff.ctypes.data_as(ctypes.c_void_p)), "pack")
-            m, s = orc.conv_multipliers(s_in, ws, oc, s_out, False)
+            m, s = self._mults(stage, s_in, ws, oc, s_out)
             q.batch, q.in_h, q.in_w, q.in_c = self.b, self.oh, self.ow, k
             q.out_h, q.out_w, q.out_c = self.oh, self.ow, oc
             q.k_h = q.k_w = q.stride_h = q.stride_w = q.dil_h = q.dil_w = 1
             q.k_pad, q.n_pad = kp.value, npd.value
             q.in_zp, q.w_zp, q.out_zp = in_zp, 0, out_zp
-            q.act_min, q.act_max = orc.act_range(act, s_out, out_zp, True)
+            q.act_min, q.act_max = self._window(stage, act, s_out, out_zp)
             q.weights, q.bias_eff = dev(packed), dev(beff)
             q.mult, q.shift = dev(m.astype(np.int32)), dev(s.astype(np.int32))
             q.requant_fast = fast_ok(m, s, oc, k, bias)
@@ -131,9 +145,9 @@ class ChainCase:
         d.dil_h = d.dil_w = self.dil
         d.pad_h, d.pad_w = self.pad
         d.in_zp, d.w_zp, d.out_zp = self.e_zp, 0, self.d_zp
-        d.act_min, d.act_max = orc.act_range(3, self.d_s, self.d_zp, True)
+        d.act_min, d.act_max = self._window("dw", 3, self.d_s, self.d_zp)
         wdr = np.ascontiguousarray(self.wd.reshape(-1))
-        m, s = orc.conv_multipliers(self.e_s, self.wd_s, self.ce, self.d_s, False)
+        m, s = self._mults("dw", self.e_s, self.wd_s, self.ce, self.d_s)
         taps = np.zeros((self.ce, 4), np.int32)
         _abi.check(lib.bh_pack_dw_taps(wdr.ctypes.data_as(ctypes.c_void_p), self.ce,
                                        self.bd.ctypes.data_as(ctypes.c_void_p), self.e_zp, 0,
@@ -141,7 +155,7 @@ class ChainCase:
         d.input, d.weights, d.bias = dev(self.e), dev(wdr), dev(self.bd)
         d.mult, d.shift, d.taps = dev(m.astype(np.int32)), dev(s.astype(np.int32)), dev(taps)
         d.requant_fast = fast_ok(m, s, self.ce, 9, self.bd)
-        c.pw1 = conv(self.wp, self.cout, self.ce, self.d_zp, self.wp_s, self.d_s, self.p_s, self.bp, self.p_zp, 0)
+        c.pw1 = conv("pw1", self.wp, self.cout, self.ce, self.d_zp, self.wp_s, self.d_s, self.p_s, self.bp, self.p_zp, 0)
         y_zp = self.p_zp
         if self.residual:
             a = c.pw1
@@ -161,7 +175,7 @@ class ChainCase:
             c.pw1.output = self._y.value
         if self.ce2:
             c.has_pw2 = 1
-            c.pw2 = conv(self.wf, self.ce2, self.cout, y_zp, self.wf_s, self.y_s, self.f_s, self.bf, self.f_zp, 3)
+            c.pw2 = conv("pw2", self.wf, self.ce2, self.cout, y_zp, self.wf_s, self.y_s, self.f_s, self.bf, self.f_zp, 3)
             self._f = DB(px * self.ce2)
             keep.append(self._f)
             c.pw2.output = self._f.value

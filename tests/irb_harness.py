@@ -51,13 +51,27 @@ class IrbCase:
         self.wp, self.wp_s, self.bp = conv_w(cout, ce, 1, self.d_s, self.p_s, ce)
         self.o_s, self.o_zp = float(max(self.p_s, self.x_s) * 1.3), int(rng.integers(-10, 11))
 
+        # explicit per-channel (mult, shift) and (act_min, act_max) per stage
+        # ("exp" / "dw" / "proj") in place of the ones derived from the scales;
+        # tensors, biases and zero points are plain attributes
+        self.q, self.win = {}, {}
+
+    def _mults(self, stage, s_in, ws, n, s_out):
+        if stage in self.q:
+            m, s = self.q[stage]
+            return np.ascontiguousarray(m, np.int32), np.ascontiguousarray(s, np.int32)
+        return orc.conv_multipliers(s_in, ws, n, s_out, False)
+
+    def _window(self, stage, act, scale, zp):
+        return self.win[stage] if stage in self.win else orc.act_range(act, scale, zp, True)
+
     # --- oracle: ops one by one ------------------------------------------
     def oracle(self):
         x = self.x
         h, w = self.h, self.w
         if self.has_expand:
-            m, s = orc.conv_multipliers(self.x_s, self.we_s, self.ce, self.e_s, False)
-            lo, hi = orc.act_range(3, self.e_s, self.e_zp, True)
+            m, s = self._mults("exp", self.x_s, self.we_s, self.ce, self.e_s)
+            lo, hi = self._window("exp", 3, self.e_s, self.e_zp)
             e = orc.conv2d(x, self.we, self.be, in_zp=self.x_zp, w_zp=0, out_zp=self.e_zp, mult=m, shift=s,
                            amin=lo, amax=hi, out_hw=(h, w))
         else:
@@ -65,12 +79,12 @@ class IrbCase:
         oh = orc.out_size(True, h, 3, self.stride, 1)
         ow = orc.out_size(True, w, 3, self.stride, 1)
         ph, pw = orc.padding(self.stride, 1, h, 3, oh), orc.padding(self.stride, 1, w, 3, ow)
-        m, s = orc.conv_multipliers(self.e_s, self.wd_s, self.ce, self.d_s, False)
-        lo, hi = orc.act_range(3, self.d_s, self.d_zp, True)
+        m, s = self._mults("dw", self.e_s, self.wd_s, self.ce, self.d_s)
+        lo, hi = self._window("dw", 3, self.d_s, self.d_zp)
         d = orc.dwconv2d(e, self.wd, self.bd, dm=1, in_zp=self.e_zp, w_zp=0, out_zp=self.d_zp, mult=m, shift=s,
                          amin=lo, amax=hi, stride=(self.stride, self.stride), pad=(ph, pw), out_hw=(oh, ow))
-        m, s = orc.conv_multipliers(self.d_s, self.wp_s, self.cout, self.p_s, False)
-        lo, hi = orc.act_range(0, self.p_s, self.p_zp, True)
+        m, s = self._mults("proj", self.d_s, self.wp_s, self.cout, self.p_s)
+        lo, hi = self._window("proj", 0, self.p_s, self.p_zp)
         p = orc.conv2d(d, self.wp, self.bp, in_zp=self.d_zp, w_zp=0, out_zp=self.p_zp, mult=m, shift=s,
                        amin=lo, amax=hi, out_hw=(oh, ow))
         if not self.residual:
@@ -89,7 +103,7 @@ class IrbCase:
             keep.append(d)
             return d.value
 
-        def pack(w, oc, k, in_zp, ws, s_in, s_out, bias):
+        def pack(stage, w, oc, k, in_zp, ws, s_in, s_out, bias):
             kp, npd = ctypes.c_int(), ctypes.c_int()
             lib.bh_conv_packed_geometry(oc, k, ctypes.byref(kp), ctypes.byref(npd))
             packed = np.zeros((npd.value, kp.value), np.int8)
@@ -99,7 +113,7 @@ class IrbCase:
                                                 bias.ctypes.data_as(ctypes.c_void_p), in_zp, 0,
                                                 packed.ctypes.data_as(ctypes.c_void_p),
                                                 beff.ctypes.data_as(ctypes.c_void_p)), "pack")
-            m, s = orc.conv_multipliers(s_in, ws, oc, s_out, False)
+            m, s = self._mults(stage, s_in, ws, oc, s_out)
             return dev(packed), kp.value, dev(beff), dev(m.astype(np.int32)), dev(s.astype(np.int32))
 
         oh = orc.out_size(True, self.h, 3, self.stride, 1)
@@ -112,19 +126,19 @@ class IrbCase:
         q.tile_h = q.tile_w = tile
         if self.has_expand:
             q.exp_w, q.exp_k_pad, q.exp_bias_eff, q.exp_mult, q.exp_shift = pack(
-                self.we, self.ce, self.cin, self.x_zp, self.we_s, self.x_s, self.e_s, self.be)
+                "exp", self.we, self.ce, self.cin, self.x_zp, self.we_s, self.x_s, self.e_s, self.be)
             q.x_zp = self.x_zp
-            q.e_act_min, q.e_act_max = orc.act_range(3, self.e_s, self.e_zp, True)
+            q.e_act_min, q.e_act_max = self._window("exp", 3, self.e_s, self.e_zp)
         q.e_zp = self.e_zp
         q.dw_w = dev(self.wd.reshape(-1))
-        m, s = orc.conv_multipliers(self.e_s, self.wd_s, self.ce, self.d_s, False)
+        m, s = self._mults("dw", self.e_s, self.wd_s, self.ce, self.d_s)
         q.dw_bias, q.dw_mult, q.dw_shift = dev(self.bd), dev(m.astype(np.int32)), dev(s.astype(np.int32))
         q.d_zp = self.d_zp
-        q.d_act_min, q.d_act_max = orc.act_range(3, self.d_s, self.d_zp, True)
+        q.d_act_min, q.d_act_max = self._window("dw", 3, self.d_s, self.d_zp)
         q.proj_w, q.proj_k_pad, q.proj_bias_eff, q.proj_mult, q.proj_shift = pack(
-            self.wp, self.cout, self.ce, self.d_zp, self.wp_s, self.d_s, self.p_s, self.bp)
+            "proj", self.wp, self.cout, self.ce, self.d_zp, self.wp_s, self.d_s, self.p_s, self.bp)
         q.p_zp = self.p_zp
-        q.p_act_min, q.p_act_max = orc.act_range(0, self.p_s, self.p_zp, True)
+        q.p_act_min, q.p_act_max = self._window("proj", 0, self.p_s, self.p_zp)
         if self.residual:
             prm = [int(v) for v in orc.add_params(self.p_s, self.x_s, self.o_s)]
             q.has_residual = 1
@@ -134,16 +148,19 @@ class IrbCase:
             q.add_act_min, q.add_act_max = orc.act_range(0, self.o_s, self.o_zp, True)
         # single-step requant per stage, as the executor decides it
         # (fast=False forces the two-step form everywhere)
-        def fast_ok(s_in, ws, n, k, s_out, bias):
-            m, sh = orc.conv_multipliers(s_in, ws, n, s_out, False)
+        def fast_ok(stage, s_in, ws, n, k, s_out, bias):
+            m, sh = self._mults(stage, s_in, ws, n, s_out)
             m = np.ascontiguousarray(m, np.int32)
             sh = np.ascontiguousarray(sh, np.int32)
             return int(lib.bh_conv_requant_fast_ok(m.ctypes.data_as(ctypes.c_void_p), sh.ctypes.data_as(ctypes.c_void_p),
                                                    n, k, int(np.abs(np.asarray(bias, np.int64)).max())))
         if self.fast:
-            q.requant_fast = ((fast_ok(self.x_s, self.we_s, self.ce, self.cin, self.e_s, self.be) if self.has_expand
-                               else 0) | (fast_ok(self.e_s, self.wd_s, self.ce, 9, self.d_s, self.bd) << 1) |
-                              (fast_ok(self.d_s, self.wp_s, self.cout, self.ce, self.p_s, self.bp) << 2))
+            q.requant_fast = ((fast_ok("exp", self.x_s, self.we_s, self.ce, self.cin, self.e_s, self.be) if self.has_expand
+                               else 0) | (fast_ok("dw", self.e_s, self.wd_s, self.ce, 9, self.d_s, self.bd) << 1) |
+                              (fast_ok("proj", self.d_s, self.wp_s, self.cout, self.ce, self.p_s, self.bp) << 2))
+            self.eligible = q.requant_fast
+            if self.fast is not True:  # a 3-bit mask: expand / depthwise / project stages
+                q.requant_fast &= int(self.fast)
         q.input = dev(self.x)
         self.out_shape = (self.b, oh, ow, self.cout)
         from band_amd.device import DeviceBuffer as DB

@@ -27,7 +27,7 @@ def xor_of(dtype):
 class ConvCase:
     def __init__(self, rng, b, ih, iw, ic, oc, kh, kw, stride=(1, 1), dil=(1, 1), same=True,
                  dtype=np.int8, per_channel=True, act=3, depthwise=False, dm=1, requant_fast=None,
-                 taps=True, kernel_hint=0):
+                 taps=True, kernel_hint=0, **explicit):
         self.dtype = dtype
         self.taps = taps
         self.kernel_hint = kernel_hint  # BH_DW_* / BH_CONV_* (0 = the shape's own route)
@@ -62,6 +62,14 @@ class ConvCase:
         self.mult, self.shift = orc.conv_multipliers(self.in_scale, self.w_scales, oc, self.out_scale, legacy)
         self.amin, self.amax = orc.act_range(act, self.out_scale, self.out_zp, dtype == np.int8)
         self.b, self.ih, self.iw, self.ic, self.oc, self.kh, self.kw = b, ih, iw, ic, oc, kh, kw
+        # explicit tensors / quantisation parameters in place of the drawn
+        # ones (directed cases); oracle() and params() read the attributes
+        for name, value in explicit.items():
+            if name not in ("x", "w", "w_zp", "bias", "in_zp", "out_zp", "mult", "shift", "amin", "amax"):
+                raise TypeError("ConvCase: unknown argument %r" % name)
+            setattr(self, name, value)
+        assert self.x.shape == (b, ih, iw, ic) and self.w.shape == wshape and len(self.bias) == oc
+        assert len(self.mult) == oc and len(self.shift) == oc
 
     def oracle(self):
         kw = dict(in_zp=self.in_zp, w_zp=self.w_zp, out_zp=self.out_zp, mult=self.mult,

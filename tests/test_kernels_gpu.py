@@ -15,6 +15,16 @@ from tests.kernel_harness import (MNV2_DEPTHWISE, MNV2_POINTWISE, ConvCase, dom,
 pytestmark = pytest.mark.gpu
 
 
+def kernel_name(lib, c):
+    """the kernel the launcher would run for a ConvCase as it stands"""
+    keep = []
+    p = c.params(lib, keep)
+    fn = lib.bh_dwconv2d_i8_kernel if c.depthwise else lib.bh_conv2d_i8_kernel
+    name = fn(ctypes.byref(p)).decode()
+    del keep
+    return name
+
+
 @pytest.mark.parametrize("spatial,ic,oc", MNV2_POINTWISE)
 def test_conv1x1_mnv2_shapes_int8(gpu_lib, spatial, ic, oc):
     rng = np.random.default_rng(1000 + spatial * 7 + ic + oc)
@@ -22,9 +32,11 @@ def test_conv1x1_mnv2_shapes_int8(gpu_lib, spatial, ic, oc):
     np.testing.assert_array_equal(c.gpu(gpu_lib), c.oracle())
 
 
-# batched 1x1 layers (job batching): M = b*h*w >= 32768 output pixels take
-# conv_rows_kernel (channel-major tiles, packed stores); N / K tails, uint8
-# per-tensor filters (row-sum correction), whole-N and chunked-N grids
+# batched 1x1 layers (job batching): K <= 320 and M = b*h*w >= 2048 output
+# pixels take conv_xs_kernel (x-stationary); N / K tails, uint8 per-tensor
+# filters (row-sum correction), whole-N and chunked-N grids.  (conv_rows_kernel
+# is opt-in by BH_CONV_ROWS_MIN_M, read once per process: it runs in
+# test_kernels_directed_gpu.py's child process.)
 @pytest.mark.parametrize("b,spatial,ic,oc,dtype", [
     (4, 112, 16, 96, np.int8), (4, 112, 32, 16, np.uint8), (12, 56, 24, 144, np.int8),
     (12, 56, 144, 24, np.uint8), (44, 28, 32, 192, np.int8), (44, 28, 192, 32, np.int8),
@@ -34,6 +46,7 @@ def test_conv1x1_rows_batched(gpu_lib, b, spatial, ic, oc, dtype):
     rng = np.random.default_rng(4000 + b + spatial + ic + oc)
     c = ConvCase(rng, b, spatial, spatial, ic, oc, 1, 1, dtype=dtype, act=3)
     ref = c.oracle()
+    assert kernel_name(gpu_lib, c) == "conv_xs_kernel"
     np.testing.assert_array_equal(c.gpu(gpu_lib), ref)
     c.requant_fast = False  # the two-step requantisation path
     np.testing.assert_array_equal(c.gpu(gpu_lib), ref)
@@ -51,8 +64,11 @@ def test_conv1x1_gemm_vs_mfma(gpu_lib, b, spatial, ic, oc):
     rng = np.random.default_rng(6000 + b + spatial + ic + oc)
     c = ConvCase(rng, b, spatial, spatial, ic, oc, 1, 1, act=3)
     ref = c.oracle()
+    # every case is int8 with K % 16 == 0, so both GEMM forms can be forced
+    names = {3: "conv_gemm_big_kernel", 2: "conv_gemm_kernel", 1: "conv_mfma_kernel"}
     for hint in (3, 2, 1):  # BH_CONV_GEMM_BIG, BH_CONV_GEMM, BH_CONV_MFMA
         c.kernel_hint = hint
+        assert kernel_name(gpu_lib, c) == names[hint], "hint %d" % hint
         for fast in (None, False):
             c.requant_fast = fast
             np.testing.assert_array_equal(c.gpu(gpu_lib), ref, err_msg="hint %d fast %s" % (hint, fast))
@@ -140,9 +156,22 @@ def test_conv_stem(gpu_lib, b, h, w, oc, stride, same, dtype):
     # 6) forced; both requantisation paths
     for hint in (0, 4, 5, 6):
         c.kernel_hint = hint
+        assert kernel_name(gpu_lib, c) == stem_form(hint, oc, b * c.oh * c.ow), "hint %d" % hint
         for fast in (None, False):
             c.requant_fast = fast
             np.testing.assert_array_equal(c.gpu(gpu_lib), ref, err_msg="hint %d fast %s" % (hint, fast))
+
+
+def stem_form(hint, oc, m):
+    """the stem kernel a hint must land on.  The MFMA form takes out_c in {16,
+    32, 48, 64} when routed or forced; out_c 8 / 24 cannot take it and go to
+    the VALU forms, as does a forced VALU hint: LDS-staged when forced (hint
+    4) or from 256 pixel blocks, never under the scalar-cache hint (6)"""
+    if hint in (0, 5) and oc % 16 == 0 and oc <= 64:
+        return "conv_stem_mfma_kernel"
+    if hint != 6 and (hint == 4 or (m + 255) // 256 >= 256):
+        return "conv_stem_lds_kernel"
+    return "conv_stem_kernel"
 
 
 def test_conv_first_layer_3x3_s2_int8(gpu_lib):
@@ -205,12 +234,21 @@ def test_dwconv_taps_vs_per_tap(gpu_lib, b, h, w, ch, stride, dil, dtype):
     ref = c.oracle()
     # every form the shape allows: its own route, then each forced one
     # (BH_DW_RUN / _DOT / _MFMA; a form the shape cannot take falls back)
+    # every case here can take the run form (dilation 1 at stride 1 / 2, or
+    # dilation 2 at stride 1) and the dot form (C % 4 == 0); the MFMA form
+    # needs C % 16 == 0, and C = 12 / 20 / 24 stay on their own route instead
+    routed = kernel_name(gpu_lib, c)
+    assert routed in ("dwconv3x3_run_kernel", "dwconv3x3_dot_kernel"), routed
+    names = {0: routed, 1: "dwconv3x3_run_kernel", 2: "dwconv3x3_dot_kernel",
+             3: "dwconv3x3_mfma_kernel" if ch % 16 == 0 else routed}
     for hint in (0, 1, 2, 3):
         c.kernel_hint = hint
+        assert kernel_name(gpu_lib, c) == names[hint], "hint %d" % hint
         for fast in (None, False):
             c.requant_fast = fast
             np.testing.assert_array_equal(c.gpu(gpu_lib), ref, err_msg="hint %d requant_fast %s" % (hint, fast))
     c.kernel_hint, c.taps = 0, False
+    assert kernel_name(gpu_lib, c) == "dwconv3x3_kernel"
     np.testing.assert_array_equal(c.gpu(gpu_lib), ref)
 
 
@@ -226,6 +264,7 @@ def test_dwconv_mfma_mnv2_layers(gpu_lib, h, ch, stride, dtype):
     rng = np.random.default_rng(7700 + h * ch + stride + (dtype == np.uint8))
     c = ConvCase(rng, b, h, h, ch, ch, 3, 3, stride=(stride, stride), depthwise=True, dtype=dtype, kernel_hint=3)
     ref = c.oracle()
+    assert kernel_name(gpu_lib, c) == "dwconv3x3_mfma_kernel"  # every C here is a multiple of 16
     np.testing.assert_array_equal(c.gpu(gpu_lib), ref)
     c.requant_fast = False
     np.testing.assert_array_equal(c.gpu(gpu_lib), ref)
