@@ -27,7 +27,12 @@
 //            readers) and -> LDS [pix][N1]
 //   phase C  second 1x1 GEMM from that LDS tile, K = N1; requant -> HBM
 // Waves: wave w works on pixel block w % RB and on every (4/RB)-th channel
-// tile from w / RB, so every phase keeps all four waves busy.
+// tile from w / RB, so every phase keeps all four waves busy.  In the 32-pixel
+// form's phase A the waves split the channel groups instead, each over both
+// blocks (chain_dw_mfma_wg).  A round of a 1x1 phase issues everything it
+// reads from global memory - filter fragments, folded bias, multiplier,
+// shift - before its MFMAs; the 16-pixel forms issue the next phase's first
+// round before the barrier in front of it.
 #include <algorithm>
 
 #include "chain_dw.hpp"
@@ -177,17 +182,48 @@ __device__ __forceinline__ void copy_out_slice(const unsigned char* src, uint8_t
 // staging tiles as bytes (no packing); the HBM stores stay the contiguous
 // 16-byte copy_out.  The operand fragments are the same bytes as the
 // transposed form's: only the MFMA operand order changes.
+// gemm_tile_nt in two halves, as dw_load / dw_finish: what a tile's first
+// round needs from global memory - the first KB K-steps' filter fragments
+// and the lane's channel constants - depends on nothing the previous phase
+// computes, so the wave issues it BEFORE that phase's barrier (plain global
+// loads stay in flight across __syncthreads()) and the phase does not start
+// cold.
+template <int KB>
+struct TileHead {
+  v4i w[KB];
+  int be, mu, sh;
+};
+template <int KB>
+__device__ __forceinline__ void tile_head_load(const bh_conv_params& c, int t, int KS, int r16, int g,
+                                               TileHead<KB>& h) {
+  const int8_t* wrow = c.weights + (long)(t * 16 + r16) * c.k_pad + g * 16;
+#pragma unroll
+  for (int u = 0; u < KB; ++u)
+    if (u < KS) h.w[u] = *(const v4i*)(wrow + u * 64);
+  const int n = t * 16 + r16;
+  const int nl = n < c.out_c ? n : 0;
+  h.be = c.bias_eff[nl];
+  h.mu = c.mult[nl];
+  h.sh = c.shift[nl];
+}
 template <int KB = 4>
 __device__ __forceinline__ v4i gemm_tile_nt(const bh_conv_params& c, const unsigned char* xrow, int t, int KS,
-                                            int r16, int g) {
+                                            int r16, int g, const TileHead<KB>& h) {
   const int8_t* wrow = c.weights + (long)(t * 16 + r16) * c.k_pad + g * 16;
-  const int n = t * 16 + r16;
-  const int be = c.bias_eff[n < c.out_c ? n : 0];
-  v4i acc = (v4i){be, be, be, be};
+  v4i acc = (v4i){h.be, h.be, h.be, h.be};
+  {
+    v4i x[KB];
+#pragma unroll
+    for (int u = 0; u < KB; ++u)
+      if (u < KS) x[u] = *(const v4i*)(xrow + u * 64);
+#pragma unroll
+    for (int u = 0; u < KB; ++u)
+      if (u < KS) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(x[u], h.w[u], acc, 0, 0, 0);
+  }
   // KB K-steps' filter fragments are issued before any of their MFMAs (a
   // ragged last batch included): K <= 64 * KB costs one L2 round trip
   // instead of one per K-step
-  for (int k = 0; k < KS; k += KB) {
+  for (int k = KB; k < KS; k += KB) {
     v4i w[KB], x[KB];
 #pragma unroll
     for (int u = 0; u < KB; ++u)
@@ -206,40 +242,62 @@ __device__ __forceinline__ v4i gemm_tile_nt(const bh_conv_params& c, const unsig
 // per memory round trip (every tile's filter fragments and epilogue
 // operands issued before their MFMAs); epi(t, n, acc, mult, shift)
 // finishes a tile for this lane's channel n (may be >= out_c).
-template <int KMAX, int TT = 2, typename Epi>
-__device__ __forceinline__ void gemm_xs_nt(const bh_conv_params& c, const unsigned char* xrow, int KS, int t0,
-                                           int tstep, int r16, int g, Epi&& epi, int t_end = -1) {
+// The load half is xs_round_load (one round: TT tiles from t, T = the end of
+// the wave's tile range), so that a phase's first round can be issued before
+// the previous phase's barrier; gemm_xs_nt_from starts from such a round.
+template <int KMAX, int TT>
+struct XsRound {
+  int tt[TT], be[TT], mu[TT], sh[TT];
+  v4i w[TT][KMAX];
+};
+template <int KMAX, int TT>
+__device__ __forceinline__ void xs_round_load(const bh_conv_params& c, int KS, int t, int tstep, int T, int r16,
+                                              int g, XsRound<KMAX, TT>& rd) {
+#pragma unroll
+  for (int u = 0; u < TT; ++u) {
+    rd.tt[u] = t + u * tstep < T ? t + u * tstep : t;  // past the end: a duplicate, not finished
+    const int8_t* r = c.weights + (long)(rd.tt[u] * 16 + r16) * c.k_pad + g * 16;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k)
+      if (k < KS) rd.w[u][k] = *(const v4i*)(r + k * 64);
+    const int n = rd.tt[u] * 16 + r16;
+    const int l = n < c.out_c ? n : 0;
+    rd.be[u] = c.bias_eff[l];
+    rd.mu[u] = c.mult[l];
+    rd.sh[u] = c.shift[l];
+  }
+}
+// `rd` holds the round of tile t0 (loaded by the caller when t0 < T)
+template <int KMAX, int TT, typename Epi>
+__device__ __forceinline__ void gemm_xs_nt_from(const bh_conv_params& c, const unsigned char* xrow, int KS, int t0,
+                                                int tstep, int T, int r16, int g, XsRound<KMAX, TT>& rd, Epi&& epi) {
   v4i x[KMAX];
 #pragma unroll
   for (int k = 0; k < KMAX; ++k) x[k] = k < KS ? *(const v4i*)(xrow + k * 64) : (v4i){0, 0, 0, 0};
-  const int T = t_end >= 0 ? t_end : (c.out_c + 15) >> 4;
   for (int t = t0; t < T; t += TT * tstep) {
-    int tt[TT], nn[TT], mu[TT], sh[TT];
-    v4i w[TT][KMAX], acc[TT];
+    if (t != t0) xs_round_load<KMAX, TT>(c, KS, t, tstep, T, r16, g, rd);
+    v4i acc[TT];
 #pragma unroll
-    for (int u = 0; u < TT; ++u) {
-      tt[u] = t + u * tstep < T ? t + u * tstep : t;  // past the end: a duplicate, not finished
-      const int8_t* r = c.weights + (long)(tt[u] * 16 + r16) * c.k_pad + g * 16;
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k)
-        if (k < KS) w[u][k] = *(const v4i*)(r + k * 64);
-      nn[u] = tt[u] * 16 + r16;
-      const int l = nn[u] < c.out_c ? nn[u] : 0;
-      const int b = c.bias_eff[l];
-      mu[u] = c.mult[l];
-      sh[u] = c.shift[l];
-      acc[u] = (v4i){b, b, b, b};
-    }
+    for (int u = 0; u < TT; ++u) acc[u] = (v4i){rd.be[u], rd.be[u], rd.be[u], rd.be[u]};
 #pragma unroll
     for (int k = 0; k < KMAX; ++k)
       if (k < KS) {
 #pragma unroll
-        for (int u = 0; u < TT; ++u) acc[u] = __builtin_amdgcn_mfma_i32_16x16x64_i8(x[k], w[u][k], acc[u], 0, 0, 0);
+        for (int u = 0; u < TT; ++u)
+          acc[u] = __builtin_amdgcn_mfma_i32_16x16x64_i8(x[k], rd.w[u][k], acc[u], 0, 0, 0);
       }
 #pragma unroll
     for (int u = 0; u < TT; ++u)
-      if (u == 0 || tt[u] != t) epi(tt[u], nn[u], acc[u], mu[u], sh[u]);
+      if (u == 0 || rd.tt[u] != t) epi(rd.tt[u], rd.tt[u] * 16 + r16, acc[u], rd.mu[u], rd.sh[u]);
   }
+}
+template <int KMAX, int TT = 2, typename Epi>
+__device__ __forceinline__ void gemm_xs_nt(const bh_conv_params& c, const unsigned char* xrow, int KS, int t0,
+                                           int tstep, int r16, int g, Epi&& epi) {
+  const int T = (c.out_c + 15) >> 4;
+  XsRound<KMAX, TT> rd;
+  if (t0 < T) xs_round_load<KMAX, TT>(c, KS, t0, tstep, T, r16, g, rd);
+  gemm_xs_nt_from<KMAX, TT>(c, xrow, KS, t0, tstep, T, r16, g, rd, epi);
 }
 
 // RB == 4 form of gemm_xs_nt: wave w takes channel tiles w, w+4, ... for
@@ -309,7 +367,6 @@ __global__ __launch_bounds__(NW * 64) BH_CHAIN_OCC void chain_kernel(bh_chain_pa
   const int m0 = blk * RB * 16;
   const int rows = min(RB * 16, P - m0);
   const int m = m0 + pb * 16 + r16;  // this lane's pixel as an A-operand row
-  const bool mval = m < P;
   unsigned char* dl = smem;           // [RB*16][S1] depthwise output; then [RB*16][N2] second 1x1 output
   unsigned char* pl = smem + off_pl;  // [RB*16][S2] first 1x1 output (second 1x1's operand)
   unsigned char* o1 = smem + off_o1;  // [RB*16][N1] first 1x1 output staged for HBM
@@ -336,9 +393,31 @@ __global__ __launch_bounds__(NW * 64) BH_CHAIN_OCC void chain_kernel(bh_chain_pa
   CHAIN_STAMP(0)
   if (stamps && threadIdx.x == 0) stamps[7] = t_entry;
 
-  // ---- phase A: depthwise 3x3 -> LDS -------------------------------------
   constexpr bool SPLIT = (VAR & 2) != 0;
-  chain_dw_mfma<FAST, DA, WPB>(cp.dw, dv, m, mval, lane, r16, g, wsub, dl, S1, orow);
+  // Prefetch across the phase barriers (the 16-pixel forms): the first round
+  // of a phase's global operands depends on nothing the previous phase
+  // computes, and plain global loads stay in flight across __syncthreads().
+  // PFC: phase C's first round is issued before the phase-B barrier.  PFB:
+  // the first round of phase B's tile loop before phase A - it pays with 16
+  // waves (most waves hold one tile) and costs the 4- and 8-wave forms
+  // 1-4 % (profiles/r08a_chain_variants.txt), so only there.
+  constexpr bool PFC = RB == 1 && DA == 2;
+  constexpr bool PFB = PFC && NW == 16;
+  constexpr int KBB = DA > 2 ? 8 : 4;  // K-steps per round of phase B's tile loop
+  TileHead<KBB> b_head;
+  if constexpr (PFB) {
+    const int KS1 = cp.pw1.k_pad >> 6;
+    if (KS1 > KX && wsub < (cp.pw1.out_c + 15) >> 4) tile_head_load<KBB>(cp.pw1, wsub, KS1, r16, g, b_head);
+  }
+
+  // ---- phase A: depthwise 3x3 -> LDS -------------------------------------
+  if constexpr (RB == 2 && DA == 2) {
+    // the waves split the channel groups, each over both pixel blocks: the
+    // per-group work (tap row, filter fragments, ChanQ) serves two items
+    chain_dw_mfma_wg<FAST, RB, NW>(cp.dw, dv, m0, P, lane, r16, g, wave, dl, S1);
+  } else {
+    chain_dw_mfma<FAST, DA, WPB>(cp.dw, dv, m, m < P, lane, r16, g, wsub, dl, S1, orow);
+  }
   __syncthreads();
   CHAIN_STAMP(1)
 
@@ -403,11 +482,29 @@ __global__ __launch_bounds__(NW * 64) BH_CHAIN_OCC void chain_kernel(bh_chain_pa
       gemm_xs_nt<KX, TTC>(a, xrow, KS1, wsub, WPB, r16, g, epi);
     } else {
       for (int t = wsub; t < T1; t += WPB) {
-        const v4i acc = gemm_tile_nt<(DA > 2 ? 8 : 4)>(a, xrow, t, KS1, r16, g);
-        const int n = t * 16 + r16;
-        const int nl = n < N1 ? n : 0;
-        epi(t, n, acc, a.mult[nl], a.shift[nl]);
+        if (!PFB || t != wsub) tile_head_load<KBB>(a, t, KS1, r16, g, b_head);
+        const v4i acc = gemm_tile_nt<KBB>(a, xrow, t, KS1, r16, g, b_head);
+        epi(t, t * 16 + r16, acc, b_head.mu, b_head.sh);
       }
+    }
+  }
+  // phase C's channel tiles [lo, hi): all, or this workgroup's grid.y slice
+  struct CTiles {
+    int lo, hi;
+  };
+  auto c_tiles = [&]() {
+    const int T2 = (cp.pw2.out_c + 15) >> 4;
+    if constexpr (SPLIT)
+      return CTiles{(int)blockIdx.y * T2 / (int)gridDim.y, ((int)blockIdx.y + 1) * T2 / (int)gridDim.y};
+    else
+      return CTiles{0, T2};
+  };
+  XsRound<KX, TTC> c_first;
+  if constexpr (PFC) {
+    if (cp.has_pw2) {
+      const CTiles ct = c_tiles();
+      if (ct.lo + wsub < ct.hi)
+        xs_round_load<KX, TTC>(cp.pw2, cp.pw2.k_pad >> 6, ct.lo + wsub, WPB, ct.hi, r16, g, c_first);
     }
   }
   __syncthreads();
@@ -422,6 +519,7 @@ __global__ __launch_bounds__(NW * 64) BH_CHAIN_OCC void chain_kernel(bh_chain_pa
     const bh_conv_params& b = cp.pw2;
     const int N2 = b.out_c;
     const int KS2 = b.k_pad >> 6;
+    const CTiles ct = c_tiles();
     const unsigned char* xrow = pl + prow * S2 + g * 16;
     auto epi4 = [&](int n, const v4i* acc, int mu, int sh) {
       if (n >= N2) return;
@@ -442,15 +540,12 @@ __global__ __launch_bounds__(NW * 64) BH_CHAIN_OCC void chain_kernel(bh_chain_pa
       for (int r = 0; r < 4; ++r) v[r] = requant_out<FAST>(acc[r], q, b.out_zp, b.act_min, b.act_max);
       stage4(dl, N2, orow, n, v);
     };
-    if constexpr (SPLIT) {
-      // this workgroup's channel tiles [t_lo, t_hi) (grid.y slices)
-      const int T2 = (N2 + 15) >> 4;
-      const int t_lo = (int)blockIdx.y * T2 / (int)gridDim.y, t_hi = ((int)blockIdx.y + 1) * T2 / (int)gridDim.y;
-      if constexpr (AM) gemm_xs4_nt<KX>(b, pl, S2, KS2, wave, r16, g, epi4, t_lo, t_hi);
-      else gemm_xs_nt<KX, TTC>(b, xrow, KS2, t_lo + wsub, WPB, r16, g, epi1, t_hi);
+    if constexpr (AM) {
+      gemm_xs4_nt<KX>(b, pl, S2, KS2, wave, r16, g, epi4, ct.lo, ct.hi);
     } else {
-      if constexpr (AM) gemm_xs4_nt<KX>(b, pl, S2, KS2, wave, r16, g, epi4);
-      else gemm_xs_nt<KX, TTC>(b, xrow, KS2, wsub, WPB, r16, g, epi1);
+      const int tc0 = ct.lo + wsub;  // this wave's tiles: tc0, tc0 + WPB, ...
+      if (!PFC && tc0 < ct.hi) xs_round_load<KX, TTC>(b, KS2, tc0, WPB, ct.hi, r16, g, c_first);
+      gemm_xs_nt_from<KX, TTC>(b, xrow, KS2, tc0, WPB, ct.hi, r16, g, c_first, epi1);
     }
   }
   __syncthreads();
