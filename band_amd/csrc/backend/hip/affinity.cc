@@ -11,6 +11,7 @@
 #include <mutex>
 #include <sstream>
 
+#include "backend/hip/env.h"
 #include "band/device/cpu.h"
 #include "band_hip_kernels.h"
 
@@ -115,8 +116,7 @@ bool PinCallingThreadToGpu(int ordinal) {
   if (pinned == ordinal) return ok;
   pinned = ordinal;
   ok = false;
-  const char* env = std::getenv("BANDX_NUMA_PIN");
-  if (env && env[0] == '0') return ok;
+  if (!env::NumaPin()) return ok;
   // resolved once per ordinal for the process
   static std::mutex mu;
   static std::vector<std::vector<int>> cache;
@@ -168,8 +168,7 @@ int PinProcessToCpus(const std::vector<int>& cpus) {
 }
 
 int PinProcessToGpu(int ordinal) {
-  const char* env = std::getenv("BANDX_NUMA_PIN");
-  if (env && env[0] == '0') return 0;
+  if (!env::NumaPin()) return 0;
   const std::vector<int> cpus = GpuNumaCpus(ordinal);
   if (cpus.empty() || cpus.size() == ProcessCpus().size()) return 0;
   return PinProcessToCpus(cpus);

@@ -63,15 +63,10 @@ std::unordered_map<void*, long long> g_ring_blocks;
 // one-job passes DMA them directly (HipModelExecutor::ExecuteJobBatchDirect)
 extern "C" void* bhx_ring_host_alloc(size_t bytes) {
   static const bool on = [] {
-    const char* e = std::getenv("BAND_HIP_PINNED_RINGS");
     int n = 0;
-    return !(e && e[0] == '0') && bh_device_count(&n) == 0 && n > 0;
+    return bh_device_count(&n) == 0 && n > 0;
   }();
-  static const long long cap = [] {
-    const char* e = std::getenv("BAND_HIP_PINNED_RING_MB");
-    const long long mb = e ? std::atoll(e) : 8192;
-    return (mb > 0 ? mb : 0) << 20;
-  }();
+  constexpr long long cap = 8192LL << 20;  // page-locked ring memory per process
   if (!on || bytes == 0) return nullptr;
   const long long b = static_cast<long long>(bytes);
   {

@@ -8,6 +8,7 @@
 #include <string>
 #include <tuple>
 
+#include "backend/hip/env.h"
 #include "backend/hip/model_executor.h"
 
 namespace band {
@@ -43,10 +44,9 @@ std::shared_ptr<JobCoalescer> JobCoalescer::Join(HipModelExecutor* e, interface:
       c->num_lanes_ = std::max(1, lanes);
       c->ordinal_ = ordinal;
       for (int l = 0; l < c->num_lanes_; ++l) c->free_lanes_.push_back(l);
-      if (const char* io = std::getenv("BAND_HIP_COALESCE_IO")) c->dma_io_ = std::string(io) == "dma";
-      if (const char* w = std::getenv("BAND_HIP_COALESCE_WAIT_US")) c->wait_us_ = std::max(0, std::atoi(w));
-      // test hook: the lane build fails as it would out of device memory
-      if (const char* f = std::getenv("BAND_HIP_COALESCE_FAIL_BUILD")) c->fail_build_ = std::atoi(f) != 0;
+      c->dma_io_ = std::string(env::CoalesceIo()) == "dma";
+      c->wait_us_ = env::CoalesceWaitUs();
+      c->fail_build_ = env::CoalesceFailBuild();
       slot = c;
     }
   }

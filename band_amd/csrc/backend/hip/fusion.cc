@@ -3,6 +3,7 @@
 // form timed on the real buffers, decisions cached per geometry / device and
 // in BAND_HIP_TUNE_FILE), glue-op epilogue folds.  Split from model_executor.cc.
 #include "backend/hip/chain_form.h"
+#include "backend/hip/env.h"
 #include "backend/hip/executor_internal.h"
 #include <mutex>
 #include <optional>
@@ -262,8 +263,8 @@ std::mutex g_tune_mu;
 std::unordered_map<std::string, int> g_tune;
 
 const char* TuneFile() {
-  const char* f = std::getenv("BAND_HIP_TUNE_FILE");
-  return f && f[0] ? f : nullptr;
+  const char* f = env::TuneFile();
+  return f[0] ? f : nullptr;
 }
 std::optional<int> TuneLookup(const std::string& key) {
   std::lock_guard<std::mutex> lk(g_tune_mu);
@@ -287,11 +288,6 @@ void TuneStore(const std::string& key, int value) {
     std::fclose(fp);
   }
   g_tune[key] = value;
-}
-// BAND_HIP_TUNE_LOG=1: every measured form of every chain on stderr
-bool TuneLog() {
-  static const bool on = std::getenv("BAND_HIP_TUNE_LOG") != nullptr;
-  return on;
 }
 
 // The time to beat: fusion must win over the unfused launches by more than
@@ -576,7 +572,6 @@ void HipModelExecutor::FuseChains(const HipModel& model, PreparedSubgraph* sg) {
       if (autotune_) {
         u = TimeLaunches(base, 10);
         if (ok3) u_p2 = TimeLaunches({P2}, 10);
-        if (TuneLog()) std::fprintf(stderr, "[chain-tune] %s unfused %.2f (pw2 %.2f)\n", key, u, u_p2);
       }
       const bool measured = u > 0 && u_p2 >= 0;
       Fastest best(u);
@@ -589,16 +584,9 @@ void HipModelExecutor::FuseChains(const HipModel& model, PreparedSubgraph* sg) {
           const double us = TimeLaunches({&F}, 10);
           // the 2-launch form leaves the second 1x1 a launch of its own
           const double total = us + (f.launches == 2 && ok3 ? u_p2 : 0.0);
-          if (TuneLog() && f.stage)
-            std::fprintf(stderr, "[chain-tune]   form3 stage%d px%d w%d split%d: %.2f\n", f.stage, f.px_blocks, f.waves,
-                         f.c_split, us);
-          else if (TuneLog())
-            std::fprintf(stderr, "[chain-tune]   form%d px%d w%d persist%d tile%d deep%d split%d: %.2f\n", f.launches,
-                         f.px_blocks, f.waves, f.persist, f.tile, f.deep, f.c_split, total);
           if (best.Offer(us > 0 ? total : us)) form = f;
         }
       }
-      if (measured && TuneLog()) std::fprintf(stderr, "[chain-tune] %s -> %d\n", key, Encode(form));
       if (measured) TuneStore(key, Encode(form));
       else form = ForcedForm(ForcedChain::kPlain, ok3 ? c3 : c2);  // no device timing: 3 launches when they apply
     }

@@ -4,6 +4,7 @@
 #include "backend/hip/executor_internal.h"
 
 #include "backend/hip/affinity.h"
+#include "backend/hip/env.h"
 
 namespace band {
 namespace hip {
@@ -29,14 +30,12 @@ absl::Status HipModelExecutor::PrepareJobBatches(interface::IModel* model, const
   // anchors (2, 4, 8, .., max_batch) measure their fusion choices; every
   // other size reuses the next anchor's.  Anchors are prepared first, the
   // largest first of all: its arena and mirrors serve every variant.
-  int step = 1;
-  if (const char* e = std::getenv("BAND_HIP_BATCH_STEP")) step = std::max(1, std::atoi(e));
   std::vector<int> anchors;
   for (int b = 2; b < max_batch; b *= 2) anchors.push_back(b);
   anchors.push_back(max_batch);
   std::vector<int> order(anchors.rbegin(), anchors.rend());
   for (int b = max_batch - 1; b >= 2; --b)
-    if ((b % step == 0) && std::find(anchors.begin(), anchors.end(), b) == anchors.end()) order.push_back(b);
+    if (std::find(anchors.begin(), anchors.end(), b) == anchors.end()) order.push_back(b);
   // the base's op set, or {} when the base was prepared as the whole model
   // (model-order I/O): the variants' I/O order is the base's
   std::set<int> ops;
@@ -67,7 +66,6 @@ absl::Status HipModelExecutor::PrepareJobBatches(interface::IModel* model, const
                                               PinnableCpus(thread_affinity_mask_));
       v.exec->cpu_pool_ = cpu_pool_;
     }
-    v.exec->io_stream_bytes_ = io_stream_bytes_;
     if (largest) {
       PreparedSubgraph* ls = largest->Find(key);
       v.exec->shared_arena_ = ls ? ls->arena : nullptr;
@@ -88,10 +86,7 @@ absl::Status HipModelExecutor::PrepareJobBatches(interface::IModel* model, const
   // rarely used size (a few jobs) captured inside the serving path, a
   // stall of that worker's lane of ~ms while its jobs wait.
   // BAND_HIP_PRECAPTURE=0 keeps the lazy capture (A-B runs).
-  static const bool precapture = [] {
-    const char* e = std::getenv("BAND_HIP_PRECAPTURE");
-    return !(e && e[0] == '0');
-  }();
+  static const bool precapture = env::Precapture();
   if (device_flag_ == DeviceFlag::kGPU && use_graph_ && precapture) {
     for (JobBatchVariant& v : variants) {
       PreparedSubgraph* vs = v.exec->Find(key);

@@ -15,6 +15,7 @@
 
 #include "backend/hip/affinity.h"
 #include "backend/hip/completion.h"
+#include "backend/hip/env.h"
 #include "backend/hip/executor_internal.h"
 
 namespace band {
@@ -42,28 +43,18 @@ HipModelExecutor::HipModelExecutor(ModelId model_id, WorkerId worker_id, DeviceF
     // executor's pool instead (PrepareJobBatches)
     cpu_pool_ = std::make_shared<CpuPool>(num_threads_ > 0 ? num_threads_ : 1, PinnableCpus(thread_affinity_mask_));
   }
-  const char* g = std::getenv("BAND_HIP_GRAPH");
-  if (g && g[0] == '0') use_graph_ = false;
-  if (const char* io = std::getenv("BAND_HIP_IO")) {
-    const std::string m(io);
-    io_mode_ = m == "graph" ? 0 : m == "stream" ? 1 : 2;
-  }
-  if (const char* b = std::getenv("BAND_HIP_IO_STREAM_BYTES")) io_stream_bytes_ = std::strtoull(b, nullptr, 10);
-  if (const char* sy = std::getenv("BAND_HIP_SYNC")) {
-    const std::string m(sy);
-    sync_mode_ = m == "block"    ? kSyncBlock
-                 : m == "poll"     ? kSyncPoll
-                 : m == "poller"   ? kSyncPoller
-                 : m == "spin"     ? kSyncSpin
-                                   : kSyncAdaptive;
-  }
-  if (const char* f = std::getenv("BAND_HIP_SYNC_SLEEP")) sleep_frac_ = std::min(0.95, std::max(0.0, std::atof(f)));
-  if (const char* f = std::getenv("BAND_HIP_SYNC_MIN_US")) sleep_min_us_ = std::max(0.0, std::atof(f));
+  use_graph_ = env::Graph();
+  const std::string m(env::Sync());
+  sync_mode_ = m == "block"    ? kSyncBlock
+               : m == "poll"     ? kSyncPoll
+               : m == "poller"   ? kSyncPoller
+               : m == "spin"     ? kSyncSpin
+                                 : kSyncAdaptive;
   block_sync_ = sync_mode_ == kSyncBlock;
-  if (const char* d = std::getenv("BAND_HIP_DIRECT_IO")) direct_io_ = d[0] != '0';
-  if (const char* c = std::getenv("BAND_HIP_COALESCE")) coalesce_max_ = std::atoi(c);
-  if (const char* c = std::getenv("BAND_HIP_COALESCE_LANES")) coalesce_lanes_ = std::max(1, std::atoi(c));
-  if (const char* dt = std::getenv("BAND_HIP_GPU_DETECTION")) gpu_detection_ = dt[0] == '1';
+  direct_io_ = env::DirectIo();
+  coalesce_max_ = env::Coalesce();
+  coalesce_lanes_ = env::CoalesceLanes();
+  gpu_detection_ = env::GpuDetection();
 }
 
 HipModelExecutor::~HipModelExecutor() {
@@ -90,7 +81,6 @@ std::unique_ptr<HipModelExecutor> HipModelExecutor::MakeLane() {
   lane->coalesce_ok_ = false;
   lane->use_graph_ = use_graph_;
   lane->io_mode_ = io_mode_;
-  lane->io_stream_bytes_ = io_stream_bytes_;
   lane->sync_mode_ = sync_mode_;
   lane->block_sync_ = block_sync_;
   // kernels-only variant graphs: the coalescer moves each pass's I/O on the
@@ -292,22 +282,21 @@ absl::Status HipModelExecutor::EnsureMeta(const HipModel& model) {
     for (int t : d.ops[i].outputs)
       if (t >= 0) producer_[t] = i;
   }
-  const char* f = std::getenv("BAND_HIP_FUSION");
-  if (f && f[0] == '0') allow_fusion_ = false;
-  if (f && std::strcmp(f, "noirb") == 0) allow_irb_ = false;   // diagnostics: one fusion kind at a time
-  if (f && std::strcmp(f, "noadd") == 0) allow_add_ = false;
-  if (f && std::strcmp(f, "nochain") == 0) allow_chain_ = false;
-  if (f && std::strcmp(f, "nogroup") == 0) allow_group_ = false;
-  if (f && std::strcmp(f, "forcechain") == 0) forced_chain_ = ForcedChain::kPlain;  // parity tests: every feasible chain
-  if (f && std::strcmp(f, "forcetile") == 0) forced_chain_ = ForcedChain::kTile;  // ... in the tile form
-  if (f && std::strcmp(f, "notile") == 0) no_tile_chain_ = true;  // A-B: the raster chain forms only
-  if (f && std::strcmp(f, "nodeep") == 0) no_deep_chain_ = true;  // A-B: without the deep-issue forms
-  if (f && std::strcmp(f, "nosplit") == 0) no_split_chain_ = true;  // A-B: without the phase-C split forms
-  if (f && std::strcmp(f, "forcedeep") == 0) forced_chain_ = ForcedChain::kDeep;  // ... in the deep form
-  if (f && std::strcmp(f, "forcestage") == 0) forced_chain_ = ForcedChain::kStage;  // ... in the stage form
-  if (f && std::strcmp(f, "nostage") == 0) no_stage_chain_ = true;  // A-B: without the stage forms
-  const char* at = std::getenv("BAND_HIP_AUTOTUNE");
-  if (at && at[0] == '0') autotune_ = false;
+  const char* f = env::Fusion();
+  if (f[0] == '0') allow_fusion_ = false;
+  if (std::strcmp(f, "noirb") == 0) allow_irb_ = false;   // diagnostics: one fusion kind at a time
+  if (std::strcmp(f, "noadd") == 0) allow_add_ = false;
+  if (std::strcmp(f, "nochain") == 0) allow_chain_ = false;
+  if (std::strcmp(f, "nogroup") == 0) allow_group_ = false;
+  if (std::strcmp(f, "forcechain") == 0) forced_chain_ = ForcedChain::kPlain;  // parity tests: every feasible chain
+  if (std::strcmp(f, "forcetile") == 0) forced_chain_ = ForcedChain::kTile;  // ... in the tile form
+  if (std::strcmp(f, "notile") == 0) no_tile_chain_ = true;  // A-B: the raster chain forms only
+  if (std::strcmp(f, "nodeep") == 0) no_deep_chain_ = true;  // A-B: without the deep-issue forms
+  if (std::strcmp(f, "nosplit") == 0) no_split_chain_ = true;  // A-B: without the phase-C split forms
+  if (std::strcmp(f, "forcedeep") == 0) forced_chain_ = ForcedChain::kDeep;  // ... in the deep form
+  if (std::strcmp(f, "forcestage") == 0) forced_chain_ = ForcedChain::kStage;  // ... in the stage form
+  if (std::strcmp(f, "nostage") == 0) no_stage_chain_ = true;  // A-B: without the stage forms
+  if (!env::Autotune()) autotune_ = false;
   return absl::OkStatus();
 }
 
@@ -354,22 +343,18 @@ absl::StatusOr<ModelSpec> HipModelExecutor::InvestigateModelSpec(interface::IMod
     // expansion (EfficientDet-Lite2's 37,629 x 90 class scores: 3.4 MB
     // instead of 13.5 MB per job, copied four times on the way).  The
     // outputs are the same (DEQUANTIZE is one exact table either side).
-    // BAND_HIP_CPU_BOUNDARY_DEQUANT=0 keeps every DEQUANTIZE on the GPU.
-    const char* bd = std::getenv("BAND_HIP_CPU_BOUNDARY_DEQUANT");
-    if (!(bd && bd[0] == '0')) {
-      std::vector<std::vector<int>> users(d.tensors.size());
-      for (int i = 0; i < num_ops; ++i)
-        for (int t : d.ops[i].inputs)
-          if (t >= 0) users[t].push_back(i);
-      for (int i = 0; i < num_ops; ++i) {
-        const TflOperator& op = d.ops[i];
-        if (op.builtin != kTflDequantize || op.outputs.empty() || op.outputs[0] < 0) continue;
-        const std::vector<int>& u = users[op.outputs[0]];
-        if (u.empty()) continue;
-        bool cpu_only = true;
-        for (int c : u) cpu_only &= unsupported[flag].count(c) > 0;
-        if (cpu_only && CpuSupports(d, op, nullptr)) unsupported[flag].insert(i);
-      }
+    std::vector<std::vector<int>> users(d.tensors.size());
+    for (int i = 0; i < num_ops; ++i)
+      for (int t : d.ops[i].inputs)
+        if (t >= 0) users[t].push_back(i);
+    for (int i = 0; i < num_ops; ++i) {
+      const TflOperator& op = d.ops[i];
+      if (op.builtin != kTflDequantize || op.outputs.empty() || op.outputs[0] < 0) continue;
+      const std::vector<int>& u = users[op.outputs[0]];
+      if (u.empty()) continue;
+      bool cpu_only = true;
+      for (int c : u) cpu_only &= unsupported[flag].count(c) > 0;
+      if (cpu_only && CpuSupports(d, op, nullptr)) unsupported[flag].insert(i);
     }
   }
   for (int i = 0; i < num_ops; ++i)
@@ -589,13 +574,8 @@ absl::Status HipModelExecutor::EnqueueLaunch(const Launch& l) {
     case Launch::kConvGroup: rc = bh_conv_group_i8(&l.cgroup, stream_); break;
     case Launch::kCopy: {
       // a kernel copy, not a blit: graphs replayed under rocprofv3's kernel
-      // trace crash on blit (memcpy) nodes; BAND_HIP_BLIT_COPY=1 restores them
-      static const bool blit = [] {
-        const char* v = std::getenv("BAND_HIP_BLIT_COPY");
-        return v && v[0] == '1';
-      }();
-      if (l.src != l.dst)
-        rc = blit ? bh_memcpy_d2d_async(l.dst, l.src, l.bytes, stream_) : bh_copy_d2d(l.dst, l.src, l.bytes, stream_);
+      // trace crash on blit (memcpy) nodes
+      if (l.src != l.dst) rc = bh_copy_d2d(l.dst, l.src, l.bytes, stream_);
       break;
     }
     case Launch::kLutU8: rc = bh_lut_u8(l.src, l.dst, l.count, l.table, stream_); break;
@@ -647,10 +627,7 @@ absl::Status HipModelExecutor::EnqueueLaunch(const Launch& l) {
 // diagnostics only (tools/concurrency_probe.py --no-io): kernels without
 // the host copies, to separate device compute scaling from the transfers
 static bool ProbeNoIo() {
-  static const bool v = [] {
-    const char* e = std::getenv("BAND_HIP_PROBE_NO_IO");
-    return e && e[0] == '1';
-  }();
+  static const bool v = env::ProbeNoIo();
   return v;
 }
 
@@ -694,7 +671,7 @@ absl::Status HipModelExecutor::CaptureGraph(PreparedSubgraph* sg) {
   for (int t : sg->inputs) io_bytes += meta_[t]->bytes;
   for (int t : sg->outputs) io_bytes += meta_[t]->bytes;
   for (int t : sg->extra_d2h) io_bytes += meta_[t]->bytes;
-  sg->io_in_graph = io_mode_ == 0 || (io_mode_ == 2 && io_bytes < io_stream_bytes_);
+  sg->io_in_graph = io_mode_ == 0 || (io_mode_ == 2 && io_bytes < kIoStreamBytes);
   int rc = bh_capture_begin(stream_);
   if (rc) return HipErr(rc, "capture begin");
   absl::Status s = sg->io_in_graph ? Enqueue(sg) : EnqueueLaunches(sg);
@@ -864,7 +841,7 @@ absl::Status HipModelExecutor::WaitPass(PreparedSubgraph* sg) {
     return rc ? HipErr(rc, "stream sync") : absl::OkStatus();
   }
   if (sync_mode_ == kSyncAdaptive) {
-    // sleep through sleep_frac_ of the pass's expected wait, then spin in
+    // sleep through kSleepFrac of the pass's expected wait, then spin in
     // hipStreamSynchronize: the thread holds a core only for the tail of the
     // pass, and it is already running (no wake-up from an idle core, the
     // cost of the blocking forms) when the pass ends.  A wake-up that finds
@@ -875,7 +852,7 @@ absl::Status HipModelExecutor::WaitPass(PreparedSubgraph* sg) {
     // short passes (a batch-1 job: ~0.2 ms) spin: a sleep's wake-up jitter
     // is a large share of them (C2: 4.88k inf/s, p99 0.76 ms sleeping
     // against 5.09k, p99 0.37 ms spinning, profiles/r05r_c2*.json)
-    const double sleep = sg->wait_us >= sleep_min_us_ ? sleep_frac_ * sg->wait_us : 0.0;
+    const double sleep = sg->wait_us >= kSleepMinUs ? kSleepFrac * sg->wait_us : 0.0;
     bool overslept = false;
     if (sleep >= 20.0) {
       timespec ts{0, static_cast<long>(sleep * 1000.0)};

@@ -153,8 +153,8 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   void ForEachSubgraph(std::function<void(const SubgraphKey&)> visitor) override;
 
   // --- job batching (backend/hip/job_batching.h; kGPU executors) ---
-  // A variant for every batch 2 .. max_batch (BAND_HIP_BATCH_STEP, default
-  // 1), so a pass of n jobs computes exactly n images: each is an executor
+  // A variant for every batch 2 .. max_batch, so a pass of n jobs computes
+  // exactly n images: each is an executor
   // of a batch-B copy of the model (HipModel::CloneWithJobBatch) over the
   // same op set, on this executor's stream, sharing its device weights.  All
   // variants of one subgraph share ONE activation arena and one set of
@@ -302,10 +302,11 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   // Where a graph pass's host copies go: captured into the graph (blit
   // kernels on the compute queue; lowest latency for small transfers) or
   // issued on the stream around a kernels-only graph (DMA engines, leaving
-  // the CUs to the kernels of concurrent passes).  BAND_HIP_IO = graph |
-  // stream | auto (default: stream from io_stream_bytes_ of host I/O per
-  // pass, BAND_HIP_IO_STREAM_BYTES)
+  // the CUs to the kernels of concurrent passes).  auto: stream from
+  // kIoStreamBytes of host I/O per pass; job-batch variants with direct I/O
+  // stream always (job_batch.cc)
   int io_mode_ = 2;  // 0 graph, 1 stream, 2 auto
+  static constexpr size_t kIoStreamBytes = 512 << 10;
   // How a pass is waited for.  spin (BAND_HIP_SYNC=spin): hipStreamSynchronize, which
   // busy-polls - a core per GPU worker for the whole pass, and the lowest
   // completion latency.  block (BAND_HIP_SYNC=block): a blocking-sync event.
@@ -319,15 +320,15 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   // pass's event completes - one polling core per GPU instead of one per
   // waiting thread.
   // adaptive (default since round 5; BAND_HIP_SYNC=spin restores spinning):
-  // sleep through BAND_HIP_SYNC_SLEEP (default 0.85) of the pass's expected
-  // wait, then spin (WaitPass).  C3 headline, interleaved on one box
+  // sleep through kSleepFrac of the pass's expected wait, then spin
+  // (WaitPass).  C3 headline, interleaved on one box
   // (profiles/r05p_*): spin 109.8k / 103.4k inf/s at 8.9 / 8.7 process
   // cores; adaptive 0.7 109.1k / 110.0k at 4.5 / 4.2; 0.85 108.4k / 109.6k
   // at 4.1 / 4.0 (one of them the request driver's submitter thread).
   enum SyncMode { kSyncSpin = 0, kSyncBlock = 1, kSyncPoll = 2, kSyncPoller = 3, kSyncAdaptive = 4 };
   int sync_mode_ = kSyncAdaptive;
-  double sleep_frac_ = 0.85;
-  double sleep_min_us_ = 500.0;  // BAND_HIP_SYNC_MIN_US: expected waits below this spin
+  static constexpr double kSleepFrac = 0.85;
+  static constexpr double kSleepMinUs = 500.0;  // expected waits below this spin
   bool block_sync_ = false;  // sync_mode_ == kSyncBlock
   // waits for everything enqueued on stream_ (the pass of `sg`)
   absl::Status WaitPass(PreparedSubgraph* sg);
@@ -336,7 +337,6 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   // BAND_HIP_DIRECT_IO=0 stages them through the slot views instead
   bool direct_io_ = true;
   bh_event_t done_event_ = nullptr;
-  size_t io_stream_bytes_ = 512 << 10;
   // job-batch variants: the arena / boundary mirrors of the largest variant
   // (PrepareSubgraph uses them when big enough), and the anchor batch whose
   // measured fusion choices this variant reuses (0: its own batch)

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "engine/engine.h"
+#include "engine/env.h"
 #include "engine/logger.h"
 #include "engine/planner.h"
 #include "engine/time.h"
@@ -438,8 +439,7 @@ BandStatus DriveRequests(BandEngine* engine, BandModel** models, BandTensor** in
   // Submitters (BANDX_DRIVER_LANES, default 1) copy requests into the rings
   // (150 KB per 224x224 job); readers (BANDX_DRIVER_READERS, default 6) copy
   // results out (DeepLab's are 1 MB), each into output tensors of its own.
-  int lanes = 1;
-  if (const char* lv = std::getenv("BANDX_DRIVER_LANES")) lanes = std::max(1, std::atoi(lv));
+  int lanes = band::env::DriverLanes();
   // a shard of the models per lane up to one model per shard (below); more
   // lanes than models share a shard: its runs are dealt to them in turn
   // (one engine over several GPUs needs several submitters per model)
@@ -450,14 +450,12 @@ BandStatus DriveRequests(BandEngine* engine, BandModel** models, BandTensor** in
   const int lanes_per_shard = (lanes + n_shards - 1) / n_shards;
   // requests of one model submitted per RequestAsync call (closed loop:
   // the job -> model order is run-major, `burst` jobs per model in turn)
-  int burst = burst_hint > 0 ? burst_hint : 1;
-  if (const char* bv = std::getenv("BANDX_DRIVER_BURST")) burst = std::max(1, std::atoi(bv));
+  int burst = band::env::DriverBurst(burst_hint > 0 ? burst_hint : 1);
   burst = std::max(1, std::min(burst, max_inflight / std::max(1, lanes)));
   for (int m = 0; m < n_models; ++m)
     burst = std::max(1, std::min(burst, e.RequestRingSize(models[m]->impl->GetId()) /
                                             (2 * std::max(n_shards, lanes_per_shard + 1))));
-  int readers = 6;
-  if (const char* rv = std::getenv("BANDX_DRIVER_READERS")) readers = std::max(1, std::atoi(rv));
+  int readers = band::env::DriverReaders();
   readers = std::max(1, std::min(readers, n_jobs > 0 ? n_jobs : 1));
   readers = std::max(readers, n_shards);  // every shard has a reader
   std::vector<std::vector<std::vector<std::unique_ptr<band::Tensor>>>> reader_outs(readers);

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "engine/env.h"
 #include "engine/logger.h"
 #include <limits>
 
@@ -222,8 +223,7 @@ absl::Status Engine::RegisterModel(Model* model) {
     // are taken in order, so one slow job stalls new requests of its model
     // once 128 younger ones are outstanding - deep closed loops over
     // several workers want more)
-    int slots = 128;
-    if (const char* rs = std::getenv("BANDX_REQUEST_RING_SLOTS")) slots = std::max(1, std::atoi(rs));
+    const int slots = env::RequestRingSlots();
     const RingHostAllocator ring_alloc = RingAllocatorFor(model_id, spec.num_ops);
     model_input_buffer_[model_id].reset(new TensorRingBuffer(
         in_views, std::vector<int>(spec.input_tensors.begin(), spec.input_tensors.end()), slots, ring_alloc));

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <mutex>
 
+#include "engine/env.h"
 #include "engine/logger.h"
 
 namespace band {
@@ -55,12 +56,9 @@ namespace {
 // stores skip the read-for-ownership of every destination line that plain
 // stores pay (the slot was last touched by the DMA, so each line would come
 // from DRAM) and leave the caches to the caller.  Large copies into ring
-// memory only; BANDX_RING_NT=0 keeps memcpy.
+// memory only.
 bool UseStreamingStores() {
-  static const bool on = [] {
-    const char* e = std::getenv("BANDX_RING_NT");
-    return !(e && e[0] == '0') && __builtin_cpu_supports("avx2");
-  }();
+  static const bool on = __builtin_cpu_supports("avx2");
   return on;
 }
 
@@ -171,8 +169,7 @@ TensorRingBuffer::TensorRingBuffer(const std::vector<std::shared_ptr<interface::
       held_(size_, 0) {
   // read per ring (not once per process), so an engine created after a
   // change of the variable sees it
-  const char* hold = std::getenv("BANDX_OUTPUT_HOLD_MS");
-  hold_ms_ = hold ? std::max(0L, std::atol(hold)) : 2000L;
+  hold_ms_ = env::OutputHoldMs();
   std::vector<size_t> stride(tensors.size(), 0);
   if (a.alloc && a.free) {
     block_free_ = a.free;

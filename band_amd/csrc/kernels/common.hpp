@@ -115,19 +115,10 @@ __device__ __forceinline__ uint32_t quad_transpose8(uint32_t p) {
 
 // Stages a D = X W^T epilogue's 4 values (pixels row0 .. row0 + 3 of channel
 // `col`, this lane's r16 = col % 16) into an LDS tile of row stride `stride`:
-// quad-transposed, one dword per lane (BH_QUAD_STORE=1, default), or four
-// byte stores (0; build-time A-B switch).
-#ifndef BH_QUAD_STORE
-#define BH_QUAD_STORE 1
-#endif
+// quad-transposed, one dword per lane.
 __device__ __forceinline__ void stage4(unsigned char* tile, int stride, int row0, int col, const int32_t v[4]) {
-#if BH_QUAD_STORE
   const int r16 = col & 15;
   *(uint32_t*)(tile + (row0 + (r16 & 3)) * stride + col - r16 + (r16 & ~3)) = quad_transpose8(pack4_bytes(v));
-#else
-#pragma unroll
-  for (int r = 0; r < 4; ++r) tile[(row0 + r) * stride + col] = (unsigned char)v[r];
-#endif
 }
 
 // Division by a runtime-invariant divisor for dividends < 2^31, by the
@@ -174,19 +165,11 @@ __device__ __forceinline__ ChanQ chan_q(int32_t mu, int32_t sh, int32_t zp) {
 
 // clamp to [lo, hi] in one v_med3_i32 (min(max()) compiles to two VALU
 // when both bounds are wave-uniform: gfx9's VOP3 reads one SGPR, so the
-// compiler will not form the med3 itself); BH_MED3=0 at build time keeps
-// min / max
-#ifndef BH_MED3
-#define BH_MED3 1
-#endif
+// compiler will not form the med3 itself)
 __device__ __forceinline__ int32_t med3_clamp(int32_t v, int32_t lo, int32_t hi) {
-#if BH_MED3
   int32_t r;
   asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(v), "s"(lo), "v"(hi));
   return r;
-#else
-  return min(max(v, lo), hi);
-#endif
 }
 
 template <bool FAST>

@@ -204,15 +204,8 @@ __global__ __launch_bounds__(256) void conv_stem_kernel(bh_conv_params p, int M,
 // PX pixels per thread (m, m + 256, ...: stores stay lane-consecutive): the
 // channel records' LDS reads serve PX pixels and their dot / requant chains
 // interleave
-// BH_STEM_ROWS (build-time A-B switch, default on): input rows staged in LDS
-#ifndef BH_STEM_ROWS
-#define BH_STEM_ROWS 1
-#endif
+// input rows staged in LDS; 16-byte output stores
 constexpr int kStemRowWords = 3072;  // 12 KB: nine 224-pixel RGB rows
-// BH_STEM_STORE16 (build-time A-B switch, default on): 16-byte output stores
-#ifndef BH_STEM_STORE16
-#define BH_STEM_STORE16 1
-#endif
 template <bool FAST, int PX>
 __global__ __launch_bounds__(256) void conv_stem_lds_kernel(bh_conv_params p, int M, DirectDivs dv, int ch_per_y) {
   __shared__ __attribute__((aligned(16))) StemChan sc[64];
@@ -222,14 +215,13 @@ __global__ __launch_bounds__(256) void conv_stem_lds_kernel(bh_conv_params p, in
   const int m0 = blockIdx.x * 256 * PX + threadIdx.x;
   const long img = (long)p.in_h * p.in_w * 3;
   uint32_t xw[PX][7];
-  // staged rows (BH_STEM_ROWS, one pixel per thread): when the workgroup's
+  // staged rows (one pixel per thread): when the workgroup's
   // 256 pixels lie in one image and their input rows fit kStemRowWords,
   // the rows come in as 16-byte loads into LDS (one load per 16 bytes of
   // the image instead of nine dword loads per pixel) and each window is read
   // from there after the barrier
   bool staged = false;
   int iy_lo = 0, rw = 0, n_img = 0;
-#if BH_STEM_ROWS
   __shared__ __attribute__((aligned(16))) uint32_t rows[kStemRowWords];
   if constexpr (PX == 1) {
     const int mf = blockIdx.x * 256, ml = min(mf + 255, M - 1);
@@ -268,7 +260,6 @@ __global__ __launch_bounds__(256) void conv_stem_lds_kernel(bh_conv_params p, in
       }
     }
   }
-#endif
   if (!staged) {
     // the windows first: their loads are in flight while the constants stage
 #pragma unroll
@@ -291,7 +282,6 @@ __global__ __launch_bounds__(256) void conv_stem_lds_kernel(bh_conv_params p, in
     }
   }
   __syncthreads();
-#if BH_STEM_ROWS
   if (staged) {
     const int mm = min(m0, M - 1);
     const int t = dv.out_w.div(mm);
@@ -300,7 +290,6 @@ __global__ __launch_bounds__(256) void conv_stem_lds_kernel(bh_conv_params p, in
     stem_window_lds(rows, rw, iy_lo, n_img * (int)img, oy * p.stride_h - p.pad_h, ox * p.stride_w - p.pad_w, p.dil_h,
                     p.in_h, p.in_w, (uint32_t)p.in_xor, (uint32_t)p.in_zp, xw[0]);
   }
-#endif
   if (m0 >= M) return;
   int rowsum[PX];
 #pragma unroll
@@ -312,7 +301,6 @@ __global__ __launch_bounds__(256) void conv_stem_lds_kernel(bh_conv_params p, in
     }
   }
   const uint8_t* tab = (const uint8_t*)p.out_table;
-#if BH_STEM_STORE16
   // 16 channels per store (one 16-byte store per pixel instead of four
   // dword stores) when the channel range and the row pitch allow it
   if ((nc & 15) == 0 && (p.out_c & 15) == 0 && (cb & 15) == 0) {
@@ -343,7 +331,6 @@ __global__ __launch_bounds__(256) void conv_stem_lds_kernel(bh_conv_params p, in
     }
     return;
   }
-#endif
   for (int c0 = 0; c0 < nc; c0 += 4) {
     uint32_t packed[PX];
 #pragma unroll
@@ -389,7 +376,7 @@ namespace {
 // of <= 64, out_c % 4 == 0 for its dword stores, aligned output, from 256
 // workgroups - at batch 1 the staging is not repaid: 5.05 vs 4.87 us; B = 24:
 // 13.6 vs 14.6 us, r05u_stem_*) or the scalar-cache form
-// (BH_CONV_STEM_SCALAR, or BH_STEM_SCALAR=1 for A-B runs)
+// (BH_CONV_STEM_SCALAR)
 struct StemPlan {
   int gx, gy, ch_per_y;
   bool lds;

@@ -614,35 +614,22 @@ static int launch_shape(const bh_conv_params& p, int M, int K, int N, hipStream_
   return launch_cfg<1, 1, 2, 2, 1, IS1X1, VEC>(p, M, K, N, s);
 }
 
-// conv_gemm_kernel configuration (tools/gemm_cfg_sweep.sh, batch-24 C3
-// shapes): 128x128 tiles over 8 waves (64x32 each, 2 LDS buffers) once they
-// still give one workgroup per CU - PoseNet's 512/1024-channel layers, 1.6-2.7x
-// conv_mfma_kernel; otherwise 64x64 tiles over 8 waves (16x32 each, 3 LDS
-// buffers), which keep ~4 waves per SIMD on the mid-size layers.
-// BH_GEMM_CFG=1 selects the first 4-wave form (128x128 ... 64x64, 4 buffers);
-// 5: the two-tile rule without the 160-row tile.  Deeper LDS rings (3-4
-// K-steps ahead) and 4-wave 128x64 tiles measured no faster
-// (profiles/r03y_gemm.txt).
+// conv_gemm_kernel configuration (batch-24 C3 shapes): 128x128 tiles over 8
+// waves (64x32 each, 2 LDS buffers) once they still give one workgroup per
+// CU - PoseNet's 512/1024-channel layers, 1.6-2.7x conv_mfma_kernel;
+// otherwise 64x64 tiles over 8 waves (16x32 each, 3 LDS buffers), which keep
+// ~4 waves per SIMD on the mid-size layers.  4-wave forms (128x128 ... 64x64,
+// 4 buffers), deeper LDS rings (3-4 K-steps ahead) and 4-wave 128x64 tiles
+// measured no faster (profiles/r03y_gemm.txt).
 static int launch_gemm_shape(const bh_conv_params& p, int M, int K, hipStream_t s) {
   const int N = p.out_c;
-  static const int cfg = [] {
-    const char* e = std::getenv("BH_GEMM_CFG");  // A-B experiments
-    return e ? std::atoi(e) : 0;
-  }();
-  if (cfg == 1) {
-    if (wgs(M, N, 128, 128) >= 256) return launch_gemm<4, 4, 2, 2, 4>(p, M, K, s);
-    if (wgs(M, N, 128, 64) >= 256) return launch_gemm<4, 2, 2, 2, 4>(p, M, K, s);
-    if (wgs(M, N, 64, 128) >= 256) return launch_gemm<2, 4, 2, 2, 4>(p, M, K, s);
-    return launch_gemm<2, 2, 2, 2, 4>(p, M, K, s);
-  }
   // 128 x 128 tiles over 8 waves once they give a workgroup per CU; when
   // they give more than one round of workgroups but 160 x 128 tiles fit in
   // one, those (8 waves, 64 B of padding rows per wave staged per K-step).
-  // BH_GEMM_CFG=5: without the 160-row tile.  (4-wave 160 x 128 / 80 x 128
-  // tiles measured slower than two rounds of 8-wave ones:
-  // profiles/r03z_gemm.txt.)
+  // (4-wave 160 x 128 / 80 x 128 tiles measured slower than two rounds of
+  // 8-wave ones: profiles/r03z_gemm.txt.)
   const long w128 = wgs(M, N, 128, 128);
-  if (cfg != 5 && w128 > 256 && wgs(M, N, 160, 128) <= 256) return launch_gemm<5, 2, 2, 4, 2>(p, M, K, s);
+  if (w128 > 256 && wgs(M, N, 160, 128) <= 256) return launch_gemm<5, 2, 2, 4, 2>(p, M, K, s);
   if (w128 >= 256) return launch_gemm<4, 2, 2, 4, 2>(p, M, K, s);
   return launch_gemm<1, 2, 4, 2, 3>(p, M, K, s);
 }
@@ -661,42 +648,11 @@ const char* bh_conv_stem_kernel_name(const bh_conv_params& p, int M);           
 namespace {
 // batched 1x1 layers (K <= 320) at or above this many output pixels take the
 // x-stationary kernel conv_xs_kernel: measured faster than conv_mfma_kernel
-// on every MobileNetV2 1x1 shape from M = 3136 up (gpurun_out/lb_conv_*,
-// DESIGN.md); BH_CONV_XS_MIN_M overrides (diagnostics / tuning)
-long XsMinM() {
-  static const long v = [] {
-    const char* e = std::getenv("BH_CONV_XS_MIN_M");
-    return e ? std::atol(e) : 2048L;
-  }();
-  return v;
-}
-// conv_rows_kernel (any K) is opt-in: BH_CONV_ROWS_MIN_M = the M from which
-// deep-K batched 1x1 layers take it (default: never; slower than
-// conv_mfma_kernel on every K > 320 MobileNet shape measured)
-long RowsMinM() {
-  static const long v = [] {
-    const char* e = std::getenv("BH_CONV_ROWS_MIN_M");
-    return e ? std::atol(e) : -1L;
-  }();
-  return v;
-}
-
-// conv_gemm_kernel (LDS-staged GEMM): BH_CONV_GEMM=0 off, 1 (default) the
-// eligible layers of at least GemmMinOps() ops, 2 every eligible layer
-int GemmMode() {
-  static const int v = [] {
-    const char* e = std::getenv("BH_CONV_GEMM");
-    return e ? std::atoi(e) : 1;
-  }();
-  return v;
-}
-double GemmMinOps() {
-  static const double v = [] {
-    const char* e = std::getenv("BH_CONV_GEMM_MIN_GOP");
-    return e ? std::atof(e) * 1e9 : 1.2e9;
-  }();
-  return v;
-}
+// on every MobileNetV2 1x1 shape from M = 3136 up
+constexpr long kXsMinM = 2048;
+// conv_gemm_kernel (LDS-staged GEMM) takes the eligible layers of at least
+// this many ops
+constexpr double kGemmMinOps = 1.2e9;
 
 enum Route { kDirect, kStem, kXs, kRows, kMfma, kGemm, kGemmBig, kStemMfma };
 
@@ -706,7 +662,7 @@ Route route(const bh_conv_params& p, long M, int K, int N) {
   // RGB-stem-like layers (tiny K, byte-granular gather): direct VALU kernel
   if (!is1x1 && K <= 64 && p.in_c < 8) {
     const bool stem = p.k_h == 3 && p.k_w == 3 && p.in_c == 3 && p.dil_w == 1 && N % 8 == 0 && !p.residual;
-    if (!stem || std::getenv("BH_CONV_NO_STEM")) return kDirect;
+    if (!stem) return kDirect;
     // the window x filter contraction on MFMA (conv_stem_mfma.hip); the VALU
     // form when forced (BH_CONV_STEM_VALU) or outside the MFMA form's range
     return bh_conv_stem_mfma_ok(p) ? kStemMfma : kStem;
@@ -716,20 +672,20 @@ Route route(const bh_conv_params& p, long M, int K, int N) {
   // symmetric filters (no row sums), 16-byte K chunks
   const bool gemm_ok = is1x1 && p.stride_h == 1 && p.stride_w == 1 && p.in_xor == 0 && p.w_zp == 0 &&
                        K % 16 == 0 && aligned && ((uintptr_t)p.input & 15) == 0;
+  const bool rows_ok = is1x1 && p.stride_h == 1 && p.stride_w == 1 && N % 4 == 0 && K % 4 == 0 && aligned;
   // (the 256-row GEMM tiles go first where K and N are both wide: there the
   // layer is MFMA work, not an activation stream)
-  const bool big_first = gemm_ok && GemmMode() > 0 && K >= 128 && N >= 128 && bh_conv_gemm_big_config(M, N) != 0;
-  if (is1x1 && p.stride_h == 1 && p.stride_w == 1 && N % 4 == 0 && K % 4 == 0 && aligned && p.kernel_hint == 0 &&
-      !big_first) {
-    if (K <= 320 && M >= XsMinM()) return kXs;
-    if (RowsMinM() >= 0 && M >= RowsMinM()) return kRows;
-  }
+  const bool big_first = gemm_ok && K >= 128 && N >= 128 && bh_conv_gemm_big_config(M, N) != 0;
+  if (rows_ok && p.kernel_hint == 0 && !big_first && K <= 320 && M >= kXsMinM) return kXs;
+  // conv_rows_kernel (any K) is reached by hint only: slower than
+  // conv_mfma_kernel on every K > 320 MobileNet shape measured
+  if (p.kernel_hint == BH_CONV_ROWS && rows_ok) return kRows;
   if (p.kernel_hint == BH_CONV_MFMA) return kMfma;
   if (p.kernel_hint == BH_CONV_GEMM) return gemm_ok ? kGemm : kMfma;
   if (p.kernel_hint == BH_CONV_GEMM_BIG) return gemm_ok ? kGemmBig : kMfma;
   // the 256-row tiles once the layer fills the chip with them (B = 32 / 256 passes)
-  if (gemm_ok && GemmMode() > 0 && bh_conv_gemm_big_config(M, N) != 0) return kGemmBig;
-  if (gemm_ok && GemmMode() > 0 && (GemmMode() == 2 || 2.0 * M * N * K >= GemmMinOps())) return kGemm;
+  if (gemm_ok && bh_conv_gemm_big_config(M, N) != 0) return kGemmBig;
+  if (gemm_ok && 2.0 * M * N * K >= kGemmMinOps) return kGemm;
   return kMfma;
 }
 }  // namespace

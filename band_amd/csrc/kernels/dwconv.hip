@@ -583,19 +583,12 @@ static void launch3x3(const bh_dwconv_params& p, long pixels, hipStream_t s) {
 namespace {
 enum DwRoute { kRun1, kRun2, kRunD2, kDot16, kDot8, kDot4, kTap16, kTap8, kTap4, kGeneric, kMfma };
 
-// MFMA form from this many 16x16 output tiles (BH_DW_MFMA_MIN_TILES; the
-// round-2 default was 4096).  Off by default since round 3: the VALU run
-// form is faster on the standalone depthwise layers of the batch-24 C3 mix
-// (64 layers unfused: 397 vs 510 us; default fused tree: kernel sum 1432 vs
-// 1447 us, PoseNet -13.5 us; profiles/r03aw_dwab_*), and it keeps MFMA on
-// the dense contractions.  kernel_hint BH_DW_MFMA still forces it.
-long MfmaMinTiles() {
-  static const long v = [] {
-    const char* e = std::getenv("BH_DW_MFMA_MIN_TILES");
-    return e ? std::atol(e) : LONG_MAX;
-  }();
-  return v;
-}
+// The MFMA form is reached by kernel_hint BH_DW_MFMA only (the round-2
+// default took it from 4096 16x16 output tiles).  Off by default since round
+// 3: the VALU run form is faster on the standalone depthwise layers of the
+// batch-24 C3 mix (64 layers unfused: 397 vs 510 us; default fused tree:
+// kernel sum 1432 vs 1447 us, PoseNet -13.5 us; profiles/r03aw_dwab_*), and
+// it keeps MFMA on the dense contractions.
 
 DwRoute dw_route(const bh_dwconv_params& p) {
   const long pixels = (long)p.batch * p.out_h * p.out_w;
@@ -609,7 +602,6 @@ DwRoute dw_route(const bh_dwconv_params& p) {
     if (p.out_c % 16 == 0) return kDot16;
     return p.out_c % 8 == 0 ? kDot8 : kDot4;
   }
-  if (bh::mfma_ok(p) && (pixels + 15) / 16 * (p.out_c / 16) >= MfmaMinTiles()) return kMfma;
   // run kernel (4 channels x 4 pixels per thread) once the grid has >= ~40k
   // threads: measured 1.5-1.9x faster than the per-pixel kernels from there
   // (MobileNetV2 depthwise layers, batch 16 / 64); below it, at batch 1, the

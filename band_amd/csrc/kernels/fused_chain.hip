@@ -337,20 +337,13 @@ __device__ __forceinline__ void gemm_xs4_nt(const bh_conv_params& c, const unsig
   }
 }
 
-// BH_CHAIN_WPE (build-time A-B switch): ask the register allocator for at
-// least that many waves per SIMD on the raster chain forms
-#ifdef BH_CHAIN_WPE
-#define BH_CHAIN_OCC __attribute__((amdgpu_waves_per_eu(BH_CHAIN_WPE)))
-#else
-#define BH_CHAIN_OCC
-#endif
 // VAR: compile-time form variants, so the default instantiation carries no
 // code of the others (built as runtime branches they cost 1-3.6 us per
 // launch on every chain at batch 24, profiles/r05m_*): bit 1 = the phase-C
 // channel split over grid.y
 template <int RB, bool FAST, int KX, int NW, bool AM, int DA = 2, int VAR = 0>
-__global__ __launch_bounds__(NW * 64) BH_CHAIN_OCC void chain_kernel(bh_chain_params cp, int P, int S1, int S2, int off_pl, int off_o1,
-                                                    int off_add, ChainDivs dv) {
+__global__ __launch_bounds__(NW * 64) void chain_kernel(bh_chain_params cp, int P, int S1, int S2, int off_pl, int off_o1,
+                                                       int off_add, ChainDivs dv) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const unsigned long long t_entry = __builtin_amdgcn_s_memtime();  // before any kernarg load
   constexpr int WPB = NW / RB;  // waves per pixel block

@@ -58,7 +58,7 @@ __device__ __forceinline__ void stem_window(const uint8_t* img, const uint8_t* e
 }
 
 // The same window read from input rows staged in LDS (conv_stem_lds_kernel
-// with BH_STEM_ROWS): staged row r holds image row iy_lo + r from the
+// with staged rows): staged row r holds image row iy_lo + r from the
 // 16-byte-aligned global address below its first byte, rw words apart, so
 // pixel x of row y starts at byte (y - iy_lo) * 4 * rw + (rel_y & 15) + 3x,
 // rel_y = the row's byte offset in the tensor (img_rel + y * in_w * 3).

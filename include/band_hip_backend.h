@@ -112,8 +112,7 @@ int bhx_executor_coalescer(bhx_executor* e, int* members, int* lanes_ready);
  * (engine/engine.cc, engine/worker.cc); Band itself never needs them.
  * bhx_ring_host_alloc: page-locked memory for a request ring's slots, so a
  * GPU worker DMAs a job's I/O straight from / into its ring slot; NULL (use
- * the heap) when no GPU is visible, BAND_HIP_PINNED_RINGS=0, or the total
- * would pass BAND_HIP_PINNED_RING_MB (default 8192).
+ * the heap) when no GPU is visible or the process's total would pass 8192 MB.
  * bhx_pin_worker_thread: pins the calling engine-owned worker thread to the
  * CPUs of the NUMA node of the GPU `worker_id` runs on (affinity.h); 1 pinned,
  * 0 nothing to do (BANDX_NUMA_PIN=0, no NUMA information), -1 the worker has

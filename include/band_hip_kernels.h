@@ -206,9 +206,10 @@ int bh_conv_group_i8(const bh_conv_group* g, bh_stream_t stream);
 #define BH_CONV_STEM_VALU 4 /* RGB stems: conv_stem_kernel (VALU dot4) instead of conv_stem_mfma_kernel */
 #define BH_CONV_STEM_MFMA 5 /* RGB stems: conv_stem_mfma_kernel (the routed form wherever its shape rules allow) */
 #define BH_CONV_STEM_SCALAR 6 /* RGB stems: conv_stem_kernel with filters read through the scalar cache (round-4 form) */
+#define BH_CONV_ROWS 7 /* conv_rows_kernel: 1x1 s1 layers of any K with N % 4 == 0 and K % 4 == 0 (never routed by shape) */
 /* the tile configuration conv_gemm_big_kernel takes for an M x N layer when
- * routed automatically (1: 256x256, 2: 256x128; BH_GEMM_BIG_CFG overrides),
- * 0 when the layer is too small for it (conv_gemm_kernel then) */
+ * routed automatically (2: 256x128, 3: 128x256), 0 when the layer is too
+ * small for it (conv_gemm_kernel then) */
 int bh_conv_gemm_big_config(long M, int N);
 
 /* DEPTHWISE_CONV_2D.  weights: int8-domain [k_h][k_w][out_c] (TFLite layout

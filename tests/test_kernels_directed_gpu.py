@@ -5,9 +5,6 @@ residual ADD, pooling of extreme planes.  Bit-exact against the oracle; every
 forced or routed form is confirmed by name before it is launched.
 """
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -480,42 +477,28 @@ def test_conv_residual_every_pair(gpu_lib, hint, sweeps, k, ic, name):
     run_residual(gpu_lib, c, name)
 
 
-# --- 7. conv_rows_kernel: opt-in by environment, read once per process ------------------
+# --- 7. conv_rows_kernel: reached by hint only (BH_CONV_ROWS = 7) ------------------------
 
-def rows_child():
-    """runs in a fresh process with BH_CONV_ROWS_MIN_M=0: conv_rows_kernel by
-    name on three of test_conv1x1_rows_batched's layers at reduced batch and a
-    K > 320 one, the fast and two-step directed layers of both dtypes, the
-    residual pairs and the saturating deep-K layers"""
-    from band_amd import _abi, device
-    lib = _abi.load()
-    assert device.device_count() > 0
-    name = "conv_rows_kernel"
+def test_conv_rows_kernel(gpu_lib):
+    """conv_rows_kernel by name on three of test_conv1x1_rows_batched's layers
+    at reduced batch and a K > 320 one, the fast and two-step directed layers
+    of both dtypes, the residual pairs and the saturating deep-K layers"""
+    lib, name, hint = gpu_lib, "conv_rows_kernel", 7
     for b, spatial, ic, oc, dtype in [(2, 28, 32, 192, I8), (8, 14, 96, 20, U8), (40, 7, 64, 520, I8),
                                       (8, 7, 384, 520, I8), (8, 7, 328, 24, U8)]:
         rng = np.random.default_rng(4000 + b + spatial + ic + oc)
-        launch(lib, ConvCase(rng, b, spatial, spatial, ic, oc, 1, 1, dtype=dtype, act=3), name, "rows %d" % ic)
+        launch(lib, ConvCase(rng, b, spatial, spatial, ic, oc, 1, 1, dtype=dtype, act=3, kernel_hint=hint), name,
+               "rows %d" % ic)
     for family, dtype in FAMILIES:
         for i, epi in enumerate(dh.epilogues(family, dtype, 16)):
             w_zp = 0 if dtype == I8 else (0, 255)[i % 2]
-            launch(lib, dh.conv_layer(epi, w_zp=w_zp, seed=i), name, epi.name)
-    run_residual(lib, dh.conv_layer(passthrough_epi()), name)
+            launch(lib, dh.conv_layer(epi, w_zp=w_zp, kernel_hint=hint, seed=i), name, epi.name)
+    run_residual(lib, dh.conv_layer(passthrough_epi(), kernel_hint=hint), name)
     for dtype, ends in ((I8, (1, 0)), (U8, (0, 1)), (U8, (1, 0))):  # saturating, K = 1280 / 1296
         for ic in (1280, 1296):
-            c = saturating_case(dtype, 2, 8, ic, 64, 1, "board", *ends)
+            c = saturating_case(dtype, 2, 8, ic, 64, 1, "board", *ends, kernel_hint=hint)
             check_spread(c.oracle(), c, "rows saturating")
             launch(lib, c, name, "saturating K %d" % ic)
-    print("ROWS-BITEXACT")
-
-
-def test_conv_rows_kernel_child_process(gpu_lib):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ)
-    env["BH_CONV_ROWS_MIN_M"] = "0"
-    code = "import sys; sys.path.insert(0, %r); from tests import test_kernels_directed_gpu as t; t.rows_child()" % root
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, "conv_rows child:\n%s" % r.stderr[-4000:]
-    assert "ROWS-BITEXACT" in r.stdout
 
 
 # --- 8. pooling of extreme planes under a narrow window ---------------------------------

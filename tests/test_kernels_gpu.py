@@ -35,8 +35,8 @@ def test_conv1x1_mnv2_shapes_int8(gpu_lib, spatial, ic, oc):
 # batched 1x1 layers (job batching): K <= 320 and M = b*h*w >= 2048 output
 # pixels take conv_xs_kernel (x-stationary); N / K tails, uint8 per-tensor
 # filters (row-sum correction), whole-N and chunked-N grids.  (conv_rows_kernel
-# is opt-in by BH_CONV_ROWS_MIN_M, read once per process: it runs in
-# test_kernels_directed_gpu.py's child process.)
+# is reached by kernel_hint BH_CONV_ROWS only: test_kernels_directed_gpu.py's
+# test_conv_rows_kernel runs it.)
 @pytest.mark.parametrize("b,spatial,ic,oc,dtype", [
     (4, 112, 16, 96, np.int8), (4, 112, 32, 16, np.uint8), (12, 56, 24, 144, np.int8),
     (12, 56, 144, 24, np.uint8), (44, 28, 32, 192, np.int8), (44, 28, 192, 32, np.int8),
