@@ -130,6 +130,18 @@ class ResizeBilinearParams(ctypes.Structure):
         (n, c_void_p) for n in ("y_tab", "x_tab", "input", "output")]
 
 
+ARG_I8, ARG_U8, ARG_F32 = 0, 1, 2
+
+
+class ArgMinMaxParams(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_long) for n in ("outer", "axis_len", "inner")] + [
+        (n, c_int) for n in ("in_type", "is_min", "out_bytes")] + [("input", c_void_p), ("output", c_void_p)]
+
+
+class ResizeArgMinMaxParams(ctypes.Structure):
+    _fields_ = [("rz", ResizeBilinearParams), ("is_min", c_int), ("out_bytes", c_int)]
+
+
 class ResizeBilinearU8Params(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("batch", "in_h", "in_w", "channels", "out_h", "out_w")] + [
         (n, c_void_p) for n in ("y_idx", "x_idx", "y_frac", "x_frac", "input", "output")]
@@ -234,6 +246,10 @@ KERNEL_SYMBOLS = {
     "bh_resize_nearest": (c_int, [ctypes.POINTER(ResizeNearestParams), c_void_p]),
     "bh_resize_bilinear_i8": (c_int, [ctypes.POINTER(ResizeBilinearParams), c_void_p]),
     "bh_resize_bilinear_u8": (c_int, [ctypes.POINTER(ResizeBilinearU8Params), c_void_p]),
+    "bh_argminmax": (c_int, [ctypes.POINTER(ArgMinMaxParams), c_void_p]),
+    "bh_argminmax_kernel": (ctypes.c_char_p, [ctypes.POINTER(ArgMinMaxParams)]),
+    "bh_resize_bilinear_argminmax_i8": (c_int, [ctypes.POINTER(ResizeArgMinMaxParams), c_void_p]),
+    "bh_resize_bilinear_argminmax_i8_ok": (c_int, [ctypes.POINTER(ResizeArgMinMaxParams)]),
     "bh_softmax_i8": (c_int, [ctypes.POINTER(SoftmaxParams), c_void_p]),
     "bh_zero_insert": (c_int, [ctypes.POINTER(ZeroInsertParams), c_void_p]),
     "bh_conv2d_f32": (c_int, [ctypes.POINTER(ConvF32Params), c_void_p]),

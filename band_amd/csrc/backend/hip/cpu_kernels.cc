@@ -790,5 +790,35 @@ void CpuMean(const CpuMeanParams& p, CpuPool& pool) {
   });
 }
 
+namespace {
+template <typename T>
+void ArgMinMaxRows(const bh_argminmax_params& p, long lo, long hi) {
+  const T* x = static_cast<const T*>(p.input);
+  for (long o = lo; o < hi; ++o) {
+    const long a = o / p.inner, c = o % p.inner;
+    const long base = a * p.axis_len * p.inner + c;
+    T best = x[base];
+    int32_t idx = 0;
+    for (long i = 1; i < p.axis_len; ++i) {
+      const T v = x[base + i * p.inner];
+      if (p.is_min ? v < best : v > best) {
+        best = v;
+        idx = static_cast<int32_t>(i);
+      }
+    }
+    if (p.out_bytes == 8) static_cast<int64_t*>(p.output)[o] = idx;
+    else static_cast<int32_t*>(p.output)[o] = idx;
+  }
+}
+}  // namespace
+
+void CpuArgMinMax(const bh_argminmax_params& p, CpuPool& pool) {
+  pool.ParallelFor(p.outer * p.inner, [&](long lo, long hi) {
+    if (p.in_type == BH_ARG_F32) ArgMinMaxRows<float>(p, lo, hi);
+    else if (p.in_type == BH_ARG_I8) ArgMinMaxRows<int8_t>(p, lo, hi);
+    else ArgMinMaxRows<uint8_t>(p, lo, hi);
+  });
+}
+
 }  // namespace hip
 }  // namespace band

@@ -102,5 +102,10 @@ struct CpuMeanParams {
 };
 void CpuMean(const CpuMeanParams& p, CpuPool& pool);
 
+// ARG_MAX / ARG_MIN: reference_ops::ArgMinMax's loop over [outer][axis_len]
+// [inner] - start at element 0, replace only on > (< for min): the first
+// extreme wins and a float NaN is selected only as element 0
+void CpuArgMinMax(const bh_argminmax_params& p, CpuPool& pool);
+
 }  // namespace hip
 }  // namespace band

@@ -272,6 +272,57 @@ inline bool MeanArgs(const TflModel& m, const TflOperator& op, long* outer, long
   return *reduce > 0 && out.num_elements() == static_cast<size_t>(*outer * *inner);
 }
 
+// ARG_MAX / ARG_MIN (arg_min_max.cc): int8 / uint8 / float32 input of rank
+// 1-4 viewed as [outer][axis_len][inner]; the axis is a constant int32 /
+// int64 scalar or one-element tensor (negatives resolved); the output is
+// int32 or int64 as ArgMaxOptions / ArgMinOptions.output_type says, with
+// outer * inner elements.  *why (optional) names what failed.
+inline bool ArgMinMaxArgs(const TflModel& m, const TflOperator& op, long* outer, long* axis_len, long* inner,
+                          int* out_bytes, int* axis_out = nullptr, const char** why = nullptr) {
+  auto no = [&](const char* w) {
+    if (why) *why = w;
+    return false;
+  };
+  if ((op.builtin != kTflArgMax && op.builtin != kTflArgMin) || op.inputs.size() < 2 || op.inputs[0] < 0 ||
+      op.inputs[1] < 0 || op.outputs.empty() || op.outputs[0] < 0)
+    return no("ARG_MAX / ARG_MIN needs an input, an axis and an output");
+  const TflTensor& in = m.tensors[op.inputs[0]];
+  const TflTensor& ax = m.tensors[op.inputs[1]];
+  const TflTensor& out = m.tensors[op.outputs[0]];
+  if (in.type != DataType::kInt8 && in.type != DataType::kUInt8 && in.type != DataType::kFloat32)
+    return no("ARG_MAX / ARG_MIN input must be int8, uint8 or float32");
+  const int rank = static_cast<int>(in.shape.size());
+  if (rank < 1 || rank > 4) return no("ARG_MAX / ARG_MIN input rank must be 1-4");
+  if (!ax.is_const()) return no("ARG_MAX / ARG_MIN axis must be a constant");
+  if ((ax.type != DataType::kInt32 && ax.type != DataType::kInt64) || ax.num_elements() != 1 ||
+      ax.data_size < (ax.type == DataType::kInt64 ? 8u : 4u))
+    return no("ARG_MAX / ARG_MIN axis must be one int32 / int64 value");
+  int64_t axis = 0;
+  if (ax.type == DataType::kInt64) {
+    std::memcpy(&axis, ax.data, 8);
+  } else {
+    int32_t v;
+    std::memcpy(&v, ax.data, 4);
+    axis = v;
+  }
+  if (axis < 0) axis += rank;
+  if (axis < 0 || axis >= rank) return no("ARG_MAX / ARG_MIN axis out of range");
+  if (out.type != DataType::kInt32 && out.type != DataType::kInt64)
+    return no("ARG_MAX / ARG_MIN output must be int32 or int64");
+  const int want = op.options.valid() ? op.options.Int8(0, 0) : 0;  // TensorType (schema default 0 = float32)
+  if (want != (out.type == DataType::kInt64 ? 4 : 2))
+    return no("ARG_MAX / ARG_MIN output type differs from output_type");
+  *outer = *inner = 1;
+  for (int dd = 0; dd < axis; ++dd) *outer *= in.shape[dd];
+  for (int dd = static_cast<int>(axis) + 1; dd < rank; ++dd) *inner *= in.shape[dd];
+  *axis_len = in.shape[axis];
+  *out_bytes = out.type == DataType::kInt64 ? 8 : 4;
+  if (axis_out) *axis_out = static_cast<int>(axis);
+  if (*axis_len <= 0 || *outer <= 0 || *inner <= 0 || out.num_elements() != static_cast<size_t>(*outer * *inner))
+    return no("ARG_MAX / ARG_MIN output must hold outer * inner elements");
+  return true;
+}
+
 // TFLite_Detection_PostProcess in the form the host kernel and the device
 // kernels (kernels/detection.hip) implement.  batch: the images of a
 // job-batch variant (the leading dimension of the op's tensors; the anchors

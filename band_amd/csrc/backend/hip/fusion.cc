@@ -747,6 +747,42 @@ void HipModelExecutor::FuseGlue(const HipModel& model, PreparedSubgraph* sg) {
     sg->fused_ops.insert(C.op_index);
     dead[i] = true;
   }
+  // (3) RESIZE_BILINEAR (int8) -> ARG_MAX / ARG_MIN over the channel axis:
+  // one resize_bilinear_argminmax_kernel launch, the resized tensor never
+  // stored (kGPU; the kCPU worker runs the two host kernels).  The launcher
+  // refuses geometries whose blended rows do not fit LDS: those keep both.
+  for (size_t i = 0; allow_argmax_ && device_flag_ == DeviceFlag::kGPU && i < sg->launches.size(); ++i) {
+    Launch& A = sg->launches[i];
+    if (A.kind != Launch::kArgMinMax || A.argmm.in_type != BH_ARG_I8 || A.argmm.inner != 1) continue;
+    int j = -1;
+    for (size_t k = i; k-- > 0 && j < 0;)
+      if (!dead[k] && sg->launches[k].kind == Launch::kResizeBilinear && sg->launches[k].rbil.output == A.argmm.input)
+        j = static_cast<int>(k);
+    if (j < 0) continue;
+    Launch& R = sg->launches[j];
+    const int t = R.out_tensor;
+    if (A.argmm.axis_len != R.rbil.channels ||
+        A.argmm.outer != static_cast<long>(R.rbil.batch) * R.rbil.out_h * R.rbil.out_w)
+      continue;
+    if (t < 0 || consumers_[t].size() != 1 || consumers_[t][0] != A.op_index || in_outputs(t) ||
+        sg->no_fuse.count(t) || sg->extra_d2h.count(t))
+      continue;
+    bh_resize_argminmax_params q{};
+    q.rz = R.rbil;
+    q.rz.output = A.argmm.output;
+    q.is_min = A.argmm.is_min;
+    q.out_bytes = A.argmm.out_bytes;
+    if (bh_resize_bilinear_argminmax_i8_ok(&q) != 0) continue;
+    A.kind = Launch::kResizeArgMinMax;
+    A.rzarg = q;
+    A.kernel = "resize_bilinear_argminmax_kernel";
+    // reads the small map, writes the indices; the resized tensor is gone
+    A.alg_bytes = static_cast<double>(R.rbil.batch) * R.rbil.in_h * R.rbil.in_w * R.rbil.channels +
+                  static_cast<double>(A.argmm.outer) * A.argmm.out_bytes;
+    sg->fused_tensors.insert(t);
+    sg->fused_ops.insert(R.op_index);
+    dead[j] = true;
+  }
   std::vector<Launch> out;
   for (size_t i = 0; i < sg->launches.size(); ++i)
     if (!dead[i]) out.push_back(sg->launches[i]);

@@ -994,6 +994,18 @@ absl::Status HipModelExecutor::Lower(const HipModel& model, int oi, PreparedSubg
     L.kind = Launch::kMean;
     L.kernel = device_flag_ == DeviceFlag::kGPU ? "mean_kernel" : "mean_host";
     L.alg_bytes = static_cast<double>(meta_[op.inputs[0]]->bytes + meta_[op.outputs[0]]->bytes);
+  } else if (op.builtin == kTflArgMax || op.builtin == kTflArgMin) {
+    bh_argminmax_params& p = L.argmm;
+    p = bh_argminmax_params{};
+    if (!ArgMinMaxArgs(d, op, &p.outer, &p.axis_len, &p.inner, &p.out_bytes))
+      return absl::InternalError("unsupported ARG_MAX / ARG_MIN");
+    p.in_type = in.type == DataType::kFloat32 ? BH_ARG_F32 : (i8 ? BH_ARG_I8 : BH_ARG_U8);
+    p.is_min = op.builtin == kTflArgMin ? 1 : 0;
+    p.input = in_ptr;
+    p.output = out_ptr;
+    L.kind = Launch::kArgMinMax;
+    L.kernel = cpu ? "argminmax_host" : bh_argminmax_kernel(&p);
+    L.alg_bytes = static_cast<double>(meta_[op.inputs[0]]->bytes + meta_[op.outputs[0]]->bytes);
   } else if (op.builtin == kTflTransposeConv) {
     RETURN_STATUS_IF(LowerTransposeConv(model, oi, out_ptr, ckey, sg, &L));
   } else if (op.builtin != kTflReshape && op.builtin != kTflSqueeze) {

@@ -64,6 +64,12 @@ absl::Status HipModel::CloneWithJobBatch(int batch, std::unique_ptr<HipModel>* o
       if (axis < 0) axis += rank;
       if (axis == 0) return absl::InternalError("job batching: CONCATENATION on the batch axis");
     }
+    if (op.builtin == kTflArgMax || op.builtin == kTflArgMin) {
+      long outer, len, inner;
+      int out_bytes, axis = -1;
+      if (ex::ArgMinMaxArgs(desc_, op, &outer, &len, &inner, &out_bytes, &axis) && axis == 0)
+        return absl::InternalError(std::string("job batching: ") + TflBuiltinName(op.builtin) + " on the batch axis");
+    }
   }
   for (const TflTensor& t : desc_.tensors)
     if (!t.is_const() && (t.shape.empty() || t.shape[0] != 1))

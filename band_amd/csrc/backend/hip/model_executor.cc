@@ -175,6 +175,14 @@ bool HipModelExecutor::GpuSupports(const TflModel& m, const TflOperator& op, std
       if (!MeanArgs(m, op, &o, &r, &i)) return no("MEAN over one contiguous run of axes, 4-D keep_dims");
       return true;
     }
+    case kTflArgMax:
+    case kTflArgMin: {
+      long o, l, i;
+      int ob;
+      const char* w = "";
+      if (!ArgMinMaxArgs(m, op, &o, &l, &i, &ob, nullptr, &w)) return no(w);
+      return true;
+    }
     case kTflSoftmax:
       if (!IsQ8(in.type) || out.type != in.type || !HasQ(in) || !HasQ(out) || in.shape.empty())
         return no("only 8-bit quantized in and out");
@@ -288,6 +296,7 @@ absl::Status HipModelExecutor::EnsureMeta(const HipModel& model) {
   if (std::strcmp(f, "noadd") == 0) allow_add_ = false;
   if (std::strcmp(f, "nochain") == 0) allow_chain_ = false;
   if (std::strcmp(f, "nogroup") == 0) allow_group_ = false;
+  if (std::strcmp(f, "noargmax") == 0) allow_argmax_ = false;
   if (std::strcmp(f, "forcechain") == 0) forced_chain_ = ForcedChain::kPlain;  // parity tests: every feasible chain
   if (std::strcmp(f, "forcetile") == 0) forced_chain_ = ForcedChain::kTile;  // ... in the tile form
   if (std::strcmp(f, "notile") == 0) no_tile_chain_ = true;  // A-B: the raster chain forms only
@@ -606,6 +615,8 @@ absl::Status HipModelExecutor::EnqueueLaunch(const Launch& l) {
       break;
     case Launch::kDetectionPost: return absl::InternalError(std::string(l.kernel) + " is a CPU-worker op");
     case Launch::kDetectionGpu: rc = bh_detection_postprocess(&l.detg, stream_); break;
+    case Launch::kArgMinMax: rc = bh_argminmax(&l.argmm, stream_); break;
+    case Launch::kResizeArgMinMax: rc = bh_resize_bilinear_argminmax_i8(&l.rzarg, stream_); break;
     case Launch::kMean: {
       bh_mean_params q{};
       q.outer = l.mean.outer;
@@ -805,6 +816,7 @@ absl::Status HipModelExecutor::ExecuteOnHost(PreparedSubgraph* sg) {
         break;
       case Launch::kDetectionPost: CpuDetectionPostprocess(l.det, pool); break;
       case Launch::kMean: CpuMean(l.mean, pool); break;
+      case Launch::kArgMinMax: CpuArgMinMax(l.argmm, pool); break;
       default: return absl::InternalError(std::string("no host implementation of ") + l.kernel);
     }
   }

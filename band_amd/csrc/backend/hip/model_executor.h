@@ -46,7 +46,9 @@ struct Launch {
     kDetectionPost,  // CPU-only TFLite_Detection_PostProcess
     kMean,           // CPU-only MEAN
     kConvGroup,      // independent small convs in one dispatch (GroupConvs)
-    kDetectionGpu    // TFLite_Detection_PostProcess on the device (BAND_HIP_GPU_DETECTION=1)
+    kDetectionGpu,   // TFLite_Detection_PostProcess on the device (BAND_HIP_GPU_DETECTION=1)
+    kArgMinMax,      // ARG_MAX / ARG_MIN
+    kResizeArgMinMax // RESIZE_BILINEAR int8 -> ARG_MAX / ARG_MIN over channels, one launch (FuseGlue; kGPU)
   } kind;
   int op_index = -1;
   int out_tensor = -1;  // tensor this launch materialises (after epilogue fusions)
@@ -77,6 +79,8 @@ struct Launch {
   CpuDetectionParams det{};
   bh_detection_params detg{};  // kDetectionGpu
   CpuMeanParams mean{};
+  bh_argminmax_params argmm{};
+  bh_resize_argminmax_params rzarg{};
   const void* table = nullptr;  // kLutU8 / kLutF32: 256-entry device table
   long count = 0;               // kLut* / kQuantF32: elements
   float q_scale = 0.f;          // kQuantF32
@@ -213,7 +217,8 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   bool PrivateTensor(const TflModel& d, const PreparedSubgraph& sg, int t, int only_consumer) const;
   void FuseChains(const HipModel& model, PreparedSubgraph* sg);
   // 8-bit unary table ops into the producing conv / FC / depthwise epilogue;
-  // CONCATENATION with outer size 1 elided (producers write their slices)
+  // CONCATENATION with outer size 1 elided (producers write their slices);
+  // int8 RESIZE_BILINEAR -> ARG_MAX / ARG_MIN over channels as one launch (kGPU)
   void FuseGlue(const HipModel& model, PreparedSubgraph* sg);
   // independent small convs (detector / pose heads) deferred past later
   // launches that do not touch them and issued as one conv_group launch
@@ -281,6 +286,7 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   bool allow_add_ = true;
   bool allow_chain_ = true;   // BAND_HIP_FUSION=nochain
   bool allow_group_ = true;   // BAND_HIP_FUSION=nogroup: one launch per conv
+  bool allow_argmax_ = true;  // BAND_HIP_FUSION=noargmax: RESIZE_BILINEAR and ARG_MAX / ARG_MIN as two launches
   // BAND_HIP_FUSION=forcechain / forcetile / forcedeep / forcestage (parity
   // tests): every feasible chain fused, in the named form where that fits
   ForcedChain forced_chain_ = ForcedChain::kNone;

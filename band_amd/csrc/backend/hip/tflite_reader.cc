@@ -45,6 +45,8 @@ const char* TflBuiltinName(int c) {
     case kTflResizeNearestNeighbor: return "RESIZE_NEAREST_NEIGHBOR";
     case kTflQuantize: return "QUANTIZE";
     case kTflHardSwish: return "HARD_SWISH";
+    case kTflArgMax: return "ARG_MAX";
+    case kTflArgMin: return "ARG_MIN";
     default: return "UNKNOWN";
   }
 }

@@ -26,6 +26,8 @@ enum TflBuiltin : int {
   kTflResizeBilinear = 23, kTflSoftmax = 25, kTflCustom = 32, kTflPad = 34, kTflMean = 40,
   kTflSub = 41, kTflRsqrt = 76, kTflSquaredDifference = 99, kTflMirrorPad = 100, kTflSqueeze = 43, kTflPadV2 = 60, kTflTransposeConv = 67, kTflResizeNearestNeighbor = 97,
   kTflQuantize = 114, kTflHardSwish = 117,
+  // ArgMaxOptions / ArgMinOptions: slot 0 output_type (TensorType: 2 int32, 4 int64)
+  kTflArgMax = 56, kTflArgMin = 79,
 };
 
 const char* TflBuiltinName(int code);

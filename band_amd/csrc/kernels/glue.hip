@@ -356,6 +356,78 @@ __global__ __launch_bounds__(256) void resize_bilinear_cols_kernel(bh_resize_bil
   }
 }
 
+// RESIZE_BILINEAR (int8) -> ARG_MAX / ARG_MIN over channels in one launch
+// (a segmentation head's last two ops): the resized logits never reach HBM.
+// The cols kernel's scheme - V[xi][c] = r0[xi][c] (1 - fy) + r1[xi][c] fy
+// once into LDS for `nr` output rows, the column tables beside it - but ONE
+// THREAD PER OUTPUT PIXEL, walking c = 0 .. C-1 over
+// rz_round20(V[x0][c] (1 - fx) + V[x1][c] fx), the cols kernel's expression,
+// and keeping the first extreme (reference_ops::ArgMinMax: replace only on a
+// strict comparison).
+// LDS layout: a pixel's channels are `cp` = C | 1 words apart.  At channel c
+// the lanes of a wave read V[x0(x) * cp + c] for consecutive x: lanes that
+// share x0 (an upsample: 16 of them at DeepLab's x16) read one address
+// (broadcast), and distinct x0 are an odd number of words apart, so the 32
+// lanes of a ds_read_b32 group fall on distinct banks at scale >= 1 (C = 16
+// or 64 unpadded would put every pixel on 2 banks or 1); a 2x downscale is
+// 2-way.
+__global__ __launch_bounds__(256) void resize_bilinear_argminmax_kernel(bh_resize_bilinear_params p, int is_min,
+                                                                        int out_bytes, int nr, FastDiv groups,
+                                                                        FastDiv chans, FastDiv ow_div) {
+  extern __shared__ __attribute__((aligned(16))) int32_t rz_lds[];
+  const int n = groups.div(blockIdx.x);
+  const int y_first = (blockIdx.x - n * (int)groups.d) * nr;
+  const int rows = min(nr, p.out_h - y_first);
+  const int C = p.channels;
+  const int cp = C | 1;
+  const int in_row = p.in_w * C;
+  const int v_row = p.in_w * cp;
+  int32_t* X0 = rz_lds;          // [out_w]: x0 * cp
+  int32_t* X1 = X0 + p.out_w;    // [out_w]: x1 * cp
+  int32_t* FX = X1 + p.out_w;    // [out_w]: fx
+  int32_t* V = FX + p.out_w;     // [rows][in_w][cp]
+  constexpr int32_t one = 1 << 10;
+  for (int i = threadIdx.x; i < rows * in_row; i += 256) {
+    const int r = i / in_row;  // rows <= 8: a short division
+    const int k = i - r * in_row;
+    const int xi = (int)chans.div((uint32_t)k);
+    const int y = y_first + r;
+    const int y0 = p.y_tab[3 * y], y1 = p.y_tab[3 * y + 1];
+    const int32_t fy = p.y_tab[3 * y + 2] - one * y0;
+    const int8_t* in = (const int8_t*)p.input + (long)n * p.in_h * in_row;
+    V[r * v_row + xi * cp + (k - xi * C)] =
+        __mul24((int32_t)in[y0 * in_row + k], one - fy) + __mul24((int32_t)in[y1 * in_row + k], fy);
+  }
+  for (int x = threadIdx.x; x < p.out_w; x += 256) {
+    const int x0 = p.x_tab[3 * x];
+    X0[x] = x0 * cp;
+    X1[x] = p.x_tab[3 * x + 1] * cp;
+    FX[x] = p.x_tab[3 * x + 2] - one * x0;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < rows * p.out_w; i += 256) {
+    const int r = (int)ow_div.div((uint32_t)i);
+    const int x = i - r * p.out_w;
+    const int32_t* V0 = V + r * v_row + X0[x];
+    const int32_t* V1 = V + r * v_row + X1[x];
+    const int32_t fx = FX[x];
+    int32_t best = 0, idx = 0;
+    for (int c = 0; c < C; ++c) {
+      // the cols kernel's byte: |V| <= 2^17, fx <= 2^10, 24-bit multiplies exact
+      const int32_t s = __mul24(V0[c], one - fx) + __mul24(V1[c], fx);
+      const int32_t v = (int32_t)(int8_t)rz_round20(s);
+      const int32_t k = is_min ? -v : v;
+      if (c == 0 || k > best) {
+        best = k;
+        idx = c;
+      }
+    }
+    const long o = ((long)n * p.out_h + y_first + r) * p.out_w + x;
+    if (out_bytes == 8) ((v2i*)p.output)[o] = (v2i){idx, 0};
+    else ((int32_t*)p.output)[o] = idx;
+  }
+}
+
 // ---- softmax ----------------------------------------------------------------
 // One thread per row; the float operations are issued exactly as the
 // reference's loop runs them (no contraction: explicit _rn intrinsics).
@@ -597,6 +669,54 @@ extern "C" int bh_resize_bilinear_i8(const bh_resize_bilinear_params* pp, bh_str
   dv.oh = bh::FastDiv(p.out_h);
   BH_LAUNCH(bh::resize_bilinear_kernel, dim3(bh::blocks(total)), dim3(256), 0, (hipStream_t)s, p, dv, total);
   return bh_check_launch("resize_bilinear_kernel");
+}
+
+// LDS words of the fused form for one output row per workgroup (the cols
+// kernel's rule with the padded pixel stride), or 0 with the reason set
+static size_t rz_argminmax_lds(const bh_resize_argminmax_params* pp, size_t* row_lds) {
+  if (!pp || !pp->rz.input || !pp->rz.output || !pp->rz.y_tab || !pp->rz.x_tab || pp->rz.batch <= 0 ||
+      pp->rz.channels <= 0 || pp->rz.in_h <= 0 || pp->rz.in_w <= 0 || pp->rz.out_h <= 0 || pp->rz.out_w <= 0 ||
+      (pp->out_bytes != 4 && pp->out_bytes != 8) || ((uintptr_t)pp->rz.output % 8) != 0) {
+    bh_set_last_error("bh_resize_bilinear_argminmax_i8: invalid parameters");
+    return 0;
+  }
+  const bh_resize_bilinear_params& p = pp->rz;
+  if ((long)p.batch * p.out_h * p.out_w * p.channels >= INT32_MAX ||
+      (long)p.batch * p.in_h * p.in_w * p.channels >= INT32_MAX) {
+    bh_set_last_error("bh_resize_bilinear_argminmax_i8: tensor too large for 32-bit indexing");
+    return 0;
+  }
+  *row_lds = (size_t)p.in_w * (p.channels | 1) * sizeof(int32_t);
+  const size_t lds = *row_lds + 3 * (size_t)p.out_w * sizeof(int32_t);
+  if (p.out_w > bh::kRzCols || lds > 64 * 1024) {
+    bh_set_last_error("bh_resize_bilinear_argminmax_i8: blended input row and column tables exceed 64 KB of LDS "
+                      "(or more than 1024 output columns); run the two launches");
+    return 0;
+  }
+  return lds;
+}
+
+extern "C" int bh_resize_bilinear_argminmax_i8_ok(const bh_resize_argminmax_params* pp) {
+  size_t row_lds = 0;
+  return rz_argminmax_lds(pp, &row_lds) ? 0 : BH_EINVAL;
+}
+
+extern "C" int bh_resize_bilinear_argminmax_i8(const bh_resize_argminmax_params* pp, bh_stream_t s) {
+  size_t row_lds = 0;
+  const size_t lds = rz_argminmax_lds(pp, &row_lds);
+  if (!lds) return BH_EINVAL;
+  const bh_resize_bilinear_params& p = pp->rz;
+  // output rows per workgroup by the cols kernel's rule: up to 8 while >= 1024
+  // workgroups remain and the blended rows fit 48 KB
+  int nr = 1;
+  while (nr < 8 && (long)p.batch * ((p.out_h + 2 * nr - 1) / (2 * nr)) >= 1024 &&
+         lds + (2 * nr - 1) * row_lds <= 48 * 1024)
+    nr *= 2;
+  const int groups = (p.out_h + nr - 1) / nr;
+  BH_LAUNCH(bh::resize_bilinear_argminmax_kernel, dim3(p.batch * groups), dim3(256), lds + (size_t)(nr - 1) * row_lds,
+            (hipStream_t)s, p, pp->is_min, pp->out_bytes, nr, bh::FastDiv(groups), bh::FastDiv(p.channels),
+            bh::FastDiv(p.out_w));
+  return bh_check_launch("resize_bilinear_argminmax_kernel");
 }
 
 extern "C" int bh_softmax_i8(const bh_softmax_params* pp, bh_stream_t s) {

@@ -17,20 +17,21 @@ import numpy as np
 
 # schema enums
 T_FLOAT32, T_FLOAT16, T_INT32, T_UINT8, T_INT8 = 0, 1, 2, 3, 9
+T_INT64 = 4
 NP_TO_SCHEMA = {np.dtype(np.float32): T_FLOAT32, np.dtype(np.float16): T_FLOAT16, np.dtype(np.int32): T_INT32,
-                np.dtype(np.uint8): T_UINT8, np.dtype(np.int8): T_INT8}
+                np.dtype(np.uint8): T_UINT8, np.dtype(np.int8): T_INT8, np.dtype(np.int64): T_INT64}
 ACT = {"NONE": 0, "RELU": 1, "RELU_N1_TO_1": 2, "RELU6": 3}
 OPC = dict(ADD=0, AVERAGE_POOL_2D=1, CONCATENATION=2, CONV_2D=3, DEPTHWISE_CONV_2D=4,
            FULLY_CONNECTED=9, LOGISTIC=14, MAX_POOL_2D=17, MUL=18, RESHAPE=22,
            RESIZE_BILINEAR=23, SOFTMAX=25, CUSTOM=32, PAD=34, SUB=41, QUANTIZE=114,
            DEQUANTIZE=6, RELU=19, RELU_N1_TO_1=20, RELU6=21, PADV2=60, RESIZE_NEAREST_NEIGHBOR=97,
-           TRANSPOSE_CONV=67)
+           TRANSPOSE_CONV=67, ARG_MAX=56, ARG_MIN=79)
 # BuiltinOptions union indices
 OPT = dict(Conv2DOptions=1, DepthwiseConv2DOptions=2, Pool2DOptions=5, FullyConnectedOptions=8,
            SoftmaxOptions=9, ConcatenationOptions=10, AddOptions=11, ReshapeOptions=17,
            ResizeBilinearOptions=15, MulOptions=21, PadOptions=22, SubOptions=28,
            DequantizeOptions=38, PadV2Options=43, TransposeConvOptions=49, ResizeNearestNeighborOptions=74,
-           QuantizeOptions=89)
+           QuantizeOptions=89, ArgMaxOptions=40, ArgMinOptions=57)
 
 
 # ---------------------------------------------------------------------------
@@ -588,6 +589,19 @@ class QGraph:
             self.fshape[t] = shp
         return outs
 
+    def arg_max(self, x, axis=-1, output=np.int32, minimum=False, axis_dtype=np.int32):
+        """ARG_MAX (ARG_MIN with minimum) of an 8-bit or float32 tensor over
+        `axis` (a constant scalar of axis_dtype): int32 / int64 indices, the
+        axis removed"""
+        shp = list(self.meta[x][0] if x in self.meta else self.fshape[x])
+        at = self.mb.tensor(self._name("axis"), [], axis_dtype, data=np.array(axis, axis_dtype))
+        del shp[axis]
+        y = self.mb.tensor(self._name("arg_min" if minimum else "arg_max"), shp, output)
+        opt = Table().set(0, "b", NP_TO_SCHEMA[np.dtype(output)])
+        self.mb.op("ARG_MIN" if minimum else "ARG_MAX", [x, at], [y],
+                   OPT["ArgMinOptions" if minimum else "ArgMaxOptions"], opt)
+        return y
+
     def quantize_float(self, xf, scale, zp=None):
         """QUANTIZE float32 -> 8-bit"""
         y = self.act_tensor(self.fshape[xf], scale, self._act_zp() if zp is None else zp)
@@ -989,11 +1003,15 @@ def efficientdet_lite2(dtype=np.int8, seed=4, size=448, batch=1, classes=90, fpn
     return g.build()
 
 
-def deeplab_v3_mobilenet_v2(dtype=np.int8, seed=2, size=224, batch=1, classes=21):
+def deeplab_v3_mobilenet_v2(dtype=np.int8, seed=2, size=224, batch=1, classes=21, argmax=None):
     """DeepLabV3 with a MobileNetV2 trunk at output stride 16 (dilated last
     stages) and the mobile ASPP: image pooling (global AVERAGE_POOL_2D, 1x1
     conv, RESIZE_BILINEAR back) + a 1x1 branch, CONCATENATION, 1x1
-    projection, 1x1 logits, RESIZE_BILINEAR x16 to the input size."""
+    projection, 1x1 logits, RESIZE_BILINEAR x16 to the input size.
+    argmax=np.int32 / np.int64: the model ends in ARG_MAX over the classes
+    and its only output is the [batch, size, size] segmentation map."""
+    if argmax is not None and np.dtype(argmax) not in (np.dtype(np.int32), np.dtype(np.int64)):
+        raise ValueError("argmax must be None, np.int32 or np.int64")
     g = QGraph(dtype, seed, "deeplab_v3_mnv2_%s" % np.dtype(dtype).name)
     x = g.input([batch, size, size, 3])
     feat, _ = _mnv2_trunk(g, x, out_stride=16)
@@ -1003,7 +1021,8 @@ def deeplab_v3_mobilenet_v2(dtype=np.int8, seed=2, size=224, batch=1, classes=21
     aspp0 = g.conv(feat, 256, k=1, act="RELU")
     y = g.conv(g.concat([pool, aspp0], axis=3), 256, k=1, act="RELU")
     y = g.conv(y, classes, k=1, act="NONE")
-    g.output(g.resize(y, (size, size), bilinear=True, align_corners=True))
+    y = g.resize(y, (size, size), bilinear=True, align_corners=True)
+    g.output(y if argmax is None else g.arg_max(y, axis=3, output=argmax))
     return g.build()
 
 

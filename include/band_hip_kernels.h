@@ -30,6 +30,8 @@
  *   bh_resize_bilinear_u8 <- RESIZE_BILINEAR uint8 (optimized_ops::ResizeBilinear, float path)
  *   bh_softmax_i8     <- SOFTMAX 8-bit      (optimized_ops::Softmax, lookup-table path)
  *   bh_mean           <- MEAN               (optimized_integer_ops::Mean / optimized_ops::Mean)
+ *   bh_argminmax      <- ARG_MAX / ARG_MIN  (reference_ops::ArgMinMax: first extreme, strict compare)
+ *   bh_resize_bilinear_argminmax_i8 <- RESIZE_BILINEAR int8 -> ARG_MAX / ARG_MIN over channels, fused
  *   bh_detection_postprocess <- TFLite_Detection_PostProcess (custom; detection_postprocess.cc,
  *                        fast NMS, one class per detection)
  *   (HARD_SWISH 8-bit runs as a bh_lut_u8 table of reference_ops::HardSwish)
@@ -611,6 +613,50 @@ typedef struct {
   void* output;
 } bh_resize_bilinear_params;
 int bh_resize_bilinear_i8(const bh_resize_bilinear_params* p, bh_stream_t s);
+
+/* ARG_MAX / ARG_MIN (TFLite arg_min_max.cc -> reference_ops::ArgMinMax): the
+ * input viewed as [outer][axis_len][inner]; out[o][i] = the index along the
+ * axis of the extreme, found as the sequential loop finds it: start at
+ * element 0 and replace only on > (< for min), so the FIRST extreme wins, a
+ * float NaN is selected only as element 0, and -0.0 == +0.0.  Output int32
+ * (out_bytes 4) or int64 (8, high word zero).  inner == 1 and axis_len < 64:
+ * a thread per row (argminmax_kernel); inner == 1 and axis_len >= 64: a wave
+ * per row with a cross-lane reduction that prefers the smaller index
+ * (argminmax_row_kernel); inner > 1: a thread per position walking the axis
+ * at stride `inner` (argminmax_kernel).  No scratch, no atomics. */
+#define BH_ARG_I8 0
+#define BH_ARG_U8 1
+#define BH_ARG_F32 2
+typedef struct {
+  long outer, axis_len, inner;
+  int in_type;                    /* BH_ARG_I8 / BH_ARG_U8 / BH_ARG_F32 */
+  int is_min;                     /* 0 ARG_MAX, 1 ARG_MIN */
+  int out_bytes;                  /* 4 (int32) or 8 (int64) */
+  const void* input;
+  void* output;                   /* [outer][inner], aligned to out_bytes */
+} bh_argminmax_params;
+int bh_argminmax(const bh_argminmax_params* p, bh_stream_t s);
+/* the kernel bh_argminmax dispatches to for these sizes */
+const char* bh_argminmax_kernel(const bh_argminmax_params* p);
+
+/* RESIZE_BILINEAR (int8) followed by ARG_MAX / ARG_MIN over the channel axis
+ * as one launch (resize_bilinear_argminmax_kernel): the resized tensor is
+ * never stored.  Per output pixel the channel values are the same integer
+ * expression as bh_resize_bilinear_i8's column form, walked c = 0 .. C-1 with
+ * the first extreme kept.  output: [batch][out_h][out_w] indices.  A
+ * workgroup stages the vertically blended input rows (int32, one padded row
+ * of in_w * (channels | 1) words per output row) and the column tables in
+ * LDS; geometries needing more than 64 KB of it, or more than 1024 output
+ * columns, are refused (BH_EINVAL, bh_last_error names the reason) and the
+ * caller runs the two launches.  bh_resize_bilinear_argminmax_i8_ok: the
+ * same check without a launch (0 = would run). */
+typedef struct {
+  bh_resize_bilinear_params rz;   /* rz.output: the index map */
+  int is_min;
+  int out_bytes;                  /* 4 / 8 */
+} bh_resize_argminmax_params;
+int bh_resize_bilinear_argminmax_i8(const bh_resize_argminmax_params* p, bh_stream_t s);
+int bh_resize_bilinear_argminmax_i8_ok(const bh_resize_argminmax_params* p);
 
 /* RESIZE_BILINEAR uint8 (TFLite 2.9.2 optimized_ops::ResizeBilinear for
  * uint8 -> ResizeBilinearGenericSmallChannel<uint8>): float interpolation.
