@@ -142,6 +142,15 @@ class ResizeArgMinMaxParams(ctypes.Structure):
     _fields_ = [("rz", ResizeBilinearParams), ("is_min", c_int), ("out_bytes", c_int)]
 
 
+REINDEX_MAX_RANK = 6
+
+
+class ReindexParams(ctypes.Structure):
+    _fields_ = [("elem_bytes", c_int), ("rank", c_int), ("out_dims", c_int * REINDEX_MAX_RANK),
+                ("in_stride", ctypes.c_int64 * REINDEX_MAX_RANK), ("in_offset", ctypes.c_int64),
+                ("input", c_void_p), ("output", c_void_p)]
+
+
 class ResizeBilinearU8Params(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("batch", "in_h", "in_w", "channels", "out_h", "out_w")] + [
         (n, c_void_p) for n in ("y_idx", "x_idx", "y_frac", "x_frac", "input", "output")]
@@ -250,6 +259,10 @@ KERNEL_SYMBOLS = {
     "bh_argminmax_kernel": (ctypes.c_char_p, [ctypes.POINTER(ArgMinMaxParams)]),
     "bh_resize_bilinear_argminmax_i8": (c_int, [ctypes.POINTER(ResizeArgMinMaxParams), c_void_p]),
     "bh_resize_bilinear_argminmax_i8_ok": (c_int, [ctypes.POINTER(ResizeArgMinMaxParams)]),
+    "bh_reindex": (c_int, [ctypes.POINTER(ReindexParams), c_void_p]),
+    "bh_reindex_as": (c_int, [ctypes.POINTER(ReindexParams), c_int, c_void_p]),
+    "bh_reindex_kernel": (ctypes.c_char_p, [ctypes.POINTER(ReindexParams)]),
+    "bh_reindex_canonical": (c_int, [ctypes.POINTER(ReindexParams), ctypes.POINTER(ReindexParams)]),
     "bh_softmax_i8": (c_int, [ctypes.POINTER(SoftmaxParams), c_void_p]),
     "bh_zero_insert": (c_int, [ctypes.POINTER(ZeroInsertParams), c_void_p]),
     "bh_conv2d_f32": (c_int, [ctypes.POINTER(ConvF32Params), c_void_p]),

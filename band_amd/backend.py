@@ -80,6 +80,7 @@ _abi.BACKEND_SYMBOLS.update({
     "bhx_profile_subgraph": (c_int, _KEY + [c_int, ctypes.POINTER(OpTiming), c_int, ctypes.POINTER(c_int),
                                             ctypes.POINTER(ctypes.c_double)]),
     "bhx_time_subgraph": (c_int, _KEY + [c_int, ctypes.POINTER(ctypes.c_double)]),
+    "bhx_cpu_reindex": (c_int, [ctypes.POINTER(_abi.ReindexParams)]),
     "bhx_prepare_job_batches": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_uint64, c_int]),
     "bhx_max_job_batch": (c_int, _KEY + [ctypes.POINTER(c_int)]),
     "bhx_job_slot_view": (c_int, _KEY + [c_int, c_int, c_int, ctypes.POINTER(TensorInfo)]),

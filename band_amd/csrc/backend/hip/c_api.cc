@@ -447,4 +447,11 @@ int bhx_time_subgraph(bhx_executor* e, int mid, int wid, uint64_t mask, int iter
   return 0;
 }
 
+int bhx_cpu_reindex(const void* reindex_params) {
+  if (!reindex_params) return Fail("null argument");
+  if (!band::hip::CpuReindex(*static_cast<const bh_reindex_params*>(reindex_params)))
+    return Fail((std::string("CpuReindex: ") + bh_last_error()).c_str());
+  return 0;
+}
+
 }  // extern "C"

@@ -820,5 +820,36 @@ void CpuArgMinMax(const bh_argminmax_params& p, CpuPool& pool) {
   });
 }
 
+bool CpuReindex(const bh_reindex_params& p) {
+  bh_reindex_params c;
+  if (!p.input || !p.output || bh_reindex_canonical(&p, &c) != 0) return false;
+  const int64_t eb = c.elem_bytes;
+  const int last = c.rank - 1;
+  const int64_t run = c.out_dims[last], step = c.in_stride[last] * eb;
+  int64_t rows = 1;
+  for (int d = 0; d < last; ++d) rows *= c.out_dims[d];
+  const char* in = static_cast<const char*>(c.input) + c.in_offset * eb;
+  char* out = static_cast<char*>(c.output);
+  int idx[BH_REINDEX_MAX_RANK] = {0};
+  int64_t off = 0;  // input byte offset of the current row
+  for (int64_t r = 0; r < rows; ++r) {
+    if (c.in_stride[last] == 1) {
+      std::memcpy(out, in + off, static_cast<size_t>(run * eb));
+    } else if (eb == 4) {
+      for (int64_t i = 0; i < run; ++i) std::memcpy(out + 4 * i, in + off + i * step, 4);
+    } else {
+      for (int64_t i = 0; i < run; ++i) out[i] = in[off + i * step];
+    }
+    out += run * eb;
+    for (int d = last - 1; d >= 0; --d) {  // odometer over the outer dims
+      off += c.in_stride[d] * eb;
+      if (++idx[d] < c.out_dims[d]) break;
+      off -= c.in_stride[d] * eb * c.out_dims[d];
+      idx[d] = 0;
+    }
+  }
+  return true;
+}
+
 }  // namespace hip
 }  // namespace band

@@ -107,5 +107,12 @@ void CpuMean(const CpuMeanParams& p, CpuPool& pool);
 // extreme wins and a float NaN is selected only as element 0
 void CpuArgMinMax(const bh_argminmax_params& p, CpuPool& pool);
 
+// The re-indexing ops (TRANSPOSE, STRIDED_SLICE, SLICE, SPLIT, SPLIT_V,
+// SPACE_TO_DEPTH, DEPTH_TO_SPACE): bh_reindex's host twin over the same
+// canonical map (bh_reindex_canonical) - rows are copied whole where the
+// innermost stride is 1, element by element otherwise.  False for a map the
+// launcher would refuse.
+bool CpuReindex(const bh_reindex_params& p);
+
 }  // namespace hip
 }  // namespace band

@@ -323,6 +323,222 @@ inline bool ArgMinMaxArgs(const TflModel& m, const TflOperator& op, long* outer,
   return true;
 }
 
+// The re-indexing ops: TRANSPOSE, STRIDED_SLICE, SLICE, SPLIT, SPLIT_V,
+// SPACE_TO_DEPTH, DEPTH_TO_SPACE
+inline bool IsReindexOp(int builtin) {
+  return builtin == kTflTranspose || builtin == kTflStridedSlice || builtin == kTflSlice || builtin == kTflSplit ||
+         builtin == kTflSplitV || builtin == kTflSpaceToDepth || builtin == kTflDepthToSpace;
+}
+// the values of a constant int32 / int64 tensor
+inline bool ConstInts(const TflTensor& t, std::vector<int64_t>* v) {
+  if (!t.is_const() || (t.type != DataType::kInt32 && t.type != DataType::kInt64)) return false;
+  const size_t eb = t.type == DataType::kInt64 ? 8 : 4, n = t.num_elements();
+  if (t.data_size < n * eb) return false;
+  v->resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    if (eb == 8) {
+      std::memcpy(&(*v)[i], t.data + 8 * i, 8);
+    } else {
+      int32_t x;
+      std::memcpy(&x, t.data + 4 * i, 4);
+      (*v)[i] = x;
+    }
+  }
+  return true;
+}
+
+// Resolves output `oi` of a re-indexing op to the map bh_reindex / CpuReindex
+// run (map->input / output stay null): the output's extents (rank <= 6),
+// signed input strides in elements and an input element offset.  Semantics
+// are numpy's: np.transpose(x, perm); x[b:b+s] per axis with size -1 = to the
+// end; basic indexing x[b:e:s] per axis (negative indices, out-of-range
+// clamping, negative strides; a begin_mask / end_mask bit makes the bound None,
+// a shrink_axis_mask bit makes the axis the index x[b]); np.split;
+// DEPTH_TO_SPACE out[n, h bs + by, w bs + bx, c] = in[n, h, w, (by bs + bx) C' + c]
+// and SPACE_TO_DEPTH its inverse.  Starts and strides come from the constants
+// and the input's shape, extents from the OUTPUT tensor's shape, which must be
+// what the constants resolve to - except that an output may take the whole of
+// input axis 0 from element 0 at stride 1 whatever end / size say (a job-batch
+// variant scales axis 0 of every tensor, not the constants).  *whole_batch:
+// the output's axis 0 is the input's, in full (the job-batch rule).  *why names
+// what was refused.
+inline bool ReindexArgs(const TflModel& m, const TflOperator& op, int oi, bh_reindex_params* map,
+                        const char** why = nullptr, bool* whole_batch = nullptr) {
+  auto no = [&](const char* w) {
+    if (why) *why = w;
+    return false;
+  };
+  const int b = op.builtin;
+  const int xin = b == kTflSplit ? 1 : 0;
+  const size_t need = b == kTflStridedSlice ? 4 : (b == kTflSlice || b == kTflSplitV) ? 3
+                      : (b == kTflTranspose || b == kTflSplit)                       ? 2
+                                                                                     : 1;
+  if (!IsReindexOp(b) || op.inputs.size() < need || oi < 0 || oi >= static_cast<int>(op.outputs.size()) ||
+      op.outputs[oi] < 0)
+    return no("missing operands");
+  for (size_t i = 0; i < need; ++i)
+    if (op.inputs[i] < 0) return no("missing operands");
+  const TflTensor& in = m.tensors[op.inputs[xin]];
+  const TflTensor& out = m.tensors[op.outputs[oi]];
+  if (in.type != DataType::kInt8 && in.type != DataType::kUInt8 && in.type != DataType::kFloat32 &&
+      in.type != DataType::kInt32)
+    return no("element type must be int8, uint8, float32 or int32");
+  if (out.type != in.type) return no("output type differs from the input's");
+  if (in.scale != out.scale || in.zero_point != out.zero_point)
+    return no("output quantization differs from the input's (the op copies bytes)");
+  if (out.num_elements() == 0) return no("output has no elements");
+  const int r = static_cast<int>(in.shape.size());
+  if (r > BH_REINDEX_MAX_RANK) return no("rank > 6");
+  std::vector<int64_t> istr(r, 1);
+  for (int d = r - 2; d >= 0; --d) istr[d] = istr[d + 1] * in.shape[d + 1];
+  std::vector<int64_t> ext, str, expect;  // the map's extents / strides, the output shape they mean
+  int64_t off = 0;
+  bool lead = false;  // map dim 0 walks input axis 0 from element 0 at stride 1
+  auto ints = [&](int input, std::vector<int64_t>* v) { return ConstInts(m.tensors[op.inputs[input]], v); };
+  if (b == kTflTranspose) {
+    std::vector<int64_t> perm;
+    if (!ints(1, &perm)) return no("TRANSPOSE perm must be a constant int32 / int64 tensor");
+    if (r > 5) return no("TRANSPOSE rank > 5");
+    std::vector<bool> seen(r, false);
+    if (static_cast<int>(perm.size()) != r) return no("TRANSPOSE perm is not a permutation");
+    for (int64_t p : perm) {
+      if (p < 0 || p >= r || seen[p]) return no("TRANSPOSE perm is not a permutation");
+      seen[p] = true;
+      ext.push_back(in.shape[p]);
+      str.push_back(istr[p]);
+    }
+    lead = r > 0 && perm[0] == 0;
+    expect = ext;
+  } else if (b == kTflSlice) {
+    std::vector<int64_t> begin, size;
+    if (!ints(1, &begin) || !ints(2, &size)) return no("SLICE begin / size must be constant int32 / int64 tensors");
+    if (r > 5) return no("SLICE rank > 5");
+    if (static_cast<int>(begin.size()) != r || static_cast<int>(size.size()) != r)
+      return no("SLICE begin / size length differs from the rank");
+    for (int d = 0; d < r; ++d) {
+      const int64_t n = in.shape[d], s = size[d] == -1 ? n - begin[d] : size[d];
+      if (begin[d] < 0 || begin[d] > n || s < 0 || begin[d] + s > n) return no("SLICE begin / size outside the input");
+      ext.push_back(s);
+      str.push_back(istr[d]);
+      off += begin[d] * istr[d];
+    }
+    lead = r > 0 && begin[0] == 0;
+    expect = ext;
+  } else if (b == kTflStridedSlice) {
+    std::vector<int64_t> begin, end, step;
+    if (!ints(1, &begin) || !ints(2, &end) || !ints(3, &step))
+      return no("STRIDED_SLICE begin / end / strides must be constant int32 / int64 tensors");
+    if (r > 5) return no("STRIDED_SLICE rank > 5");
+    if (static_cast<int>(begin.size()) != r || static_cast<int>(end.size()) != r || static_cast<int>(step.size()) != r)
+      return no("STRIDED_SLICE begin / end / strides length differs from the rank");
+    const FbTable& o = op.options;
+    const int begin_mask = o.valid() ? o.Int(0, 0) : 0, end_mask = o.valid() ? o.Int(1, 0) : 0;
+    const int shrink_mask = o.valid() ? o.Int(4, 0) : 0;
+    if (o.valid() && (o.Int(2, 0) != 0 || o.Int(3, 0) != 0))
+      return no("STRIDED_SLICE ellipsis_mask / new_axis_mask unsupported");
+    for (int d = 0; d < r; ++d) {
+      const int64_t n = in.shape[d], s = step[d];
+      if (s == 0) return no("STRIDED_SLICE stride 0");
+      if (shrink_mask >> d & 1) {  // x[b]
+        const int64_t i = begin[d] < 0 ? begin[d] + n : begin[d];
+        if (i < 0 || i >= n) return no("STRIDED_SLICE shrink index outside the input");
+        off += i * istr[d];
+        continue;
+      }
+      // slice(b, e, s).indices(n)
+      const int64_t lo = s > 0 ? 0 : -1, hi = s > 0 ? n : n - 1;
+      auto bound = [&](int64_t v) {
+        if (v < 0) v += n;
+        return v < lo ? lo : (v > hi ? hi : v);
+      };
+      const int64_t start = begin_mask >> d & 1 ? (s > 0 ? 0 : n - 1) : bound(begin[d]);
+      const int64_t stop = end_mask >> d & 1 ? (s > 0 ? n : -1) : bound(end[d]);
+      const int64_t count = s > 0 ? (stop > start ? (stop - start + s - 1) / s : 0)
+                                  : (start > stop ? (start - stop - s - 1) / -s : 0);
+      if (d == 0) lead = start == 0 && s == 1;
+      ext.push_back(count);
+      str.push_back(s * istr[d]);
+      off += (count > 0 ? start : 0) * istr[d];
+    }
+    expect = ext;
+  } else if (b == kTflSplit || b == kTflSplitV) {
+    std::vector<int64_t> axis_v, sizes;
+    const bool v = b == kTflSplitV;
+    if (!ints(v ? 2 : 0, &axis_v) || axis_v.size() != 1)
+      return no(v ? "SPLIT_V axis must be one constant int32 / int64 value"
+                  : "SPLIT axis must be one constant int32 / int64 value");
+    int64_t axis = axis_v[0] < 0 ? axis_v[0] + r : axis_v[0];
+    if (axis < 0 || axis >= r) return no(v ? "SPLIT_V axis out of range" : "SPLIT axis out of range");
+    const int64_t n = in.shape[axis], parts = static_cast<int64_t>(op.outputs.size());
+    if (op.options.valid() && op.options.Int(0, 0) != 0 && op.options.Int(0, 0) != parts)
+      return no(v ? "SPLIT_V num_splits differs from the number of outputs"
+                  : "SPLIT num_splits differs from the number of outputs");
+    int64_t first = 0, len = 0;
+    if (v) {
+      if (!ints(1, &sizes)) return no("SPLIT_V size_splits must be a constant int32 / int64 tensor");
+      int64_t sum = 0;
+      int open = -1;
+      bool bad = static_cast<int64_t>(sizes.size()) != parts;
+      for (size_t k = 0; k < sizes.size() && !bad; ++k) {
+        if (sizes[k] == -1 && open < 0) open = static_cast<int>(k);
+        else if (sizes[k] < 0) bad = true;
+        else sum += sizes[k];
+      }
+      if (!bad && open >= 0 && sum <= n) sizes[open] = n - sum, sum = n;
+      if (bad || sum != n) return no("SPLIT_V size_splits do not sum to the axis extent");
+      for (int k = 0; k < oi; ++k) first += sizes[k];
+      len = sizes[oi];
+    } else {
+      if (n % parts != 0) return no("SPLIT axis extent is not a multiple of num_splits");
+      len = n / parts;
+      first = oi * len;
+    }
+    for (int d = 0; d < r; ++d) {
+      ext.push_back(d == axis ? len : in.shape[d]);
+      str.push_back(istr[d]);
+    }
+    off = first * istr[axis];
+    lead = axis != 0;
+    expect = ext;
+  } else {  // SPACE_TO_DEPTH / DEPTH_TO_SPACE
+    const bool d2s = b == kTflDepthToSpace;
+    if (r != 4 || out.shape.size() != 4)
+      return no(d2s ? "DEPTH_TO_SPACE needs 4-D tensors" : "SPACE_TO_DEPTH needs 4-D tensors");
+    const int64_t bs = op.options.valid() ? op.options.Int(0, 0) : 0;
+    const int64_t N = in.shape[0], H = in.shape[1], W = in.shape[2], C = in.shape[3];
+    if (d2s) {
+      if (bs < 1 || C % (bs * bs) != 0) return no("DEPTH_TO_SPACE block_size does not divide the channels");
+      const int64_t c = C / (bs * bs);
+      ext = {N, H, bs, W, bs, c};  // (n, h, by, w, bx, c)
+      str = {istr[0], istr[1], bs * c, istr[2], c, 1};
+      expect = {N, H * bs, W * bs, c};
+    } else {
+      if (bs < 1 || H % bs != 0 || W % bs != 0) return no("SPACE_TO_DEPTH block_size does not divide height and width");
+      ext = {N, H / bs, W / bs, bs, bs, C};  // (n, h, w, by, bx, c)
+      str = {istr[0], bs * istr[1], bs * istr[2], istr[1], istr[2], 1};
+      expect = {N, H / bs, W / bs, C * bs * bs};
+    }
+    lead = true;
+  }
+  if (expect.size() != out.shape.size()) return no("output shape differs from what the op's arguments resolve to");
+  const bool whole0 = lead && !out.shape.empty() && out.shape[0] == in.shape[0];
+  for (size_t d = 0; d < expect.size(); ++d)
+    if (out.shape[d] != expect[d] && !(d == 0 && whole0))
+      return no("output shape differs from what the op's arguments resolve to");
+  if (whole0) ext[0] = in.shape[0];
+  if (ext.size() > BH_REINDEX_MAX_RANK) return no("rank > 6");
+  *map = bh_reindex_params{};
+  map->elem_bytes = static_cast<int>(GetDataTypeBytes(in.type));
+  map->rank = static_cast<int>(ext.size());
+  for (size_t d = 0; d < ext.size(); ++d) {
+    map->out_dims[d] = static_cast<int>(ext[d]);
+    map->in_stride[d] = str[d];
+  }
+  map->in_offset = off;
+  if (whole_batch) *whole_batch = whole0;
+  return true;
+}
+
 // TFLite_Detection_PostProcess in the form the host kernel and the device
 // kernels (kernels/detection.hip) implement.  batch: the images of a
 // job-batch variant (the leading dimension of the op's tensors; the anchors

@@ -711,6 +711,48 @@ absl::Status HipModelExecutor::LowerDetectionGpu(const HipModel& model, int oi, 
   return absl::OkStatus();
 }
 
+// TRANSPOSE / STRIDED_SLICE / SLICE / SPLIT / SPLIT_V / SPACE_TO_DEPTH /
+// DEPTH_TO_SPACE: each output is one map (ReindexArgs) and one launch - a
+// SPLIT with n outputs is n launches, each writing its own dense tensor.
+absl::Status HipModelExecutor::LowerReindex(const HipModel& model, int oi, PreparedSubgraph* sg) {
+  const TflModel& d = model.desc();
+  const TflOperator& op = d.ops[oi];
+  void* in_ptr = nullptr;
+  RETURN_STATUS_IF(DevicePtr(model, op.inputs[op.builtin == kTflSplit ? 1 : 0], sg, &in_ptr));
+  for (int k = 0; k < static_cast<int>(op.outputs.size()); ++k) {
+    Launch L;
+    L.op_index = oi;
+    L.out_tensor = op.outputs[k];
+    const char* why = "";
+    if (!ReindexArgs(d, op, k, &L.reindex, &why))
+      return absl::InternalError(std::string("unsupported ") + TflBuiltinName(op.builtin) + ": " + why);
+    void* out_ptr = nullptr;
+    RETURN_STATUS_IF(DevicePtr(model, op.outputs[k], sg, &out_ptr));
+    L.reindex.input = in_ptr;
+    L.reindex.output = out_ptr;
+    bh_reindex_params c;
+    if (bh_reindex_canonical(&L.reindex, &c) != 0)
+      return absl::InternalError(std::string(TflBuiltinName(op.builtin)) + ": " + bh_last_error());
+    const size_t bytes = meta_[op.outputs[k]]->bytes;
+    L.alg_bytes = 2.0 * bytes;
+    if (c.rank == 1 && c.in_stride[0] == 1 && c.in_offset == 0) {
+      // the identity (a TRANSPOSE that only moves unit dims, a SLICE of
+      // everything): same bytes, as RESHAPE
+      L.kind = Launch::kCopy;
+      L.kernel = "copy";
+      L.src = in_ptr;
+      L.dst = out_ptr;
+      L.bytes = bytes;
+      if (L.src == L.dst) continue;
+    } else {
+      L.kind = Launch::kReindex;
+      L.kernel = device_flag_ == DeviceFlag::kCPU ? "reindex_host" : bh_reindex_kernel(&L.reindex);
+    }
+    sg->launches.push_back(L);
+  }
+  return absl::OkStatus();
+}
+
 absl::Status HipModelExecutor::Lower(const HipModel& model, int oi, PreparedSubgraph* sg) {
   const TflModel& d = model.desc();
   const TflOperator& op = d.ops[oi];
@@ -724,6 +766,7 @@ absl::Status HipModelExecutor::Lower(const HipModel& model, int oi, PreparedSubg
     sg->fused_tensors.insert(op.outputs[0]);
     return absl::OkStatus();
   }
+  if (IsReindexOp(op.builtin)) return LowerReindex(model, oi, sg);
   auto T = [&](int i) -> const TflTensor& { return d.tensors[i]; };
   const TflTensor& in = T(op.inputs[0]);
   const TflTensor& out = T(op.outputs[0]);

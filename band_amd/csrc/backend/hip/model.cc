@@ -70,6 +70,17 @@ absl::Status HipModel::CloneWithJobBatch(int batch, std::unique_ptr<HipModel>* o
       if (ex::ArgMinMaxArgs(desc_, op, &outer, &len, &inner, &out_bytes, &axis) && axis == 0)
         return absl::InternalError(std::string("job batching: ") + TflBuiltinName(op.builtin) + " on the batch axis");
     }
+    if (ex::IsReindexOp(op.builtin)) {
+      // a map may touch axis 0 only as the full range: no TRANSPOSE with
+      // perm[0] != 0, no SPLIT / SPLIT_V on axis 0, no slice of part of it
+      for (int k = 0; k < static_cast<int>(op.outputs.size()); ++k) {
+        bh_reindex_params map;
+        bool whole_batch = false;
+        if (ex::ReindexArgs(desc_, op, k, &map, nullptr, &whole_batch) && !whole_batch)
+          return absl::InternalError(std::string("job batching: ") + TflBuiltinName(op.builtin) +
+                                     " does not keep the whole batch axis");
+      }
+    }
   }
   for (const TflTensor& t : desc_.tensors)
     if (!t.is_const() && (t.shape.empty() || t.shape[0] != 1))

@@ -183,6 +183,19 @@ bool HipModelExecutor::GpuSupports(const TflModel& m, const TflOperator& op, std
       if (!ArgMinMaxArgs(m, op, &o, &l, &i, &ob, nullptr, &w)) return no(w);
       return true;
     }
+    case kTflTranspose:
+    case kTflStridedSlice:
+    case kTflSlice:
+    case kTflSplit:
+    case kTflSplitV:
+    case kTflSpaceToDepth:
+    case kTflDepthToSpace: {
+      bh_reindex_params map;
+      const char* w = "";
+      for (int k = 0; k < static_cast<int>(op.outputs.size()); ++k)
+        if (!ReindexArgs(m, op, k, &map, &w)) return no(w);
+      return true;
+    }
     case kTflSoftmax:
       if (!IsQ8(in.type) || out.type != in.type || !HasQ(in) || !HasQ(out) || in.shape.empty())
         return no("only 8-bit quantized in and out");
@@ -617,6 +630,7 @@ absl::Status HipModelExecutor::EnqueueLaunch(const Launch& l) {
     case Launch::kDetectionGpu: rc = bh_detection_postprocess(&l.detg, stream_); break;
     case Launch::kArgMinMax: rc = bh_argminmax(&l.argmm, stream_); break;
     case Launch::kResizeArgMinMax: rc = bh_resize_bilinear_argminmax_i8(&l.rzarg, stream_); break;
+    case Launch::kReindex: rc = bh_reindex(&l.reindex, stream_); break;
     case Launch::kMean: {
       bh_mean_params q{};
       q.outer = l.mean.outer;
@@ -817,6 +831,7 @@ absl::Status HipModelExecutor::ExecuteOnHost(PreparedSubgraph* sg) {
       case Launch::kDetectionPost: CpuDetectionPostprocess(l.det, pool); break;
       case Launch::kMean: CpuMean(l.mean, pool); break;
       case Launch::kArgMinMax: CpuArgMinMax(l.argmm, pool); break;
+      case Launch::kReindex: CpuReindex(l.reindex); break;
       default: return absl::InternalError(std::string("no host implementation of ") + l.kernel);
     }
   }

@@ -48,7 +48,8 @@ struct Launch {
     kConvGroup,      // independent small convs in one dispatch (GroupConvs)
     kDetectionGpu,   // TFLite_Detection_PostProcess on the device (BAND_HIP_GPU_DETECTION=1)
     kArgMinMax,      // ARG_MAX / ARG_MIN
-    kResizeArgMinMax // RESIZE_BILINEAR int8 -> ARG_MAX / ARG_MIN over channels, one launch (FuseGlue; kGPU)
+    kResizeArgMinMax, // RESIZE_BILINEAR int8 -> ARG_MAX / ARG_MIN over channels, one launch (FuseGlue; kGPU)
+    kReindex          // one output of TRANSPOSE / STRIDED_SLICE / SLICE / SPLIT / SPLIT_V / SPACE_TO_DEPTH / DEPTH_TO_SPACE
   } kind;
   int op_index = -1;
   int out_tensor = -1;  // tensor this launch materialises (after epilogue fusions)
@@ -81,6 +82,7 @@ struct Launch {
   CpuMeanParams mean{};
   bh_argminmax_params argmm{};
   bh_resize_argminmax_params rzarg{};
+  bh_reindex_params reindex{};
   const void* table = nullptr;  // kLutU8 / kLutF32: 256-entry device table
   long count = 0;               // kLut* / kQuantF32: elements
   float q_scale = 0.f;          // kQuantF32
@@ -237,6 +239,10 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
                                   PreparedSubgraph* sg, Launch* l);
   absl::Status LowerGlue(const HipModel& model, int op_index, void* in_ptr, void* out_ptr, const std::string& ckey,
                          PreparedSubgraph* sg, Launch* l);
+  // the re-indexing ops (ReindexArgs): one kReindex launch per output; a map
+  // that is the identity lowers as RESHAPE does (a kCopy, dropped when both
+  // sides share a slot)
+  absl::Status LowerReindex(const HipModel& model, int op_index, PreparedSubgraph* sg);
   // TFLite_Detection_PostProcess on the device: one bh_detection_postprocess launch
   absl::Status LowerDetectionGpu(const HipModel& model, int op_index, PreparedSubgraph* sg, Launch* l);
   // op_index is an 8-bit DEQUANTIZE whose float output only the device

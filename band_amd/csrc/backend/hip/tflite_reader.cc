@@ -47,6 +47,13 @@ const char* TflBuiltinName(int c) {
     case kTflHardSwish: return "HARD_SWISH";
     case kTflArgMax: return "ARG_MAX";
     case kTflArgMin: return "ARG_MIN";
+    case kTflDepthToSpace: return "DEPTH_TO_SPACE";
+    case kTflSpaceToDepth: return "SPACE_TO_DEPTH";
+    case kTflTranspose: return "TRANSPOSE";
+    case kTflStridedSlice: return "STRIDED_SLICE";
+    case kTflSplit: return "SPLIT";
+    case kTflSlice: return "SLICE";
+    case kTflSplitV: return "SPLIT_V";
     default: return "UNKNOWN";
   }
 }

@@ -28,6 +28,12 @@ enum TflBuiltin : int {
   kTflQuantize = 114, kTflHardSwish = 117,
   // ArgMaxOptions / ArgMinOptions: slot 0 output_type (TensorType: 2 int32, 4 int64)
   kTflArgMax = 56, kTflArgMin = 79,
+  // the re-indexing ops.  StridedSliceOptions: slots 0-4 begin_mask, end_mask,
+  // ellipsis_mask, new_axis_mask, shrink_axis_mask; SplitOptions /
+  // SplitVOptions: slot 0 num_splits; SpaceToDepthOptions /
+  // DepthToSpaceOptions: slot 0 block_size; TRANSPOSE and SLICE have no fields
+  kTflDepthToSpace = 5, kTflSpaceToDepth = 26, kTflTranspose = 39, kTflStridedSlice = 45, kTflSplit = 49,
+  kTflSlice = 65, kTflSplitV = 102,
 };
 
 const char* TflBuiltinName(int code);

@@ -10,7 +10,7 @@ import numpy as np
 
 from . import tflite_synth as S
 
-_NP = {0: np.float32, 2: np.int32, 3: np.uint8, 4: np.int64, 9: np.int8, 7: np.int16}
+_NP = {0: np.float32, 1: np.float16, 2: np.int32, 3: np.uint8, 4: np.int64, 9: np.int8, 7: np.int16}
 
 # BuiltinOptions union index -> [(slot, fmt)], fmt 'vi' = vector<int>
 OPTION_FIELDS = {
@@ -24,6 +24,13 @@ OPTION_FIELDS = {
     17: [(0, "vi")],                                                            # Reshape
     21: [(0, "b")],                                                             # Mul
     28: [(0, "b"), (1, "B")],                                                   # Sub
+    19: [(0, "i")],                                                             # SpaceToDepth
+    26: [],                                                                     # Transpose
+    32: [(0, "i"), (1, "i"), (2, "i"), (3, "i"), (4, "i")],                     # StridedSlice
+    35: [(0, "i")],                                                             # Split
+    44: [],                                                                     # Slice
+    79: [(0, "i")],                                                             # SplitV
+    94: [(0, "i")],                                                             # DepthToSpace
 }
 
 

@@ -25,13 +25,16 @@ OPC = dict(ADD=0, AVERAGE_POOL_2D=1, CONCATENATION=2, CONV_2D=3, DEPTHWISE_CONV_
            FULLY_CONNECTED=9, LOGISTIC=14, MAX_POOL_2D=17, MUL=18, RESHAPE=22,
            RESIZE_BILINEAR=23, SOFTMAX=25, CUSTOM=32, PAD=34, SUB=41, QUANTIZE=114,
            DEQUANTIZE=6, RELU=19, RELU_N1_TO_1=20, RELU6=21, PADV2=60, RESIZE_NEAREST_NEIGHBOR=97,
-           TRANSPOSE_CONV=67, ARG_MAX=56, ARG_MIN=79)
+           TRANSPOSE_CONV=67, ARG_MAX=56, ARG_MIN=79,
+           DEPTH_TO_SPACE=5, SPACE_TO_DEPTH=26, TRANSPOSE=39, STRIDED_SLICE=45, SPLIT=49, SLICE=65, SPLIT_V=102)
 # BuiltinOptions union indices
 OPT = dict(Conv2DOptions=1, DepthwiseConv2DOptions=2, Pool2DOptions=5, FullyConnectedOptions=8,
            SoftmaxOptions=9, ConcatenationOptions=10, AddOptions=11, ReshapeOptions=17,
            ResizeBilinearOptions=15, MulOptions=21, PadOptions=22, SubOptions=28,
            DequantizeOptions=38, PadV2Options=43, TransposeConvOptions=49, ResizeNearestNeighborOptions=74,
-           QuantizeOptions=89, ArgMaxOptions=40, ArgMinOptions=57)
+           QuantizeOptions=89, ArgMaxOptions=40, ArgMinOptions=57,
+           SpaceToDepthOptions=19, TransposeOptions=26, StridedSliceOptions=32, SplitOptions=35, SliceOptions=44,
+           SplitVOptions=79, DepthToSpaceOptions=94)
 
 
 # ---------------------------------------------------------------------------
@@ -297,10 +300,91 @@ def act_options(act="NONE"):
     return Table().set(0, "b", ACT[act])
 
 
+class _ReindexOps:
+    """The re-indexing ops of QGraph and FGraph: TRANSPOSE, STRIDED_SLICE,
+    SLICE, SPLIT, SPLIT_V, SPACE_TO_DEPTH, DEPTH_TO_SPACE.  They draw nothing
+    from the RNG; an output inherits the input's quantisation (the ops copy
+    bytes).  Index arguments are constant int32 tensors."""
+
+    def _re_out(self, x, shape):
+        shape = [int(v) for v in shape]
+        return self._like(x, shape=shape) if hasattr(self, "_like") else self._act(shape)
+
+    def _re_ints(self, kind, values):
+        v = np.asarray(values, np.int32)
+        return self.mb.tensor(self._name(kind), list(v.shape), np.int32, data=v)
+
+    def transpose(self, x, perm):
+        shp = self.meta[x][0]
+        pt = self._re_ints("perm", list(perm))
+        y = self._re_out(x, [shp[p] for p in perm])
+        self.mb.op("TRANSPOSE", [x, pt], [y], OPT["TransposeOptions"], Table())
+        return y
+
+    def slice(self, x, begin, size):
+        """x[b0:b0+s0, ...]; size -1 = to the end"""
+        shp = self.meta[x][0]
+        bt, st = self._re_ints("begin", list(begin)), self._re_ints("size", list(size))
+        y = self._re_out(x, [shp[d] - begin[d] if size[d] == -1 else size[d] for d in range(len(shp))])
+        self.mb.op("SLICE", [x, bt, st], [y], OPT["SliceOptions"], Table())
+        return y
+
+    def strided_slice(self, x, begin, end, strides, begin_mask=0, end_mask=0, shrink_axis_mask=0,
+                      ellipsis_mask=0, new_axis_mask=0):
+        """numpy basic indexing x[b:e:s] per axis; a begin_mask / end_mask bit
+        drops that bound, a shrink_axis_mask bit makes the axis the index x[b]"""
+        shp = self.meta[x][0]
+        idx = tuple(int(begin[d]) if shrink_axis_mask >> d & 1 else
+                    slice(None if begin_mask >> d & 1 else int(begin[d]),
+                          None if end_mask >> d & 1 else int(end[d]), int(strides[d])) for d in range(len(shp)))
+        out_shape = np.broadcast_to(np.int8(0), shp)[idx].shape
+        ins = [x, self._re_ints("begin", list(begin)), self._re_ints("end", list(end)),
+               self._re_ints("strides", list(strides))]
+        y = self._re_out(x, out_shape)
+        opt = (Table().set(0, "i", begin_mask).set(1, "i", end_mask).set(2, "i", ellipsis_mask)
+               .set(3, "i", new_axis_mask).set(4, "i", shrink_axis_mask))
+        self.mb.op("STRIDED_SLICE", ins, [y], OPT["StridedSliceOptions"], opt)
+        return y
+
+    def split(self, x, num_splits, axis):
+        """np.split(x, num_splits, axis): a list of outputs"""
+        shp = list(self.meta[x][0])
+        at = self.mb.tensor(self._name("axis"), [], np.int32, data=np.array(axis, np.int32))
+        shp[axis] //= num_splits
+        ys = [self._re_out(x, shp) for _ in range(num_splits)]
+        self.mb.op("SPLIT", [at, x], ys, OPT["SplitOptions"], Table().set(0, "i", num_splits))
+        return ys
+
+    def split_v(self, x, sizes, axis):
+        """np.split at the running sums of `sizes` (one may be -1: the rest)"""
+        shp = list(self.meta[x][0])
+        st = self._re_ints("size_splits", list(sizes))
+        at = self.mb.tensor(self._name("axis"), [], np.int32, data=np.array(axis, np.int32))
+        known = sum(s for s in sizes if s != -1)
+        ys = []
+        for s in sizes:
+            shp[axis] = self.meta[x][0][axis] - known if s == -1 else s
+            ys.append(self._re_out(x, shp))
+        self.mb.op("SPLIT_V", [x, st, at], ys, OPT["SplitVOptions"], Table().set(0, "i", len(sizes)))
+        return ys
+
+    def space_to_depth(self, x, block_size):
+        n, h, w, c = self.meta[x][0]
+        y = self._re_out(x, [n, h // block_size, w // block_size, c * block_size * block_size])
+        self.mb.op("SPACE_TO_DEPTH", [x], [y], OPT["SpaceToDepthOptions"], Table().set(0, "i", block_size))
+        return y
+
+    def depth_to_space(self, x, block_size):
+        n, h, w, c = self.meta[x][0]
+        y = self._re_out(x, [n, h * block_size, w * block_size, c // (block_size * block_size)])
+        self.mb.op("DEPTH_TO_SPACE", [x], [y], OPT["DepthToSpaceOptions"], Table().set(0, "i", block_size))
+        return y
+
+
 # ---------------------------------------------------------------------------
 # quantised graph construction with synthetic (seeded) weights
 # ---------------------------------------------------------------------------
-class QGraph:
+class QGraph(_ReindexOps):
     """Builds an int8 (per-channel) or uint8 (per-tensor) NHWC graph.
 
     Scales mimic converter output (RELU6 tensors at 6/255) and filter scales
@@ -612,7 +696,7 @@ class QGraph:
         return self.mb.build()
 
 
-class FGraph:
+class FGraph(_ReindexOps):
     """Float graph builder with QGraph's method names: a TFLite fp16 model
     (post-training float16 quantization) - float32 activations, every
     constant stored as float16 behind a DEQUANTIZE op, float32 compute.

@@ -178,6 +178,10 @@ int bhx_run_mixed_jobs(int n_models, bhx_executor* const* execs, const int* mode
 /* device microseconds per pass of a prepared subgraph, `iters` passes issued
  * back to back on the executor's stream (graph replay when captured) */
 int bhx_time_subgraph(bhx_executor* e, int model_id, int worker_id, uint64_t unit_mask, int iters, double* us);
+/* CpuReindex, the kCPU worker's host twin of bh_reindex, over host pointers:
+ * `reindex_params` is a bh_reindex_params (band_hip_kernels.h).  Tests compare
+ * it with numpy without building a model around every map. */
+int bhx_cpu_reindex(const void* reindex_params);
 
 /* --- job batching (extension, backend/hip/job_batching.h) -------------
  * Not in the reference interface: Band runs one job per ExecuteSubgraph

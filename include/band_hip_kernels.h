@@ -32,6 +32,8 @@
  *   bh_mean           <- MEAN               (optimized_integer_ops::Mean / optimized_ops::Mean)
  *   bh_argminmax      <- ARG_MAX / ARG_MIN  (reference_ops::ArgMinMax: first extreme, strict compare)
  *   bh_resize_bilinear_argminmax_i8 <- RESIZE_BILINEAR int8 -> ARG_MAX / ARG_MIN over channels, fused
+ *   bh_reindex        <- TRANSPOSE, STRIDED_SLICE, SLICE, SPLIT, SPLIT_V, SPACE_TO_DEPTH,
+ *                        DEPTH_TO_SPACE (one launch per output; numpy's indexing semantics)
  *   bh_detection_postprocess <- TFLite_Detection_PostProcess (custom; detection_postprocess.cc,
  *                        fast NMS, one class per detection)
  *   (HARD_SWISH 8-bit runs as a bh_lut_u8 table of reference_ops::HardSwish)
@@ -638,6 +640,48 @@ typedef struct {
 int bh_argminmax(const bh_argminmax_params* p, bh_stream_t s);
 /* the kernel bh_argminmax dispatches to for these sizes */
 const char* bh_argminmax_kernel(const bh_argminmax_params* p);
+
+/* The re-indexing ops - TRANSPOSE, STRIDED_SLICE, SLICE, SPLIT, SPLIT_V,
+ * SPACE_TO_DEPTH, DEPTH_TO_SPACE: every output element is one input element.
+ * The output is dense row-major over out_dims[0 .. rank); element
+ * (i_0, .., i_{rank-1}) is input element in_offset + sum_d i_d * in_stride[d]
+ * (strides and offset in elements; a stride may be negative).  The caller guarantees every such element lies inside the input.
+ * bh_reindex_canonical drops unit dims and merges dims d, d + 1 when
+ * in_stride[d] == in_stride[d + 1] * out_dims[d + 1] (rank >= 1 afterwards; a
+ * map that is the identity comes out as rank 1, stride 1); pure host.  The
+ * launcher canonicalises, refuses rank > 6 and more than 2^31 - 1 elements
+ * (FastDiv index math), and runs one of
+ *   reindex_rows_kernel    innermost stride 1: runs of out_dims[last] *
+ *                          elem_bytes contiguous bytes on both sides, moved 16 /
+ *                          8 / 4 / 1 bytes per lane (the widest that divides
+ *                          the run, both addresses and every outer stride in
+ *                          bytes); short runs share a wave
+ *   reindex_tile_kernel    another dim has input stride 1 (a true transpose)
+ *                          and that dim and the last are both >= 64 long:
+ *                          64 x 64 tiles through LDS, loads coalesced along the
+ *                          input-contiguous dim, stores along the output's last
+ *   reindex_gather_kernel  the rest (negative / non-unit innermost stride, a
+ *                          transpose with an edge shorter than a tile - measured
+ *                          faster there): a thread per 4 output bytes, dword stores
+ * No scratch, no atomics. */
+#define BH_REINDEX_MAX_RANK 6
+typedef struct {
+  int elem_bytes;                 /* 1 or 4 */
+  int rank;                       /* 0 .. BH_REINDEX_MAX_RANK */
+  int out_dims[BH_REINDEX_MAX_RANK];
+  int64_t in_stride[BH_REINDEX_MAX_RANK]; /* elements */
+  int64_t in_offset;              /* elements */
+  const void* input;              /* aligned to elem_bytes */
+  void* output;                   /* aligned to elem_bytes */
+} bh_reindex_params;
+int bh_reindex(const bh_reindex_params* p, bh_stream_t s);
+/* the kernel bh_reindex dispatches to for this map ("" for a refused one) */
+const char* bh_reindex_kernel(const bh_reindex_params* p);
+int bh_reindex_canonical(const bh_reindex_params* p, bh_reindex_params* canonical);
+/* bh_reindex with the form chosen by the caller: gather != 0 runs
+ * reindex_gather_kernel, which takes any map, whatever bh_reindex would pick
+ * (tools/reindex_profile.py times the forms side by side); 0 is bh_reindex. */
+int bh_reindex_as(const bh_reindex_params* p, int gather, bh_stream_t s);
 
 /* RESIZE_BILINEAR (int8) followed by ARG_MAX / ARG_MIN over the channel axis
  * as one launch (resize_bilinear_argminmax_kernel): the resized tensor is
