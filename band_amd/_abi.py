@@ -101,7 +101,7 @@ class ChainParams(ctypes.Structure):
     _fields_ = [("dw", DwConvParams), ("pw1", ConvParams), ("pw2", ConvParams), ("has_pw2", c_int),
                 ("px_blocks", c_int), ("waves", c_int), ("persist", c_int), ("tile", c_int),
                 ("tile_blob", c_void_p), ("debug_stamps", c_void_p), ("deep", c_int), ("c_split", c_int),
-                ("stage", c_int)]
+                ("stage", c_int), ("dense", c_int)]
 
 
 # symbol -> (restype, argtypes)
@@ -289,6 +289,8 @@ KERNEL_SYMBOLS = {
     "bh_chain_tile_pack": (c_int, [ctypes.POINTER(ChainParams), c_void_p, c_void_p]),
     "bh_chain_stage_lds_bytes": (c_size_t, [ctypes.POINTER(ChainParams)]),
     "bh_chain_stage_launch": (c_int, [ctypes.POINTER(ChainParams), c_void_p]),
+    "bh_chain_dense_lds_bytes": (c_size_t, [ctypes.POINTER(ChainParams)]),
+    "bh_chain_dense_launch": (c_int, [ctypes.POINTER(ChainParams), c_void_p]),
     "bh_last_error": (ctypes.c_char_p, []),
 }
 

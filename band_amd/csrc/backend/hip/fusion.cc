@@ -575,8 +575,8 @@ void HipModelExecutor::FuseChains(const HipModel& model, PreparedSubgraph* sg) {
       }
       const bool measured = u > 0 && u_p2 >= 0;
       Fastest best(u);
-      for (ChainForm f : kChainForms) {
-        if (!measured || FilteredOut(f, no_tile_chain_, no_deep_chain_, no_split_chain_, no_stage_chain_)) continue;
+      ForEachChainForm([&](ChainForm f) {
+        if (!measured || FilteredOut(f, no_tile_chain_, no_deep_chain_, no_split_chain_, no_stage_chain_)) return;
         for (f.launches = 3; f.launches >= 2; --f.launches) {
           Launch F;
           F.kind = Launch::kChain;
@@ -586,7 +586,7 @@ void HipModelExecutor::FuseChains(const HipModel& model, PreparedSubgraph* sg) {
           const double total = us + (f.launches == 2 && ok3 ? u_p2 : 0.0);
           if (best.Offer(us > 0 ? total : us)) form = f;
         }
-      }
+      });
       if (measured) TuneStore(key, Encode(form));
       else form = ForcedForm(ForcedChain::kPlain, ok3 ? c3 : c2);  // no device timing: 3 launches when they apply
     }
@@ -600,7 +600,9 @@ void HipModelExecutor::FuseChains(const HipModel& model, PreparedSubgraph* sg) {
     if (F.chain.tile_blob) sg->consts.push_back(form.launches == 3 ? blob3 : blob2);  // owned by the subgraph
     const bool three = form.launches == 3;
     F.out_tensor = three ? P2->out_tensor : P1.out_tensor;
-    F.kernel = F.chain.stage ? "chain_stage_kernel" : (F.chain.tile ? "chain_tile_kernel" : "chain_kernel");
+    F.kernel = F.chain.dense   ? "chain_dense_kernel"
+               : F.chain.stage ? "chain_stage_kernel"
+                               : (F.chain.tile ? "chain_tile_kernel" : "chain_kernel");
     const bh_dwconv_params& dw = F.chain.dw;
     const bh_conv_params& a = F.chain.pw1;
     const double px = static_cast<double>(dw.batch) * dw.out_h * dw.out_w;

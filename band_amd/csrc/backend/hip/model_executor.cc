@@ -317,6 +317,7 @@ absl::Status HipModelExecutor::EnsureMeta(const HipModel& model) {
   if (std::strcmp(f, "nosplit") == 0) no_split_chain_ = true;  // A-B: without the phase-C split forms
   if (std::strcmp(f, "forcedeep") == 0) forced_chain_ = ForcedChain::kDeep;  // ... in the deep form
   if (std::strcmp(f, "forcestage") == 0) forced_chain_ = ForcedChain::kStage;  // ... in the stage form
+  if (std::strcmp(f, "forcedense") == 0) forced_chain_ = ForcedChain::kDense;  // ... in the dense form
   if (std::strcmp(f, "nostage") == 0) no_stage_chain_ = true;  // A-B: without the stage forms
   if (!env::Autotune()) autotune_ = false;
   return absl::OkStatus();

@@ -293,7 +293,7 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   bool allow_chain_ = true;   // BAND_HIP_FUSION=nochain
   bool allow_group_ = true;   // BAND_HIP_FUSION=nogroup: one launch per conv
   bool allow_argmax_ = true;  // BAND_HIP_FUSION=noargmax: RESIZE_BILINEAR and ARG_MAX / ARG_MIN as two launches
-  // BAND_HIP_FUSION=forcechain / forcetile / forcedeep / forcestage (parity
+  // BAND_HIP_FUSION=forcechain / forcetile / forcedeep / forcestage / forcedense (parity
   // tests): every feasible chain fused, in the named form where that fits
   ForcedChain forced_chain_ = ForcedChain::kNone;
   bool no_tile_chain_ = false;     // BAND_HIP_FUSION=notile: the tuner skips the tile form

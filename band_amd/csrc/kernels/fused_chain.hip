@@ -961,6 +961,7 @@ extern "C" size_t bh_chain_lds_bytes(const bh_chain_params* pp) {
   }
   const long widest = std::max<long>(std::max(d.out_c, p.pw1.out_c), p.has_pw2 ? p.pw2.out_c : 0);
   if (P * widest >= INT32_MAX || (long)d.batch * d.in_h * d.in_w * d.in_c >= INT32_MAX) return 0;
+  if (p.dense) return bh_chain_dense_lds_bytes(pp);
   if (p.stage) return bh_chain_stage_lds_bytes(pp);
   if (p.c_split < 0 || p.c_split > 4) return 0;
   if (p.c_split > 1 && (p.tile || p.persist || p.deep || p.px_blocks > 2 || !p.has_pw2 ||
@@ -986,6 +987,7 @@ extern "C" int bh_chain_i8(const bh_chain_params* pp, bh_stream_t stream) {
     return BH_EINVAL;
   }
   const bh_chain_params& p = *pp;
+  if (p.dense) return bh_chain_dense_launch(pp, stream);
   if (p.stage) return bh_chain_stage_launch(pp, stream);
   if (p.tile) return bh_chain_tile_launch(pp, stream);
   const int P = p.dw.batch * p.dw.out_h * p.dw.out_w;

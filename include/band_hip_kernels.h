@@ -373,7 +373,8 @@ int bh_irb_i8(const bh_irb_params* p, bh_stream_t s);
  * stride / dilation; all stages int8 in / symmetric filters (in_xor == 0,
  * w_zp == 0), no out_table; pw1 / pw2 1x1 stride 1 with out_c % 4 == 0;
  * pw2 without residual and with K = pw1.out_c <= 320.  px_blocks in {1, 2, 4};
- * 16 waves (px_blocks 1) spread few-pixel layers' channel work wider. */
+ * 16 waves (px_blocks 1) spread few-pixel layers' channel work wider; the
+ * dense form holds more waves per SIMD on the large-grid layers. */
 typedef struct bh_chain_params {
   bh_dwconv_params dw;
   bh_conv_params pw1;
@@ -419,6 +420,13 @@ typedef struct bh_chain_params {
    * with the burst issued by the upper half of the waves while the lower
    * half runs the depthwise phase */
   int stage;
+  /* 1: dense raster form (chain_dense_kernel) for chains whose grid gives
+   * every CU several workgroups - 64 pixels per 4-wave workgroup, a wave
+   * keeping its 16 pixels in LDS of its own through all three phases (no
+   * workgroup barrier between them), one item per load round, compiled for
+   * 6 - 8 waves per SIMD; px_blocks 4, 4 waves, no persist / tile / deep /
+   * c_split / stage, at most 64 KB of LDS */
+  int dense;
 } bh_chain_params;
 
 /* LDS bytes one workgroup of bh_chain_i8 needs (0 if unsupported) */
@@ -426,6 +434,9 @@ size_t bh_chain_lds_bytes(const bh_chain_params* p);
 /* the stage form's share of bh_chain_lds_bytes / bh_chain_i8 (stage != 0) */
 size_t bh_chain_stage_lds_bytes(const bh_chain_params* p);
 int bh_chain_stage_launch(const bh_chain_params* p, bh_stream_t s);
+/* the dense form's share of bh_chain_lds_bytes / bh_chain_i8 (dense != 0) */
+size_t bh_chain_dense_lds_bytes(const bh_chain_params* p);
+int bh_chain_dense_launch(const bh_chain_params* p, bh_stream_t s);
 /* the tile form's share of bh_chain_lds_bytes / bh_chain_i8 (tile != 0) */
 size_t bh_chain_tile_lds_bytes(const bh_chain_params* p);
 int bh_chain_tile_launch(const bh_chain_params* p, bh_stream_t s);

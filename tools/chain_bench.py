@@ -22,11 +22,14 @@ def main():
     ap.add_argument("--batch", type=int, default=24)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--px", default="1,2,4,1w16,1w8,4p,t,1d,1w8d,2d,g1w8,G1w8s2",
-                    help="forms: px_blocks [wN waves] [p persistent] [d deep-issue]; t = the 2-D tile form, "
+                    help="forms: px_blocks [wN waves] [p persistent] [d deep-issue] [x dense: 4x]; t = the 2-D tile form, "
                          "t3 / t4 = runs of 2 / 4 tiles per workgroup; "
                          "sN suffix = the phase-C split over N workgroups; "
                          "g prefix = the stage form (g1w8s2: 1 pixel block, 8 waves, 2 slices)")
     ap.add_argument("--only", default="", help="comma-separated chain indices")
+    ap.add_argument("--extra", default="", help="further chains, ';'-separated, each H,ce,stride,cout,residual,ce2 "
+                                                "(112,32,1,64,0,0: PoseNet's first depthwise + pointwise pair)")
+    ap.add_argument("--skip-base", action="store_true", help="only the --extra chains")
     a = ap.parse_args()
     from band_amd import _abi
     from tests.chain_harness import MNV2_CHAINS, ChainCase
@@ -38,7 +41,9 @@ def main():
     lib.bh_event_create(ctypes.byref(e1))
     total = {}
     only = [int(v) for v in a.only.split(",")] if a.only else list(range(len(MNV2_CHAINS)))
-    for (h, ce, s, cout, res, ce2) in [MNV2_CHAINS[i] for i in only]:
+    extra = [tuple(int(v) for v in e.split(",")) for e in a.extra.split(";") if e]
+    for (h, ce, s, cout, res, ce2) in ([] if a.skip_base else [MNV2_CHAINS[i] for i in only]) + [(e[0], e[1], e[2], e[3], bool(e[4]), e[5])
+                                                                        for e in extra]:
         c = ChainCase(np.random.default_rng(1), a.batch, h, h, ce, s, cout, res, ce2)
         row = []
         for form in a.px.split(","):
@@ -52,10 +57,12 @@ def main():
             tile = {"t": 1, "t3": 3, "t4": 4}.get(form, 0)
             persist = int(form.endswith("p") and not tile)
             deep = int(form.endswith("d"))
-            f = "4" if tile else form.rstrip("pd")
+            dense = int(form.endswith("x"))
+            f = "4" if tile else form.rstrip("pdx")
             px, waves = (int(f.split("w")[0]), int(f.split("w")[1])) if "w" in f else (int(f), 4)
             keep = []
             q = c.params(lib, px, keep, waves, persist, tile, deep, split, stage)
+            q.dense = dense
             if lib.bh_chain_lds_bytes(ctypes.byref(q)) == 0:
                 row.append("   -   ")
                 continue

@@ -38,8 +38,10 @@ def decode(choice):
     if choice >= 100000:  # kStageChoice + 1000 (stage - 1) + 100 slices + 10 px_blocks + (8 waves)
         c = choice - 100000
         return dict(stage=1 + c // 1000, c_split=(c % 1000) // 100, px_blocks=(c // 10) % 10,
-                    waves=8 if c % 10 else 4, deep=0, three=True, persist=0, tile=0, fused=True)
+                    waves=8 if c % 10 else 4, deep=0, three=True, persist=0, tile=0, fused=True, dense=0)
     f = dict(stage=0)
+    f["dense"] = int(8000 <= choice < 10000)  # 8004 / 8014: the dense raster form
+    choice -= 8000 * f["dense"]
     f["c_split"] = choice // 2000 + 1 if choice >= 2000 else 0
     choice %= 2000
     f["deep"] = int(choice >= 1000)
@@ -70,6 +72,9 @@ def instantiation(q, f, fast):
         return "chain_stage_kernel<%d, %s" % (f["px_blocks"], F), f["waves"]
     if f["tile"]:
         return "chain_tile_kernel<8, 8, %s" % F, 4
+    if f.get("dense"):  # K fragments of the second 1x1 held: 1, 2 or 5
+        ks2 = q.pw2.k_pad // 64 if q.has_pw2 else 1
+        return "chain_dense_kernel<%s, %d, 8>" % (F, 1 if ks2 <= 1 else (2 if ks2 <= 2 else 5)), 4
     k2 = (not q.has_pw2) or q.pw2.k_pad <= 128
     kx = 2 if k2 else 5
     var = 2 if f["c_split"] > 1 else 0
@@ -123,6 +128,7 @@ def main():
         keep = []
         q = case.params(lib, max(f["px_blocks"], 1), keep, f["waves"], 0, f["tile"], f["deep"], f["c_split"],
                         f["stage"])
+        q.dense = f["dense"]
         lds = lib.bh_chain_lds_bytes(ctypes.byref(q))
         if lds == 0:
             print("%-40s choice %d: not launchable here" % (str(tag), choice))
@@ -157,7 +163,7 @@ def main():
         lib.bh_event_elapsed_ms(e0, e1, ctypes.byref(ms))
         us = 1e3 * ms.value / a.iters
         form = ("t%d" % f["tile"]) if f["tile"] else "%s%d%s%s%s" % (
-            "gG"[f["stage"] - 1] if f["stage"] else "", f["px_blocks"], "w%d" % f["waves"] if f["waves"] != 4 else "", "d" if f["deep"] else "",
+            "gG"[f["stage"] - 1] if f["stage"] else "", f["px_blocks"], "w%d" % f["waves"] if f["waves"] != 4 else "", "x" if f["dense"] else ("d" if f["deep"] else ""),
             "s%d" % f["c_split"] if f["c_split"] > 1 else "")
         label = "%dx%d x%d s%d d%d -> %d%s -> %d" % (h, w, c, s, dil, cout, "+res" if r else "", nxt)
         print("%-40s %-6s %-44s %7.1f %6d %5s %4d %4d %-14s %6.2f %8.2f" % (
