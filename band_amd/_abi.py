@@ -30,6 +30,11 @@ class ConvParams(ctypes.Structure):
                                                                   ("out_img_stride", ctypes.c_int64)]
 
 
+class ConvGroupedParams(ctypes.Structure):
+    """bh_conv_grouped_params: grouped CONV_2D (`conv` carries the total channel counts)."""
+    _fields_ = [("conv", ConvParams), ("groups", c_int32)]
+
+
 class ConvGroup(ctypes.Structure):
     _fields_ = [("n", c_int), ("blocks", c_int), ("is1x1", c_int), ("table", c_void_p)]
 
@@ -245,6 +250,8 @@ KERNEL_SYMBOLS = {
     "bh_conv_group_plan": (c_int, [ctypes.POINTER(ConvParams), c_int, c_void_p, ctypes.POINTER(ConvGroup)]),
     "bh_conv_group_i8": (c_int, [ctypes.POINTER(ConvGroup), c_void_p]),
     "bh_conv2d_i8_kernel": (ctypes.c_char_p, [ctypes.POINTER(ConvParams)]),
+    "bh_conv2d_grouped_i8": (c_int, [ctypes.POINTER(ConvGroupedParams), c_void_p]),
+    "bh_conv2d_grouped_i8_kernel": (ctypes.c_char_p, [ctypes.POINTER(ConvGroupedParams)]),
     "bh_conv_gemm_big_config": (ctypes.c_int, [ctypes.c_long, ctypes.c_int]),
     "bh_dwconv2d_i8_kernel": (ctypes.c_char_p, [ctypes.POINTER(DwConvParams)]),
     "bh_lut_u8": (c_int, [c_void_p, c_void_p, ctypes.c_long, c_void_p, c_void_p]),

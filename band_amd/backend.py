@@ -81,6 +81,8 @@ _abi.BACKEND_SYMBOLS.update({
                                             ctypes.POINTER(ctypes.c_double)]),
     "bhx_time_subgraph": (c_int, _KEY + [c_int, ctypes.POINTER(ctypes.c_double)]),
     "bhx_cpu_reindex": (c_int, [ctypes.POINTER(_abi.ReindexParams)]),
+    "bhx_launch_kernels": (c_int, _KEY + [ctypes.POINTER(ctypes.c_char_p), c_int, ctypes.POINTER(c_int)]),
+    "bhx_cpu_conv_grouped": (c_int, [ctypes.POINTER(_abi.ConvGroupedParams)]),
     "bhx_prepare_job_batches": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_uint64, c_int]),
     "bhx_max_job_batch": (c_int, _KEY + [ctypes.POINTER(c_int)]),
     "bhx_job_slot_view": (c_int, _KEY + [c_int, c_int, c_int, ctypes.POINTER(TensorInfo)]),
@@ -480,6 +482,14 @@ class HipModelExecutor:
         rows = [dict(op_index=arr[i].op_index, kernel=arr[i].kernel.decode(), ms=arr[i].ms,
                      alg_bytes=arr[i].alg_bytes, alg_ops=arr[i].alg_ops) for i in range(min(n.value, cap))]
         return (rows, floor.value) if with_floor else rows
+
+    def LaunchKernels(self, key):
+        """kernel symbol of every launch of the prepared subgraph, in program order (no device needed)"""
+        n = c_int(0)
+        cap = 4096
+        arr = (ctypes.c_char_p * cap)()
+        _abi.check(self.lib.bhx_launch_kernels(self.handle, *key._args(), arr, cap, ctypes.byref(n)), "LaunchKernels")
+        return [arr[i].decode() for i in range(min(n.value, cap))]
 
     def TimeSubgraph(self, key, iters=100):
         """device microseconds per subgraph pass, passes issued back to back"""

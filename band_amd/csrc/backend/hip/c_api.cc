@@ -454,4 +454,28 @@ int bhx_cpu_reindex(const void* reindex_params) {
   return 0;
 }
 
+int bhx_launch_kernels(bhx_executor* e, int mid, int wid, uint64_t mask, const char** out, int cap, int* n) {
+  auto* h = e ? dynamic_cast<band::hip::HipModelExecutor*>(e->exec.get()) : nullptr;
+  if (!h) return Fail("not a HIP executor");
+  std::vector<const char*> k;
+  auto s = h->LaunchKernels(Key(mid, wid, mask), &k);
+  if (!s.ok()) return Fail(s);
+  if (n) *n = static_cast<int>(k.size());
+  for (int i = 0; out && i < cap && i < static_cast<int>(k.size()); ++i) out[i] = k[i];
+  return 0;
+}
+
+int bhx_cpu_conv_grouped(const void* grouped_params) {
+  if (!grouped_params) return Fail("null argument");
+  const bh_conv_grouped_params& gp = *static_cast<const bh_conv_grouped_params*>(grouped_params);
+  const bh_conv_params& p = gp.conv;
+  if (gp.groups < 1 || p.in_c <= 0 || p.out_c <= 0 || p.in_c % gp.groups || p.out_c % gp.groups || !p.input ||
+      !p.output || !p.weights || !p.bias_eff || !p.mult || !p.shift ||
+      p.k_pad < p.k_h * p.k_w * (p.in_c / gp.groups))
+    return Fail("CpuConvGrouped: invalid parameters");
+  band::hip::CpuPool pool(1);
+  band::hip::CpuConvGrouped(p, gp.groups, pool);
+  return 0;
+}
+
 }  // extern "C"

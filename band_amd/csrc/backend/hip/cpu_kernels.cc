@@ -196,6 +196,65 @@ void CpuConv(const bh_conv_params& p, CpuPool& pool) {
   });
 }
 
+// ---- grouped CONV_2D: CpuConv per group (rows of K_g, the group's slice) ------
+
+void CpuConvGrouped(const bh_conv_params& p, int groups, CpuPool& pool) {
+  const long M = static_cast<long>(p.batch) * p.out_h * p.out_w;
+  const int icg = p.in_c / groups, ocg = p.out_c / groups;
+  const int K = p.k_h * p.k_w * icg;
+  const uint8_t* in = static_cast<const uint8_t*>(p.input);
+  const int8_t* W = p.weights;
+  uint8_t* out = static_cast<uint8_t*>(p.output);
+  const uint8_t* res = static_cast<const uint8_t*>(p.residual);
+  const uint8_t* tab = static_cast<const uint8_t*>(p.out_table);
+  const uint8_t xorb = static_cast<uint8_t>(p.in_xor);
+  const int8_t padv = static_cast<int8_t>(p.in_zp);
+  pool.ParallelFor(M, [&](long m0, long m1) {
+    std::vector<int8_t> row(static_cast<size_t>(K));
+    for (long m = m0; m < m1; ++m) {
+      const int ox = static_cast<int>(m % p.out_w);
+      const long t = m / p.out_w;
+      const int oy = static_cast<int>(t % p.out_h);
+      const int n = static_cast<int>(t / p.out_h);
+      const int y0 = oy * p.stride_h - p.pad_h, x0 = ox * p.stride_w - p.pad_w;
+      uint8_t* o = out + m * p.out_c;
+      for (int g = 0; g < groups; ++g) {
+        // im2col row of the group's channel slice; out-of-image taps hold the input zp
+        int k = 0;
+        for (int fy = 0; fy < p.k_h; ++fy) {
+          const int y = y0 + fy * p.dil_h;
+          for (int fx = 0; fx < p.k_w; ++fx) {
+            const int x = x0 + fx * p.dil_w;
+            if (y < 0 || y >= p.in_h || x < 0 || x >= p.in_w) {
+              std::memset(&row[k], static_cast<uint8_t>(padv), icg);
+            } else {
+              const uint8_t* src = in + ((static_cast<long>(n) * p.in_h + y) * p.in_w + x) * p.in_c + g * icg;
+              for (int c = 0; c < icg; ++c) row[k + c] = static_cast<int8_t>(src[c] ^ xorb);
+            }
+            k += icg;
+          }
+        }
+        int32_t rowsum = 0;
+        if (p.w_zp != 0)
+          for (int i = 0; i < K; ++i) rowsum += row[i];
+        for (int c = g * ocg; c < (g + 1) * ocg; ++c) {
+          int32_t a = Dot(row.data(), W + static_cast<long>(c) * p.k_pad, K) + p.bias_eff[c];
+          if (p.w_zp != 0) a -= p.w_zp * rowsum;
+          int32_t v = Clamp(Requant(a, p.mult[c], p.shift[c]) + p.out_zp, p.act_min, p.act_max);
+          if (res) {
+            const int32_t q = Load8(res, m * p.out_c + c, p.in_xor == 0);
+            const int32_t sy = RequantLt1((v + p.add_y_off) * (1 << p.add_left_shift), p.add_y_mult, p.add_y_shift);
+            const int32_t sr = RequantLt1((q + p.add_r_off) * (1 << p.add_left_shift), p.add_r_mult, p.add_r_shift);
+            v = Clamp(RequantLt1(sy + sr, p.add_o_mult, p.add_o_shift) + p.add_o_off, p.add_act_min, p.add_act_max);
+          }
+          const uint8_t byte = static_cast<uint8_t>(v);
+          o[c] = tab ? tab[byte] : byte;
+        }
+      }
+    }
+  });
+}
+
 // ---- DEPTHWISE_CONV_2D: [kh][kw][out_c] int8-domain filters, raw bias -------
 
 void CpuDwConv(const bh_dwconv_params& p, CpuPool& pool) {

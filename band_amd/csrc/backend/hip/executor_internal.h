@@ -64,7 +64,9 @@ inline const char* WithAdd(const char* k) {
                                          {"conv_xs_kernel", "conv_xs_kernel+add"},
                                          {"conv_rows_kernel", "conv_rows_kernel+add"},
                                          {"conv_direct_kernel", "conv_direct_kernel+add"},
-                                         {"conv_stem_kernel", "conv_stem_kernel+add"}};
+                                         {"conv_stem_kernel", "conv_stem_kernel+add"},
+                                         {"conv_grouped_mfma_kernel", "conv_grouped_mfma_kernel+add"},
+                                         {"conv_grouped_host", "conv_grouped_host+add"}};
   for (const auto& n : names)
     if (std::strcmp(k, n[0]) == 0) return n[1];
   return k;
@@ -177,7 +179,7 @@ inline bool FloatSupports(const TflModel& m, const TflOperator& op, std::string*
         return w.shape.size() == 2 && w.shape[1] > 0 && in.num_elements() % w.shape[1] == 0 ? true
                                                                                           : no("FC weights");
       if (in.shape.size() != 4 || w.shape.size() != 4 || out.shape.size() != 4) return no("conv needs 4-D");
-      if (op.builtin == kTflConv2D && w.shape[3] != in.shape[3]) return no("grouped conv unsupported");
+      if (op.builtin == kTflConv2D && w.shape[3] != in.shape[3]) return no("grouped conv: int8 / uint8 only");
       if (op.builtin == kTflDepthwiseConv2D && (in.shape[3] == 0 || w.shape[3] % in.shape[3] != 0))
         return no("bad depth multiplier");
       return true;

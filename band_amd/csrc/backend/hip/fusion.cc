@@ -21,6 +21,7 @@ namespace {
 bool LaunchIo(const Launch& l, std::vector<const void*>* rd, std::vector<const void*>* wr) {
   switch (l.kind) {
     case Launch::kConv:
+    case Launch::kConvGrouped:
       *rd = {l.conv.input, l.conv.residual};
       *wr = {l.conv.output};
       return true;
@@ -627,7 +628,8 @@ namespace {
 void** OutSlot(Launch& l) {
   switch (l.kind) {
     case Launch::kChain: return l.chain.has_pw2 ? &l.chain.pw2.output : &l.chain.pw1.output;
-    case Launch::kConv: return &l.conv.output;
+    case Launch::kConv:
+    case Launch::kConvGrouped: return &l.conv.output;
     case Launch::kDwConv: return &l.dw.output;
     case Launch::kFc: return &l.fc.output;
     case Launch::kEltwise: return &l.elt.out;
@@ -639,7 +641,8 @@ void** OutSlot(Launch& l) {
 }
 const void** TableSlot(Launch& l) {
   switch (l.kind) {
-    case Launch::kConv: return l.conv.residual ? nullptr : &l.conv.out_table;  // + ADD epilogue: keep apart
+    case Launch::kConv:
+    case Launch::kConvGrouped: return l.conv.residual ? nullptr : &l.conv.out_table;  // + ADD epilogue: keep apart
     case Launch::kDwConv: return &l.dw.out_table;
     case Launch::kFc: return &l.fc.out_table;
     default: return nullptr;

@@ -813,7 +813,12 @@ absl::Status HipModelExecutor::Lower(const HipModel& model, int oi, PreparedSubg
     const int32_t w_zp = i8 ? 0 : Dom(w);  // int8 kernels ignore the filter zero point
     const double M = static_cast<double>(b) * oh * ow;
     if (!dw) {
-      const int K = kh * kw * ic;
+      // grouped (filter [oc][kh][kw][icg], icg != ic): the same packed layout
+      // with K = K_g, one row per output channel (GpuSupports checked that
+      // the group count divides both channel counts)
+      const int icg = w.shape[3];
+      const int groups = icg == ic ? 1 : ic / icg;
+      const int K = kh * kw * icg;
       int kp = 0, np = 0;
       bh_conv_packed_geometry(oc, K, &kp, &np);
       const size_t wbytes = static_cast<size_t>(kp) * np;
@@ -845,8 +850,15 @@ absl::Status HipModelExecutor::Lower(const HipModel& model, int oi, PreparedSubg
       p.weights = static_cast<const int8_t*>(blob->ptr());
       p.bias_eff = tab; p.mult = tab + oc; p.shift = tab + 2 * oc;
       p.requant_fast = bh_conv_requant_fast_ok(mult.data(), shift.data(), oc, K, MaxAbs(bias, oc));
-      L.kind = Launch::kConv;
-      L.kernel = bh_conv2d_i8_kernel(&p);  // the kernel bh_conv2d_i8 dispatches to
+      if (groups == 1) {
+        L.kind = Launch::kConv;
+        L.kernel = bh_conv2d_i8_kernel(&p);  // the kernel bh_conv2d_i8 dispatches to
+      } else {
+        L.kind = Launch::kConvGrouped;
+        L.conv_groups = groups;
+        const bh_conv_grouped_params gp{p, groups};
+        L.kernel = cpu ? "conv_grouped_host" : bh_conv2d_grouped_i8_kernel(&gp);
+      }
       L.alg_ops = 2.0 * M * oc * K;
       L.alg_bytes = static_cast<double>(in.num_elements()) + M * oc + static_cast<double>(oc) * K + 12.0 * oc;
     } else {
@@ -1086,6 +1098,8 @@ absl::Status HipModelExecutor::Lower(const HipModel& model, int oi, PreparedSubg
     } else {
       TryFuseResidualAdd(model, oi, sg, &L);
     }
+  } else if (L.kind == Launch::kConvGrouped) {
+    TryFuseResidualAdd(model, oi, sg, &L);  // the grouped kernel shares the dense epilogue
   }
   sg->launches.push_back(L);
   return absl::OkStatus();

@@ -120,7 +120,13 @@ bool HipModelExecutor::GpuSupports(const TflModel& m, const TflOperator& op, std
         return true;
       }
       if (in.shape.size() != 4 || w.shape.size() != 4 || out.shape.size() != 4) return no("conv needs 4-D");
-      if (op.builtin == kTflConv2D && w.shape[3] != in.shape[3]) return no("grouped conv unsupported");
+      if (op.builtin == kTflConv2D && w.shape[3] != in.shape[3]) {
+        // grouped: groups = in_c / filter_in_c must divide both channel counts
+        if (w.shape[3] <= 0 || in.shape[3] % w.shape[3] != 0)
+          return no("grouped conv: input channels not a multiple of the filter's");
+        if (w.shape[0] % (in.shape[3] / w.shape[3]) != 0)
+          return no("grouped conv: output channels not a multiple of the group count");
+      }
       if (op.builtin == kTflDepthwiseConv2D && (in.shape[3] == 0 || w.shape[3] % in.shape[3] != 0))
         return no("bad depth multiplier");
       return true;
@@ -588,6 +594,11 @@ absl::Status HipModelExecutor::EnqueueLaunch(const Launch& l) {
   int rc = 0;
   switch (l.kind) {
     case Launch::kConv: rc = bh_conv2d_i8(&l.conv, stream_); break;
+    case Launch::kConvGrouped: {
+      const bh_conv_grouped_params gp{l.conv, l.conv_groups};
+      rc = bh_conv2d_grouped_i8(&gp, stream_);
+      break;
+    }
     case Launch::kDwConv: rc = bh_dwconv2d_i8(&l.dw, stream_); break;
     case Launch::kFc: rc = bh_fc_i8(&l.fc, stream_); break;
     case Launch::kEltwise: rc = bh_eltwise_i8(&l.elt, stream_); break;
@@ -798,6 +809,7 @@ absl::Status HipModelExecutor::ExecuteOnHost(PreparedSubgraph* sg) {
   for (const Launch& l : sg->launches) {
     switch (l.kind) {
       case Launch::kConv: CpuConv(l.conv, pool); break;
+      case Launch::kConvGrouped: CpuConvGrouped(l.conv, l.conv_groups, pool); break;
       case Launch::kDwConv: CpuDwConv(l.dw, pool); break;
       case Launch::kFc: CpuFc(l.fc, pool); break;
       case Launch::kEltwise: CpuEltwise(l.elt, pool); break;
@@ -963,6 +975,14 @@ absl::Status HipModelExecutor::TimeSubgraph(const SubgraphKey& key, int iters, d
   for (auto e : ring) bh_event_destroy(e);
   if (status.ok()) *us = 1e3 * ms / iters;
   return status;
+}
+
+absl::Status HipModelExecutor::LaunchKernels(const SubgraphKey& key, std::vector<const char*>* out) const {
+  PreparedSubgraph* sg = Find(key);
+  if (!sg) return absl::InternalError("Cannot find subgraph");
+  out->clear();
+  for (const Launch& l : sg->launches) out->push_back(l.kernel);
+  return absl::OkStatus();
 }
 
 absl::Status HipModelExecutor::ProfileSubgraph(const SubgraphKey& key, int iters, std::vector<OpTiming>* out,

@@ -49,11 +49,13 @@ struct Launch {
     kDetectionGpu,   // TFLite_Detection_PostProcess on the device (BAND_HIP_GPU_DETECTION=1)
     kArgMinMax,      // ARG_MAX / ARG_MIN
     kResizeArgMinMax, // RESIZE_BILINEAR int8 -> ARG_MAX / ARG_MIN over channels, one launch (FuseGlue; kGPU)
-    kReindex          // one output of TRANSPOSE / STRIDED_SLICE / SLICE / SPLIT / SPLIT_V / SPACE_TO_DEPTH / DEPTH_TO_SPACE
+    kReindex,         // one output of TRANSPOSE / STRIDED_SLICE / SLICE / SPLIT / SPLIT_V / SPACE_TO_DEPTH / DEPTH_TO_SPACE
+    kConvGrouped      // grouped CONV_2D: `conv` with the total channel counts + conv_groups (never chained / grouped / blocked)
   } kind;
   int op_index = -1;
   int out_tensor = -1;  // tensor this launch materialises (after epilogue fusions)
   bh_conv_params conv{};
+  int conv_groups = 1;  // kConvGrouped
   bh_dwconv_params dw{};
   bh_fc_params fc{};
   bh_eltwise_params elt{};
@@ -183,6 +185,9 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   // + gap), what an event figure holds beyond the kernel itself.
   absl::Status ProfileSubgraph(const SubgraphKey& key, int iters, std::vector<OpTiming>* out,
                                double* floor_us = nullptr);
+  // Kernel symbol of every launch of a prepared subgraph in program order
+  // (host twins on a kCPU executor); needs no device
+  absl::Status LaunchKernels(const SubgraphKey& key, std::vector<const char*>* out) const;
   // Device time of one subgraph pass (us) with `iters` passes issued back to
   // back (replayed hipGraph when captured, else the launch sequence): no host
   // gaps, H2D/D2H included.  The latency floor of ExecuteSubgraph's device side.

@@ -454,17 +454,20 @@ class QGraph(_ReindexOps):
         return self.mb.tensor(self._name("bias"), [out_c], np.int32, scale=bs, zero_point=[0] * out_c, data=b)
 
     def conv(self, x, out_c, k=1, stride=1, act="RELU6", padding="SAME", dilation=1, out_scale=None,
-             bias_offset_lsb=0):
+             bias_offset_lsb=0, groups=1):
         """CONV_2D; `out_scale` overrides the output scale and
         `bias_offset_lsb` shifts every output channel by that many output
-        LSBs (a detection head's class prior)"""
+        LSBs (a detection head's class prior); `groups` > 1 writes the grouped
+        filter [out_c, k, k, c // groups] (output channel o reads the input
+        channels of group o // (out_c // groups) only)"""
         shp, s_in, _ = self.meta[x]
         b, h, w, c = shp
+        assert c % groups == 0 and out_c % groups == 0, "groups must divide both channel counts"
         s_out, zp = self._out_q(act, s_in)
         if out_scale is not None:
             s_out = float(out_scale)
-        K = k * k * c
-        wt, ws = self._weights([out_c, k, k, c], out_c, 0, s_in, s_out, K)
+        K = k * k * c // groups
+        wt, ws = self._weights([out_c, k, k, c // groups], out_c, 0, s_in, s_out, K)
         bt = self._bias(out_c, s_in, ws, K)
         if bias_offset_lsb:
             bias = self.mb.tensors[bt]
@@ -884,6 +887,45 @@ def mobilenet_v1(dtype=np.int8, seed=0, size=224, batch=1, classes=1001):
     x = g.conv(x, classes, k=1, act="NONE")
     x = g.reshape(x, [batch, classes])
     g.output(x)
+    return g.build()
+
+
+def shufflenet_v1(dtype=np.int8, seed=5, size=224, groups=3, width=1.0, batch=1, classes=1000, repeats=(3, 7, 3)):
+    """ShuffleNet-v1 (Zhang et al. 2018, table 1; 240 / 480 / 960 channels at
+    groups=3, width 1.0).  A unit is grouped 1x1 CONV_2D -> channel shuffle
+    (RESHAPE - TRANSPOSE - RESHAPE) -> depthwise 3x3 -> grouped 1x1 CONV_2D,
+    joined to its input by ADD (stride 1) or, after a 3x3 stride-2 average
+    pool of the input, by CONCATENATION (stride 2).  The very first grouped
+    layer is dense, as in the paper (its input has 8 * groups channels)."""
+    g = QGraph(dtype, seed, "shufflenet_v1_g%d_%s" % (groups, np.dtype(dtype).name))
+    q = 4 * groups  # stage widths: the bottleneck (a quarter) splits into `groups`
+    stem = 8 * groups
+    x = g.input([batch, size, size, 3])
+    x = g.conv(x, stem, k=3, stride=2)
+    x = g.maxpool(x, (3, 3), 2)
+    c_in = stem
+    for stage, n in enumerate(repeats):
+        c_out = max(q, int(80 * groups * width * (1 << stage)) // q * q)
+        for i in range(n + 1):
+            stride = 2 if i == 0 else 1
+            mid = c_out // 4
+            branch_out = c_out - c_in if stride == 2 else c_out
+            _, h, w, _ = g.meta[x][0]
+            y = g.conv(x, mid, k=1, groups=1 if (stage == 0 and i == 0) else groups)
+            y = g.reshape(y, [batch, h, w, groups, mid // groups])
+            y = g.transpose(y, (0, 1, 2, 4, 3))
+            y = g.reshape(y, [batch, h, w, mid])
+            y = g.dwconv(y, k=3, stride=stride, act="NONE")
+            y = g.conv(y, branch_out, k=1, act="NONE", groups=groups)
+            if stride == 2:
+                x = g.relu(g.concat([g.avgpool(x, (3, 3), 2, "SAME"), y], axis=3))
+            else:
+                x = g.add(y, x, act="RELU")
+            c_in = c_out
+    _, h, w, _ = g.meta[x][0]
+    x = g.avgpool(x, (h, w))
+    x = g.conv(x, classes, k=1, act="NONE")
+    g.output(g.reshape(x, [batch, classes]))
     return g.build()
 
 

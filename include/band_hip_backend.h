@@ -182,6 +182,14 @@ int bhx_time_subgraph(bhx_executor* e, int model_id, int worker_id, uint64_t uni
  * `reindex_params` is a bh_reindex_params (band_hip_kernels.h).  Tests compare
  * it with numpy without building a model around every map. */
 int bhx_cpu_reindex(const void* reindex_params);
+/* kernel symbols (static storage) of a prepared subgraph's launches in program
+ * order, up to cap; *n = the count.  Works on kCPU executors too. */
+int bhx_launch_kernels(bhx_executor* e, int model_id, int worker_id, uint64_t unit_mask, const char** out, int cap,
+                       int* n);
+/* CpuConvGrouped, the kCPU worker's host twin of bh_conv2d_grouped_i8, over
+ * host pointers: `grouped_params` is a bh_conv_grouped_params.  Refuses a
+ * group count that does not divide both channel counts. */
+int bhx_cpu_conv_grouped(const void* grouped_params);
 
 /* --- job batching (extension, backend/hip/job_batching.h) -------------
  * Not in the reference interface: Band runs one job per ExecuteSubgraph

@@ -14,6 +14,8 @@
  * `TfLiteModelExecutor::ExecuteSubgraph` (band/backend/tfl/model_executor.cc:249-255):
  *   bh_conv2d_i8      <- CONV_2D            (reference_integer_ops::ConvPerChannel,
  *                                            reference_ops::Conv uint8)
+ *   bh_conv2d_grouped_i8 <- CONV_2D whose filter has fewer input channels than the input
+ *                                            (the same two kernels, groups = in_c / filter_in_c)
  *   bh_dwconv2d_i8    <- DEPTHWISE_CONV_2D  (reference_integer_ops::DepthwiseConvPerChannel)
  *   bh_fc_i8          <- FULLY_CONNECTED    (reference_integer_ops::FullyConnected)
  *   bh_eltwise_i8     <- ADD / SUB / MUL    (reference_integer_ops::Add / Mul, sub.cc)
@@ -215,6 +217,24 @@ int bh_conv_group_i8(const bh_conv_group* g, bh_stream_t stream);
  * routed automatically (2: 256x128, 3: 128x256), 0 when the layer is too
  * small for it (conv_gemm_kernel then) */
 int bh_conv_gemm_big_config(long M, int N);
+
+/* Grouped CONV_2D (TFLite filter [out_c][k_h][k_w][in_c / groups]).  `conv`
+ * is the dense block with in_c / out_c the TOTAL channel counts; output
+ * channel c belongs to group c / (out_c / groups) and reads input channels
+ * [g * in_c / groups, (g + 1) * in_c / groups) only.  `weights` / bias_eff are
+ * bh_pack_conv_weights(w, signed, out_c, K_g, ...) on the geometry
+ * bh_conv_packed_geometry(out_c, K_g) with K_g = k_h * k_w * in_c / groups
+ * (one row per output channel; group g owns rows [g * ocg, (g + 1) * ocg)).
+ * groups must divide in_c and out_c.  Residual ADD, out_table, requant_fast
+ * and out_img_stride are the dense epilogue's.  conv.kernel_hint takes the
+ * BH_CONV_GROUPED_* values (anything else routes by shape). */
+typedef struct bh_conv_grouped_params {
+  bh_conv_params conv;
+  int32_t groups;
+} bh_conv_grouped_params;
+#define BH_CONV_GROUPED_AUTO 0
+#define BH_CONV_GROUPED_MFMA 1 /* conv_grouped_mfma_kernel, one 16-pixel tile per wave: the routed form */
+#define BH_CONV_GROUPED_MFMA_2 2 /* the same kernel, two 16-pixel tiles per wave (never routed by shape) */
 
 /* DEPTHWISE_CONV_2D.  weights: int8-domain [k_h][k_w][out_c] (TFLite layout
  * [1,kh,kw,oc] with XOR applied for uint8 filters).  Exact int32 math
@@ -496,6 +516,12 @@ int bh_conv2d_i8(const bh_conv_params* p, bh_stream_t s);
  * ("conv_mfma_kernel", "conv_xs_kernel", "conv_rows_kernel",
  * "conv_direct_kernel"); static storage.  Profiling attribution only. */
 const char* bh_conv2d_i8_kernel(const bh_conv_params* p);
+/* grouped CONV_2D (bh_conv_grouped_params); BH_EINVAL with bh_last_error set
+ * when groups does not divide the channel counts or a pointer is missing */
+int bh_conv2d_grouped_i8(const bh_conv_grouped_params* p, bh_stream_t s);
+/* Symbol bh_conv2d_grouped_i8 dispatches to ("conv_grouped_mfma_kernel"), ""
+ * for a block it would refuse; static storage */
+const char* bh_conv2d_grouped_i8_kernel(const bh_conv_grouped_params* p);
 int bh_dwconv2d_i8(const bh_dwconv_params* p, bh_stream_t s);
 /* Symbol of the kernel bh_dwconv2d_i8 dispatches these parameters to
  * ("dwconv3x3_run_kernel", "dwconv3x3_dot_kernel", "dwconv3x3_kernel",
