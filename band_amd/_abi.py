@@ -156,6 +156,19 @@ class ReindexParams(ctypes.Structure):
                 ("input", c_void_p), ("output", c_void_p)]
 
 
+BMM_AUTO, BMM_BYTES, BMM_NT1, BMM_NT4 = 0, 1, 2, 4
+BMM_READ_B128, BMM_READ_GATHER, BMM_READ_TR8 = 8, 16, 32
+
+
+class BatchMatMulParams(ctypes.Structure):
+    """bh_batch_matmul_params: operands by strides (elements); a batch stride of 0 broadcasts"""
+    _fields_ = [("batch", c_int32 * 2), ("m", c_int32), ("n", c_int32), ("k", c_int32),
+                ("lhs_bstride", ctypes.c_int64 * 2), ("rhs_bstride", ctypes.c_int64 * 2)] + [
+        (n, ctypes.c_int64) for n in ("lhs_row_stride", "lhs_k_stride", "rhs_k_stride", "rhs_col_stride")] + [
+        (n, c_int32) for n in ("lhs_zp", "rhs_zp", "out_zp", "mult", "shift", "requant_fast", "kernel_hint")] + [
+        (n, c_void_p) for n in ("lhs", "rhs", "out")]
+
+
 class ResizeBilinearU8Params(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("batch", "in_h", "in_w", "channels", "out_h", "out_w")] + [
         (n, c_void_p) for n in ("y_idx", "x_idx", "y_frac", "x_frac", "input", "output")]
@@ -270,6 +283,10 @@ KERNEL_SYMBOLS = {
     "bh_reindex_as": (c_int, [ctypes.POINTER(ReindexParams), c_int, c_void_p]),
     "bh_reindex_kernel": (ctypes.c_char_p, [ctypes.POINTER(ReindexParams)]),
     "bh_reindex_canonical": (c_int, [ctypes.POINTER(ReindexParams), ctypes.POINTER(ReindexParams)]),
+    "bh_batch_matmul_i8": (c_int, [ctypes.POINTER(BatchMatMulParams), c_void_p]),
+    "bh_batch_matmul_i8_kernel": (ctypes.c_char_p, [ctypes.POINTER(BatchMatMulParams)]),
+    "bh_batch_matmul_f32": (c_int, [ctypes.POINTER(BatchMatMulParams), c_void_p]),
+    "bh_batch_matmul_check": (c_int, [ctypes.POINTER(BatchMatMulParams), c_int]),
     "bh_softmax_i8": (c_int, [ctypes.POINTER(SoftmaxParams), c_void_p]),
     "bh_zero_insert": (c_int, [ctypes.POINTER(ZeroInsertParams), c_void_p]),
     "bh_conv2d_f32": (c_int, [ctypes.POINTER(ConvF32Params), c_void_p]),

@@ -83,6 +83,7 @@ _abi.BACKEND_SYMBOLS.update({
     "bhx_cpu_reindex": (c_int, [ctypes.POINTER(_abi.ReindexParams)]),
     "bhx_launch_kernels": (c_int, _KEY + [ctypes.POINTER(ctypes.c_char_p), c_int, ctypes.POINTER(c_int)]),
     "bhx_cpu_conv_grouped": (c_int, [ctypes.POINTER(_abi.ConvGroupedParams)]),
+    "bhx_cpu_batch_matmul": (c_int, [ctypes.POINTER(_abi.BatchMatMulParams), c_int]),
     "bhx_prepare_job_batches": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_uint64, c_int]),
     "bhx_max_job_batch": (c_int, _KEY + [ctypes.POINTER(c_int)]),
     "bhx_job_slot_view": (c_int, _KEY + [c_int, c_int, c_int, ctypes.POINTER(TensorInfo)]),

@@ -478,4 +478,14 @@ int bhx_cpu_conv_grouped(const void* grouped_params) {
   return 0;
 }
 
+int bhx_cpu_batch_matmul(const void* batch_matmul_params, int is_float32) {
+  const auto* p = static_cast<const bh_batch_matmul_params*>(batch_matmul_params);
+  if (bh_batch_matmul_check(p, is_float32 ? 4 : 1) != 0)
+    return Fail((std::string("CpuBatchMatMul: ") + bh_last_error()).c_str());
+  band::hip::CpuPool pool(1);
+  if (is_float32) band::hip::CpuBatchMatMulF32(*p, pool);
+  else band::hip::CpuBatchMatMul(*p, pool);
+  return 0;
+}
+
 }  // extern "C"

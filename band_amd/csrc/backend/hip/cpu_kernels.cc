@@ -910,5 +910,61 @@ bool CpuReindex(const bh_reindex_params& p) {
   return true;
 }
 
+// ---- BATCH_MATMUL: bh_batch_matmul_i8 / _f32's host twins --------------------
+// The same integer arithmetic unfolded - sum_k (a - z_l)(b - z_r), no row or
+// column sums - over (batch x row) blocks; each row gathers its operand row
+// once, each column of the slice is gathered once per block.
+
+namespace {
+template <typename T, typename Row>
+void BatchMatMulBlocks(const bh_batch_matmul_params& p, CpuPool& pool, Row&& row_fn) {
+  const long rows = static_cast<long>(p.batch[0]) * p.batch[1] * p.m;
+  const T* L = static_cast<const T*>(p.lhs);
+  const T* R = static_cast<const T*>(p.rhs);
+  pool.ParallelFor(rows, [&](long r0, long r1) {
+    std::vector<T> a(static_cast<size_t>(p.k)), bt(static_cast<size_t>(p.k) * p.n);
+    long staged = -1;  // the batch index whose rhs slice `bt` ([n][k]) holds
+    for (long r = r0; r < r1; ++r) {
+      const long b = r / p.m;
+      const int i = static_cast<int>(r - b * p.m);
+      const long bi0 = b / p.batch[1], bi1 = b - bi0 * p.batch[1];
+      if (b != staged) {
+        const T* rb = R + bi0 * p.rhs_bstride[0] + bi1 * p.rhs_bstride[1];
+        for (int j = 0; j < p.n; ++j)
+          for (int k = 0; k < p.k; ++k) bt[static_cast<size_t>(j) * p.k + k] = rb[k * p.rhs_k_stride + j * p.rhs_col_stride];
+        staged = b;
+      }
+      const T* la = L + bi0 * p.lhs_bstride[0] + bi1 * p.lhs_bstride[1] + i * p.lhs_row_stride;
+      for (int k = 0; k < p.k; ++k) a[k] = la[k * p.lhs_k_stride];
+      row_fn(a.data(), bt.data(), r);
+    }
+  });
+}
+}  // namespace
+
+void CpuBatchMatMul(const bh_batch_matmul_params& p, CpuPool& pool) {
+  int8_t* out = static_cast<int8_t*>(p.out);
+  BatchMatMulBlocks<int8_t>(p, pool, [&](const int8_t* a, const int8_t* bt, long r) {
+    for (int j = 0; j < p.n; ++j) {
+      const int8_t* b = bt + static_cast<size_t>(j) * p.k;
+      int32_t acc = 0;
+      for (int k = 0; k < p.k; ++k) acc += (static_cast<int32_t>(a[k]) - p.lhs_zp) * (static_cast<int32_t>(b[k]) - p.rhs_zp);
+      out[r * p.n + j] = static_cast<int8_t>(Clamp(Requant(acc, p.mult, p.shift) + p.out_zp, -128, 127));
+    }
+  });
+}
+
+void CpuBatchMatMulF32(const bh_batch_matmul_params& p, CpuPool& pool) {
+  float* out = static_cast<float*>(p.out);
+  BatchMatMulBlocks<float>(p, pool, [&](const float* a, const float* bt, long r) {
+    for (int j = 0; j < p.n; ++j) {
+      const float* b = bt + static_cast<size_t>(j) * p.k;
+      float acc = 0.f;
+      for (int k = 0; k < p.k; ++k) acc += a[k] * b[k];
+      out[r * p.n + j] = acc;
+    }
+  });
+}
+
 }  // namespace hip
 }  // namespace band

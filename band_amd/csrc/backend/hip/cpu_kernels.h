@@ -116,5 +116,12 @@ void CpuArgMinMax(const bh_argminmax_params& p, CpuPool& pool);
 // launcher would refuse.
 bool CpuReindex(const bh_reindex_params& p);
 
+// BATCH_MATMUL (bh_batch_matmul_params, validated by the caller): the host
+// twins of bh_batch_matmul_i8 - sum_k (a - z_l)(b - z_r) unfolded, TFLite's
+// two-step requantisation - and of bh_batch_matmul_f32 (a k-ordered float32
+// sum), over the pool by batch x row blocks
+void CpuBatchMatMul(const bh_batch_matmul_params& p, CpuPool& pool);
+void CpuBatchMatMulF32(const bh_batch_matmul_params& p, CpuPool& pool);
+
 }  // namespace hip
 }  // namespace band

@@ -142,10 +142,101 @@ inline void FloatActRange(int act, float* lo, float* hi) {
   *lo = act == 1 || act == 3 ? 0.f : (act == 2 ? -1.f : -inf);
   *hi = act == 3 ? 6.f : (act == 2 ? 1.f : inf);
 }
+// BATCH_MATMUL (int8 / float32): shapes, adj_x / adj_y and numpy-matmul
+// broadcasting of the leading dims resolved to the stride form of
+// bh_batch_matmul_params (pointers stay null) - the only place that does; the
+// support checks, the lowering, the host twin's caller and the job-batch rule
+// all come through here.  int8: one per-tensor (mult, shift) from
+// FullyConnectedMultiplier, the zero points of both operands and the output.
+// *batch_axis_ok: axis 0 of the output and of every non-constant operand is
+// the same matmul batch dim (rank >= 3, the output's rank) and a constant
+// operand broadcasts along it (lower rank, or a leading 1), so a job-batch
+// variant that scales axis 0 computes each job's product.  *why names what
+// was refused.
+inline bool BatchMatMulArgs(const TflModel& m, const TflOperator& op, bh_batch_matmul_params* p,
+                            const char** why = nullptr, bool* batch_axis_ok = nullptr) {
+  auto no = [&](const char* w) {
+    if (why) *why = w;
+    return false;
+  };
+  if (op.builtin != kTflBatchMatMul || op.inputs.size() < 2 || op.inputs[0] < 0 || op.inputs[1] < 0 ||
+      op.outputs.empty() || op.outputs[0] < 0)
+    return no("missing operands");
+  const TflTensor& l = m.tensors[op.inputs[0]];
+  const TflTensor& r = m.tensors[op.inputs[1]];
+  const TflTensor& o = m.tensors[op.outputs[0]];
+  if (l.type == DataType::kFloat32 && r.type == DataType::kInt8)
+    return no("hybrid BATCH_MATMUL (float32 lhs, int8 rhs)");
+  if (l.type != r.type || l.type != o.type) return no("BATCH_MATMUL operands and output differ in type");
+  if (l.type != DataType::kInt8 && l.type != DataType::kFloat32)
+    return no("BATCH_MATMUL: int8 and float32 only (no uint8, no int16)");
+  const bool i8 = l.type == DataType::kInt8;
+  if (i8 && (!HasQ(l) || !HasQ(r) || !HasQ(o))) return no("missing quantization");
+  const int rl = static_cast<int>(l.shape.size()), rr = static_cast<int>(r.shape.size());
+  const int ro = static_cast<int>(o.shape.size());
+  if (rl < 2 || rr < 2 || rl > 4 || rr > 4) return no("BATCH_MATMUL operands must have rank 2 to 4");
+  if (ro != std::max(rl, rr)) return no("BATCH_MATMUL output rank differs from the operands' larger rank");
+  const bool adj_x = op.options.valid() && op.options.Int8(0, 0) != 0;
+  const bool adj_y = op.options.valid() && op.options.Int8(1, 0) != 0;
+  const int64_t la = l.shape[rl - 2], lb = l.shape[rl - 1], ra = r.shape[rr - 2], rb = r.shape[rr - 1];
+  const int64_t M = adj_x ? lb : la, K = adj_x ? la : lb;
+  const int64_t Kr = adj_y ? rb : ra, N = adj_y ? ra : rb;
+  if (M <= 0 || N <= 0 || K <= 0) return no("empty matrix");
+  if (K != Kr) return no("BATCH_MATMUL: mismatched K");
+  if (i8 && K > 32767) return no("BATCH_MATMUL: K > 32767");
+  int64_t bl[2] = {1, 1}, br[2] = {1, 1}, bo[2] = {1, 1};
+  for (int d = 0; d < rl - 2; ++d) bl[2 - (rl - 2) + d] = l.shape[d];
+  for (int d = 0; d < rr - 2; ++d) br[2 - (rr - 2) + d] = r.shape[d];
+  for (int d = 0; d < ro - 2; ++d) bo[2 - (ro - 2) + d] = o.shape[d];
+  for (int d = 0; d < 2; ++d) {
+    const int64_t want = std::max(bl[d], br[d]);
+    if ((bl[d] != want && bl[d] != 1) || (br[d] != want && br[d] != 1))
+      return no("BATCH_MATMUL: batch dims neither equal nor 1");
+    if (bo[d] != want || want <= 0) return no("BATCH_MATMUL output shape mismatch");
+  }
+  if (o.shape[ro - 2] != M || o.shape[ro - 1] != N) return no("BATCH_MATMUL output shape mismatch");
+  // the launchers' limits (bh_batch_matmul_check), so that a refusal surfaces here and not at prepare time
+  if (bo[0] > 65535 || bo[1] > 65535) return no("BATCH_MATMUL: a batch dim above 65535");
+  if (l.num_elements() > 0x7fffffffu || r.num_elements() > 0x7fffffffu || o.num_elements() > 0x7fffffffu)
+    return no("BATCH_MATMUL: a tensor of 2^31 or more elements");
+  if (p) {
+    *p = bh_batch_matmul_params{};
+    p->batch[0] = static_cast<int32_t>(bo[0]);
+    p->batch[1] = static_cast<int32_t>(bo[1]);
+    p->m = static_cast<int32_t>(M);
+    p->n = static_cast<int32_t>(N);
+    p->k = static_cast<int32_t>(K);
+    p->lhs_bstride[1] = bl[1] == 1 ? 0 : la * lb;
+    p->lhs_bstride[0] = bl[0] == 1 ? 0 : bl[1] * la * lb;
+    p->rhs_bstride[1] = br[1] == 1 ? 0 : ra * rb;
+    p->rhs_bstride[0] = br[0] == 1 ? 0 : br[1] * ra * rb;
+    p->lhs_row_stride = adj_x ? 1 : lb;
+    p->lhs_k_stride = adj_x ? lb : 1;
+    p->rhs_k_stride = adj_y ? 1 : rb;
+    p->rhs_col_stride = adj_y ? rb : 1;
+    p->requant_fast = -1;  // the launcher decides
+    if (i8) {
+      p->lhs_zp = Zp(l);
+      p->rhs_zp = Zp(r);
+      p->out_zp = Zp(o);
+      FullyConnectedMultiplier(Scale(l), Scale(r), Scale(o), &p->mult, &p->shift);
+    }
+  }
+  if (batch_axis_ok) {
+    auto rides = [&](const TflTensor& t, int rank) {
+      if (t.is_const()) return rank < ro || t.shape[0] == 1;
+      return rank == ro;
+    };
+    *batch_axis_ok = ro >= 3 && rides(l, rl) && rides(r, rr);
+  }
+  return true;
+}
+
 inline bool IsFloatOp(const TflModel& m, const TflOperator& op) {
   if (op.inputs.empty() || op.inputs[0] < 0) return false;
   const DataType t = m.tensors[op.inputs[0]].type;
   switch (op.builtin) {
+    case kTflBatchMatMul:
     case kTflConv2D: case kTflDepthwiseConv2D: case kTflFullyConnected: case kTflAdd: case kTflSub: case kTflMul:
     case kTflAveragePool2D: case kTflMaxPool2D: case kTflRelu: case kTflRelu6: case kTflReluN1To1:
     case kTflLogistic: case kTflSoftmax: case kTflSquaredDifference: case kTflRsqrt:
@@ -205,6 +296,10 @@ inline bool FloatSupports(const TflModel& m, const TflOperator& op, std::string*
       return in.shape.size() == 4 ? true : no("4-D only");
     case kTflSoftmax:
       return !in.shape.empty() ? true : no("rank >= 1");
+    case kTflBatchMatMul: {
+      const char* w = "";
+      return BatchMatMulArgs(m, op, nullptr, &w) ? true : no(w);
+    }
     default:
       return true;  // RELU / RELU6 / RELU_N1_TO_1 / LOGISTIC / RSQRT
   }

@@ -612,6 +612,8 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
       L->src = in_ptr;
       L->dst = out_ptr;
       return absl::OkStatus();
+    case kTflBatchMatMul:
+      return LowerBatchMatMul(model, oi, in_ptr, out_ptr, sg, L);
     default: {  // RELU / RELU6 / RELU_N1_TO_1 / LOGISTIC / RSQRT
       L->kind = Launch::kUnaryF32;
       L->kernel = "unary_f32_kernel";
@@ -750,6 +752,35 @@ absl::Status HipModelExecutor::LowerReindex(const HipModel& model, int oi, Prepa
     }
     sg->launches.push_back(L);
   }
+  return absl::OkStatus();
+}
+
+// BATCH_MATMUL (int8 / float32): one launch over BatchMatMulArgs' stride form.
+// Both operands may be activations; a constant one is uploaded as it is (no
+// repacking).  The launch joins no chain, block or conv group and takes no
+// epilogue fold.
+absl::Status HipModelExecutor::LowerBatchMatMul(const HipModel& model, int oi, void* lhs_ptr, void* out_ptr,
+                                                PreparedSubgraph* sg, Launch* L) {
+  const TflModel& d = model.desc();
+  const TflOperator& op = d.ops[oi];
+  const char* why = "";
+  bh_batch_matmul_params& p = L->bmm;
+  if (!BatchMatMulArgs(d, op, &p, &why)) return absl::InternalError(std::string("unsupported BATCH_MATMUL: ") + why);
+  void* rhs_ptr = nullptr;
+  RETURN_STATUS_IF(DevicePtr(model, op.inputs[1], sg, &rhs_ptr));
+  p.lhs = lhs_ptr;
+  p.rhs = rhs_ptr;
+  p.out = out_ptr;
+  const bool f32 = d.tensors[op.inputs[0]].type == DataType::kFloat32;
+  if (bh_batch_matmul_check(&p, f32 ? 4 : 1) != 0) return absl::InternalError(std::string("BATCH_MATMUL: ") + bh_last_error());
+  const bool cpu = device_flag_ == DeviceFlag::kCPU;
+  L->kind = f32 ? Launch::kBatchMatMulF32 : Launch::kBatchMatMul;
+  L->kernel = f32 ? (cpu ? "batch_matmul_f32_host" : "bmm_f32_kernel")
+                  : (cpu ? "batch_matmul_host" : bh_batch_matmul_i8_kernel(&p));
+  L->alg_ops = 2.0 * p.batch[0] * p.batch[1] * p.m * p.n * p.k;
+  // operands and output once each; a broadcast operand holds fewer bytes than the batch reads
+  L->alg_bytes = static_cast<double>(meta_[op.inputs[0]]->bytes + meta_[op.outputs[0]]->bytes) +
+                 static_cast<double>(GetDataTypeBytes(d.tensors[op.inputs[1]].type) * d.tensors[op.inputs[1]].num_elements());
   return absl::OkStatus();
 }
 
@@ -1061,6 +1092,8 @@ absl::Status HipModelExecutor::Lower(const HipModel& model, int oi, PreparedSubg
     L.kind = Launch::kArgMinMax;
     L.kernel = cpu ? "argminmax_host" : bh_argminmax_kernel(&p);
     L.alg_bytes = static_cast<double>(meta_[op.inputs[0]]->bytes + meta_[op.outputs[0]]->bytes);
+  } else if (op.builtin == kTflBatchMatMul) {
+    RETURN_STATUS_IF(LowerBatchMatMul(model, oi, in_ptr, out_ptr, sg, &L));
   } else if (op.builtin == kTflTransposeConv) {
     RETURN_STATUS_IF(LowerTransposeConv(model, oi, out_ptr, ckey, sg, &L));
   } else if (op.builtin != kTflReshape && op.builtin != kTflSqueeze) {

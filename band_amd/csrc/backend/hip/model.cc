@@ -70,6 +70,20 @@ absl::Status HipModel::CloneWithJobBatch(int batch, std::unique_ptr<HipModel>* o
       if (ex::ArgMinMaxArgs(desc_, op, &outer, &len, &inner, &out_bytes, &axis) && axis == 0)
         return absl::InternalError(std::string("job batching: ") + TflBuiltinName(op.builtin) + " on the batch axis");
     }
+    if (op.builtin == kTflBatchMatMul) {
+      // axis 0 must be a matmul batch dim of the output and of every
+      // activation operand; a constant operand has to broadcast along it
+      bool batch_axis_ok = false;
+      if (ex::BatchMatMulArgs(desc_, op, nullptr, nullptr, &batch_axis_ok) && !batch_axis_ok) {
+        bool rank2 = false;
+        for (int k = 0; k < 2; ++k) {
+          const TflTensor& t = desc_.tensors[op.inputs[k]];
+          rank2 = rank2 || (!t.is_const() && t.shape.size() == 2);
+        }
+        return absl::InternalError(rank2 ? "job batching: BATCH_MATMUL with a rank-2 activation operand"
+                                         : "job batching: BATCH_MATMUL operand does not broadcast along the batch axis");
+      }
+    }
     if (ex::IsReindexOp(op.builtin)) {
       // a map may touch axis 0 only as the full range: no TRANSPOSE with
       // perm[0] != 0, no SPLIT / SPLIT_V on axis 0, no slice of part of it

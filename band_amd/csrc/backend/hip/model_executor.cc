@@ -202,6 +202,10 @@ bool HipModelExecutor::GpuSupports(const TflModel& m, const TflOperator& op, std
         if (!ReindexArgs(m, op, k, &map, &w)) return no(w);
       return true;
     }
+    case kTflBatchMatMul: {
+      const char* w = "";
+      return BatchMatMulArgs(m, op, nullptr, &w) ? true : no(w);
+    }
     case kTflSoftmax:
       if (!IsQ8(in.type) || out.type != in.type || !HasQ(in) || !HasQ(out) || in.shape.empty())
         return no("only 8-bit quantized in and out");
@@ -643,6 +647,8 @@ absl::Status HipModelExecutor::EnqueueLaunch(const Launch& l) {
     case Launch::kArgMinMax: rc = bh_argminmax(&l.argmm, stream_); break;
     case Launch::kResizeArgMinMax: rc = bh_resize_bilinear_argminmax_i8(&l.rzarg, stream_); break;
     case Launch::kReindex: rc = bh_reindex(&l.reindex, stream_); break;
+    case Launch::kBatchMatMul: rc = bh_batch_matmul_i8(&l.bmm, stream_); break;
+    case Launch::kBatchMatMulF32: rc = bh_batch_matmul_f32(&l.bmm, stream_); break;
     case Launch::kMean: {
       bh_mean_params q{};
       q.outer = l.mean.outer;
@@ -845,6 +851,8 @@ absl::Status HipModelExecutor::ExecuteOnHost(PreparedSubgraph* sg) {
       case Launch::kMean: CpuMean(l.mean, pool); break;
       case Launch::kArgMinMax: CpuArgMinMax(l.argmm, pool); break;
       case Launch::kReindex: CpuReindex(l.reindex); break;
+      case Launch::kBatchMatMul: CpuBatchMatMul(l.bmm, pool); break;
+      case Launch::kBatchMatMulF32: CpuBatchMatMulF32(l.bmm, pool); break;
       default: return absl::InternalError(std::string("no host implementation of ") + l.kernel);
     }
   }

@@ -50,7 +50,9 @@ struct Launch {
     kArgMinMax,      // ARG_MAX / ARG_MIN
     kResizeArgMinMax, // RESIZE_BILINEAR int8 -> ARG_MAX / ARG_MIN over channels, one launch (FuseGlue; kGPU)
     kReindex,         // one output of TRANSPOSE / STRIDED_SLICE / SLICE / SPLIT / SPLIT_V / SPACE_TO_DEPTH / DEPTH_TO_SPACE
-    kConvGrouped      // grouped CONV_2D: `conv` with the total channel counts + conv_groups (never chained / grouped / blocked)
+    kConvGrouped,     // grouped CONV_2D: `conv` with the total channel counts + conv_groups (never chained / grouped / blocked)
+    kBatchMatMul,     // BATCH_MATMUL int8 (BatchMatMulArgs -> `bmm`; never chained / grouped / blocked, no epilogue folds)
+    kBatchMatMulF32   // BATCH_MATMUL float32
   } kind;
   int op_index = -1;
   int out_tensor = -1;  // tensor this launch materialises (after epilogue fusions)
@@ -85,6 +87,7 @@ struct Launch {
   bh_argminmax_params argmm{};
   bh_resize_argminmax_params rzarg{};
   bh_reindex_params reindex{};
+  bh_batch_matmul_params bmm{};
   const void* table = nullptr;  // kLutU8 / kLutF32: 256-entry device table
   long count = 0;               // kLut* / kQuantF32: elements
   float q_scale = 0.f;          // kQuantF32
@@ -248,6 +251,9 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   // that is the identity lowers as RESHAPE does (a kCopy, dropped when both
   // sides share a slot)
   absl::Status LowerReindex(const HipModel& model, int op_index, PreparedSubgraph* sg);
+  // BATCH_MATMUL int8 / float32 (BatchMatMulArgs): one kBatchMatMul / kBatchMatMulF32 launch
+  absl::Status LowerBatchMatMul(const HipModel& model, int op_index, void* lhs_ptr, void* out_ptr,
+                                PreparedSubgraph* sg, Launch* L);
   // TFLite_Detection_PostProcess on the device: one bh_detection_postprocess launch
   absl::Status LowerDetectionGpu(const HipModel& model, int op_index, PreparedSubgraph* sg, Launch* l);
   // op_index is an 8-bit DEQUANTIZE whose float output only the device

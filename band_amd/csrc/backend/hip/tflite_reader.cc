@@ -54,6 +54,7 @@ const char* TflBuiltinName(int c) {
     case kTflSplit: return "SPLIT";
     case kTflSlice: return "SLICE";
     case kTflSplitV: return "SPLIT_V";
+    case kTflBatchMatMul: return "BATCH_MATMUL";
     default: return "UNKNOWN";
   }
 }

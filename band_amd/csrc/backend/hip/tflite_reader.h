@@ -34,6 +34,8 @@ enum TflBuiltin : int {
   // DepthToSpaceOptions: slot 0 block_size; TRANSPOSE and SLICE have no fields
   kTflDepthToSpace = 5, kTflSpaceToDepth = 26, kTflTranspose = 39, kTflStridedSlice = 45, kTflSplit = 49,
   kTflSlice = 65, kTflSplitV = 102,
+  // BatchMatMulOptions: slots 0-2 adj_x, adj_y, asymmetric_quantize_inputs
+  kTflBatchMatMul = 126,
 };
 
 const char* TflBuiltinName(int code);

@@ -31,6 +31,7 @@ OPTION_FIELDS = {
     44: [],                                                                     # Slice
     79: [(0, "i")],                                                             # SplitV
     94: [(0, "i")],                                                             # DepthToSpace
+    101: [(0, "b"), (1, "b"), (2, "b")],                                        # BatchMatMul
 }
 
 

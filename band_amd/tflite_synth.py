@@ -18,15 +18,18 @@ import numpy as np
 # schema enums
 T_FLOAT32, T_FLOAT16, T_INT32, T_UINT8, T_INT8 = 0, 1, 2, 3, 9
 T_INT64 = 4
+T_INT16 = 7
 NP_TO_SCHEMA = {np.dtype(np.float32): T_FLOAT32, np.dtype(np.float16): T_FLOAT16, np.dtype(np.int32): T_INT32,
-                np.dtype(np.uint8): T_UINT8, np.dtype(np.int8): T_INT8, np.dtype(np.int64): T_INT64}
+                np.dtype(np.uint8): T_UINT8, np.dtype(np.int8): T_INT8, np.dtype(np.int64): T_INT64,
+                np.dtype(np.int16): T_INT16}
 ACT = {"NONE": 0, "RELU": 1, "RELU_N1_TO_1": 2, "RELU6": 3}
 OPC = dict(ADD=0, AVERAGE_POOL_2D=1, CONCATENATION=2, CONV_2D=3, DEPTHWISE_CONV_2D=4,
            FULLY_CONNECTED=9, LOGISTIC=14, MAX_POOL_2D=17, MUL=18, RESHAPE=22,
            RESIZE_BILINEAR=23, SOFTMAX=25, CUSTOM=32, PAD=34, SUB=41, QUANTIZE=114,
            DEQUANTIZE=6, RELU=19, RELU_N1_TO_1=20, RELU6=21, PADV2=60, RESIZE_NEAREST_NEIGHBOR=97,
            TRANSPOSE_CONV=67, ARG_MAX=56, ARG_MIN=79,
-           DEPTH_TO_SPACE=5, SPACE_TO_DEPTH=26, TRANSPOSE=39, STRIDED_SLICE=45, SPLIT=49, SLICE=65, SPLIT_V=102)
+           DEPTH_TO_SPACE=5, SPACE_TO_DEPTH=26, TRANSPOSE=39, STRIDED_SLICE=45, SPLIT=49, SLICE=65, SPLIT_V=102,
+           BATCH_MATMUL=126)
 # BuiltinOptions union indices
 OPT = dict(Conv2DOptions=1, DepthwiseConv2DOptions=2, Pool2DOptions=5, FullyConnectedOptions=8,
            SoftmaxOptions=9, ConcatenationOptions=10, AddOptions=11, ReshapeOptions=17,
@@ -34,7 +37,9 @@ OPT = dict(Conv2DOptions=1, DepthwiseConv2DOptions=2, Pool2DOptions=5, FullyConn
            DequantizeOptions=38, PadV2Options=43, TransposeConvOptions=49, ResizeNearestNeighborOptions=74,
            QuantizeOptions=89, ArgMaxOptions=40, ArgMinOptions=57,
            SpaceToDepthOptions=19, TransposeOptions=26, StridedSliceOptions=32, SplitOptions=35, SliceOptions=44,
-           SplitVOptions=79, DepthToSpaceOptions=94)
+           SplitVOptions=79, DepthToSpaceOptions=94,
+           # written from memory of schema.fbs; the C++ reader never keys on the union number
+           BatchMatMulOptions=101)
 
 
 # ---------------------------------------------------------------------------
@@ -300,6 +305,20 @@ def act_options(act="NONE"):
     return Table().set(0, "b", ACT[act])
 
 
+def bmm_options(adj_x=False, adj_y=False, asymmetric_quantize_inputs=False):
+    """BatchMatMulOptions: adj_x, adj_y, asymmetric_quantize_inputs (fields 0-2)"""
+    return (Table().set(0, "b", int(adj_x)).set(1, "b", int(adj_y)).set(2, "b", int(asymmetric_quantize_inputs)))
+
+
+def _bmm_shape(sa, sb, adj_x, adj_y):
+    """(output shape, K) of BATCH_MATMUL on shapes sa, sb: numpy matmul after the adjoints"""
+    ma = list(sa[-2:])[::-1] if adj_x else list(sa[-2:])
+    mb_ = list(sb[-2:])[::-1] if adj_y else list(sb[-2:])
+    assert ma[1] == mb_[0], "BATCH_MATMUL: K differs"
+    lead = np.broadcast_shapes(tuple(sa[:-2]), tuple(sb[:-2]))
+    return [int(v) for v in lead] + [ma[0], mb_[1]], ma[1]
+
+
 class _ReindexOps:
     """The re-indexing ops of QGraph and FGraph: TRANSPOSE, STRIDED_SLICE,
     SLICE, SPLIT, SPLIT_V, SPACE_TO_DEPTH, DEPTH_TO_SPACE.  They draw nothing
@@ -530,7 +549,10 @@ class QGraph(_ReindexOps):
         self.mb.op("RESHAPE", [x, st], [y], OPT["ReshapeOptions"], Table().set(0, "o", Vec("i", list(shape))))
         return y
 
-    def fully_connected(self, x, units, act="NONE"):
+    def fully_connected(self, x, units, act="NONE", keep_num_dims=False, out_scale=None):
+        """FULLY_CONNECTED; keep_num_dims keeps the input's leading dims
+        ([1, T, C] -> [1, T, units]) instead of flattening them to rows;
+        out_scale overrides the output scale"""
         shp, s_in, _ = self.meta[x]
         depth = shp[-1]
         rows = int(np.prod(shp)) // depth
@@ -539,11 +561,29 @@ class QGraph(_ReindexOps):
         ws = np.array([np.exp(self.rng.uniform(np.log(1e-3), np.log(2e-2)))], np.float32)
         wzp = 0 if self.dtype == np.int8 else int(self.rng.integers(125, 132))
         s_out, zp = self._out_q(act, s_in)
+        if out_scale is not None:
+            s_out = float(out_scale)
         ws = np.array([40.0 * s_out / (s_in * np.sqrt(depth) * 45.0 * 73.0)], np.float32)
         wt = self.mb.tensor(self._name("fc_weights"), [units, depth], self.dtype, scale=ws, zero_point=[wzp], data=w)
         bt = self._bias(units, s_in, ws, depth)
-        y = self.act_tensor([rows, units], s_out, zp)
-        self.mb.op("FULLY_CONNECTED", [x, wt, bt], [y], OPT["FullyConnectedOptions"], act_options(act))
+        y = self.act_tensor(list(shp[:-1]) + [units] if keep_num_dims else [rows, units], s_out, zp)
+        opt = act_options(act)
+        if keep_num_dims:
+            opt.set(2, "b", 1)
+        self.mb.op("FULLY_CONNECTED", [x, wt, bt], [y], OPT["FullyConnectedOptions"], opt)
+        return y
+
+    def batch_matmul(self, a, b, adj_x=False, adj_y=False, out_scale=None, out_zp=None):
+        """BATCH_MATMUL of two activations (numpy matmul over the last two
+        dims after adj_x / adj_y, leading dims broadcast).  The default output
+        scale puts sum_k (a - z_a)(b - z_b) of ~45-LSB operands ~32 output
+        LSBs wide."""
+        sa, s_a, _ = self.meta[a]
+        sb, s_b, _ = self.meta[b]
+        shape, K = _bmm_shape(sa, sb, adj_x, adj_y)
+        s_out = float(out_scale) if out_scale is not None else float(s_a * s_b * np.sqrt(K) * 45.0 * 45.0 / 32.0)
+        y = self.act_tensor(shape, s_out, self._act_zp() if out_zp is None else out_zp)
+        self.mb.op("BATCH_MATMUL", [a, b], [y], OPT["BatchMatMulOptions"], bmm_options(adj_x, adj_y))
         return y
 
     # --- glue ops ------------------------------------------------------------
@@ -793,14 +833,24 @@ class FGraph(_ReindexOps):
         self.mb.op("RESHAPE", [x, st], [y], OPT["ReshapeOptions"], Table().set(0, "o", Vec("i", list(shape))))
         return y
 
-    def fully_connected(self, x, units, act="NONE"):
+    def fully_connected(self, x, units, act="NONE", keep_num_dims=False, gain=1.0):
+        """`gain` scales the weights' standard deviation (an attention block's 1 / sqrt(D) folded into Q)"""
         shp = self.meta[x][0]
         depth = shp[-1]
         rows = int(np.prod(shp)) // depth
-        wt = self._const(self.rng.normal(0, np.sqrt(1.0 / depth), (units, depth)), "fc_weights")
+        wt = self._const(self.rng.normal(0, gain * np.sqrt(1.0 / depth), (units, depth)), "fc_weights")
         bt = self._const(self.rng.normal(0, 0.05, units), "fc_bias")
-        y = self._act([rows, units])
-        self.mb.op("FULLY_CONNECTED", [x, wt, bt], [y], OPT["FullyConnectedOptions"], act_options(act))
+        y = self._act(list(shp[:-1]) + [units] if keep_num_dims else [rows, units])
+        opt = act_options(act)
+        if keep_num_dims:
+            opt.set(2, "b", 1)
+        self.mb.op("FULLY_CONNECTED", [x, wt, bt], [y], OPT["FullyConnectedOptions"], opt)
+        return y
+
+    def batch_matmul(self, a, b, adj_x=False, adj_y=False, out_scale=None, out_zp=None):
+        shape, _ = _bmm_shape(self.meta[a][0], self.meta[b][0], adj_x, adj_y)
+        y = self._act(shape)
+        self.mb.op("BATCH_MATMUL", [a, b], [y], OPT["BatchMatMulOptions"], bmm_options(adj_x, adj_y))
         return y
 
     def concat(self, xs, axis=3):
@@ -933,6 +983,65 @@ def shufflenet_v1(dtype=np.int8, seed=5, size=224, groups=3, width=1.0, batch=1,
 # BASELINE C3 mix: detection / segmentation / pose heads on MobileNet trunks
 # (synthetic weights, 224x224 inputs - "synthetic 224x224 batches", §8(d))
 # ---------------------------------------------------------------------------
+def _attention(g, x, heads):
+    """One multi-head self-attention block on x [B, T, C] (no LayerNorm): Q, K, V
+    projections, per-head softmax(Q K^T / sqrt(D)) V, output projection,
+    residual ADD.  The float model's 1 / sqrt(D) leaves no op: it is folded
+    into the Q projection (its output scale, so its filter scale, is the
+    input's over sqrt(D); the fp16 model scales the Q weights), and the scores'
+    scale then stands for Q K^T / sqrt(D)."""
+    b, t, c = g.meta[x][0]
+    d = c // heads
+    assert d * heads == c, "heads must divide dim"
+    quant = isinstance(g, QGraph)
+    s_in = g.meta[x][1]
+    if quant:
+        q = g.fully_connected(x, c, keep_num_dims=True, out_scale=s_in / np.sqrt(d))
+    else:
+        q = g.fully_connected(x, c, keep_num_dims=True, gain=1.0 / np.sqrt(d))
+    k = g.fully_connected(x, c, keep_num_dims=True)
+    v = g.fully_connected(x, c, keep_num_dims=True)
+    q, k, v = [g.transpose(g.reshape(z, [b, t, heads, d]), (0, 2, 1, 3)) for z in (q, k, v)]
+    scores = g.batch_matmul(q, k, adj_y=True)            # [B, H, T, T]
+    p = g.softmax(scores, beta=1.0)                      # scale 1 / 256, zero point -128
+    # a row of P sums to ~256 LSBs, so at V's scale the context is V's weighted mean
+    ctx = g.batch_matmul(p, v, out_scale=g.meta[v][1] if quant else None)  # [B, H, T, D]
+    ctx = g.reshape(g.transpose(ctx, (0, 2, 1, 3)), [b, t, c])
+    y = g.fully_connected(ctx, c, keep_num_dims=True)
+    return g.add(y, x)
+
+
+def attention_block(dtype=np.int8, seed=6, tokens=196, dim=192, heads=3, batch=1):
+    """One self-attention block on [batch, tokens, dim]: three FULLY_CONNECTED
+    (keep_num_dims), RESHAPE / TRANSPOSE to [batch, heads, tokens, dim / heads],
+    BATCH_MATMUL(adj_y) -> SOFTMAX -> BATCH_MATMUL, TRANSPOSE / RESHAPE back,
+    FULLY_CONNECTED, ADD with the input.  dtype float32 (or float16) builds the
+    fp16-constant float model.  LayerNorm is left out (its int8 MEAN over
+    channels / SQUARED_DIFFERENCE / RSQRT chain is not lowered yet)."""
+    if np.dtype(dtype) in (np.dtype(np.float32), np.dtype(np.float16)):
+        g = FGraph(seed, "attention_block_f32")
+    else:
+        g = QGraph(dtype, seed, "attention_block_%s" % np.dtype(dtype).name)
+    x = g.input([batch, tokens, dim], scale=0.05)
+    g.output(_attention(g, x, heads))
+    return g.build()
+
+
+def vit_tiny(dtype=np.int8, seed=7, size=224, dim=192, heads=3, blocks=2, batch=1):
+    """ViT-Tiny's front: a 16 x 16 stride-16 patch CONV_2D, RESHAPE to tokens
+    [batch, (size / 16)^2, dim] and `blocks` attention blocks.  No class token,
+    no position embedding, no MLP and no LayerNorm (see attention_block)."""
+    g = QGraph(dtype, seed, "vit_tiny_%s" % np.dtype(dtype).name)
+    x = g.input([batch, size, size, 3], scale=0.05)
+    y = g.conv(x, dim, k=16, stride=16, act="NONE", padding="VALID")
+    n = (size // 16) ** 2
+    y = g.reshape(y, [batch, n, dim])
+    for _ in range(blocks):
+        y = _attention(g, y, heads)
+    g.output(y)
+    return g.build()
+
+
 def _mnv2_trunk(g, x, out_stride=32, tap_expansion_at=None):
     """MobileNetV2 feature extractor.  out_stride 16 turns the last stride-2
     stage into stride 1 with dilation 2 (DeepLab).  Returns (features, taps):

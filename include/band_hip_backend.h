@@ -190,6 +190,11 @@ int bhx_launch_kernels(bhx_executor* e, int model_id, int worker_id, uint64_t un
  * host pointers: `grouped_params` is a bh_conv_grouped_params.  Refuses a
  * group count that does not divide both channel counts. */
 int bhx_cpu_conv_grouped(const void* grouped_params);
+/* CpuBatchMatMul / CpuBatchMatMulF32, the kCPU worker's host twins of
+ * bh_batch_matmul_i8 / bh_batch_matmul_f32, over host pointers:
+ * `batch_matmul_params` is a bh_batch_matmul_params.  Refuses what the
+ * launchers refuse (bh_batch_matmul_check). */
+int bhx_cpu_batch_matmul(const void* batch_matmul_params, int is_float32);
 
 /* --- job batching (extension, backend/hip/job_batching.h) -------------
  * Not in the reference interface: Band runs one job per ExecuteSubgraph

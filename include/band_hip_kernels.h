@@ -36,6 +36,8 @@
  *   bh_resize_bilinear_argminmax_i8 <- RESIZE_BILINEAR int8 -> ARG_MAX / ARG_MIN over channels, fused
  *   bh_reindex        <- TRANSPOSE, STRIDED_SLICE, SLICE, SPLIT, SPLIT_V, SPACE_TO_DEPTH,
  *                        DEPTH_TO_SPACE (one launch per output; numpy's indexing semantics)
+ *   bh_batch_matmul_i8 / bh_batch_matmul_f32 <- BATCH_MATMUL int8 / float32 (the arithmetic of
+ *                        reference_integer_ops::FullyConnected without a bias, per batch slice)
  *   bh_detection_postprocess <- TFLite_Detection_PostProcess (custom; detection_postprocess.cc,
  *                        fast NMS, one class per detection)
  *   (HARD_SWISH 8-bit runs as a bh_lut_u8 table of reference_ops::HardSwish)
@@ -719,6 +721,49 @@ int bh_reindex_canonical(const bh_reindex_params* p, bh_reindex_params* canonica
  * reindex_gather_kernel, which takes any map, whatever bh_reindex would pick
  * (tools/reindex_profile.py times the forms side by side); 0 is bh_reindex. */
 int bh_reindex_as(const bh_reindex_params* p, int gather, bh_stream_t s);
+
+/* BATCH_MATMUL: out[b0, b1] = lhs[b0, b1] x rhs[b0, b1], an [m, k] by [k, n]
+ * product per batch index; both operands may be activations.  The output is
+ * dense [batch[0], batch[1], m, n].  An operand is given by strides (in
+ * elements), so a transposed (adj_x / adj_y) or broadcast (batch stride 0)
+ * operand is data: exactly one of an operand's two matrix strides is 1 (both
+ * may be when one of its extents is 1).
+ *   int8 (bh_batch_matmul_i8, bmm_mfma_kernel):
+ *     out = clamp(MBQM(sum_k (lhs - lhs_zp)(rhs - rhs_zp), mult, shift) + out_zp, -128, 127)
+ *     with one per-tensor (mult, shift); k <= 32767.  requant_fast: 0 the
+ *     two-step form, 1 / -1 the single-step form where
+ *     bh_conv_requant_fast_ok(&mult, &shift, 1, k, 0) holds (else two-step).
+ *   float32 (bh_batch_matmul_f32, bmm_f32_kernel): the plain float32 sum; the
+ *     quantisation fields are ignored.
+ * Refused (BH_EINVAL, bh_last_error names the launcher and the reason): null
+ * pointers, non-positive extents, a batch dim above 65535, k above the limit,
+ * negative strides, an operand without exactly one unit stride, 2^31 or more
+ * elements in a tensor.  No scratch, no atomics. */
+#define BH_BMM_AUTO 0
+/* kernel_hint bits (parity tests, A-B timing) */
+#define BH_BMM_BYTES 1 /* 1-byte fragment units whatever the alignment */
+#define BH_BMM_NT1 2   /* one 16-column tile per wave whatever the grid */
+#define BH_BMM_NT4 4   /* four 16-column tiles per wave whatever the grid */
+/* the transposed read of a K-strided (staged) operand */
+#define BH_BMM_READ_B128 8    /* transposing LDS writes, one ds_read_b128 */
+#define BH_BMM_READ_GATHER 16 /* row-major LDS image, 16 byte reads */
+#define BH_BMM_READ_TR8 32    /* row-major LDS image, two ds_read_b64_tr_b8 */
+typedef struct bh_batch_matmul_params {
+  int32_t batch[2], m, n, k;
+  int64_t lhs_bstride[2], rhs_bstride[2]; /* 0 = broadcast */
+  int64_t lhs_row_stride, lhs_k_stride;
+  int64_t rhs_k_stride, rhs_col_stride;
+  int32_t lhs_zp, rhs_zp, out_zp, mult, shift, requant_fast, kernel_hint;
+  const void* lhs;
+  const void* rhs;
+  void* out;
+} bh_batch_matmul_params;
+int bh_batch_matmul_i8(const bh_batch_matmul_params* p, bh_stream_t s);
+/* "bmm_mfma_kernel", or "" for parameters bh_batch_matmul_i8 refuses; static storage */
+const char* bh_batch_matmul_i8_kernel(const bh_batch_matmul_params* p);
+int bh_batch_matmul_f32(const bh_batch_matmul_params* p, bh_stream_t s);
+/* the launchers' parameter checks alone (elem_bytes 1: int8, 4: float32); pure host */
+int bh_batch_matmul_check(const bh_batch_matmul_params* p, int elem_bytes);
 
 /* RESIZE_BILINEAR (int8) followed by ARG_MAX / ARG_MIN over the channel axis
  * as one launch (resize_bilinear_argminmax_kernel): the resized tensor is
