@@ -8,6 +8,103 @@ namespace hip {
 
 using namespace ex;
 
+namespace {
+
+// what an int8 / uint8 conv's epilogue needs: per-channel multipliers, the
+// clamp, the zero points in the kernels' int8 domain and the bias
+struct ConvQuant {
+  std::vector<int32_t> mult, shift;
+  int32_t amin, amax, in_zp, w_zp;
+  const int32_t* bias;
+};
+
+ConvQuant QuantOf(const TflModel& d, const ConvGeometry& g, const TflTensor& out) {
+  const TflTensor& in = d.tensors[g.input];
+  const TflTensor& w = d.tensors[g.filter];
+  const bool i8 = in.type == DataType::kInt8;
+  ConvQuant q;
+  ConvMultipliers(Scale(in), w.scale, g.out_c, Scale(out), !i8, &q.mult, &q.shift);
+  ActivationRangeQuantized(g.act, Scale(out), Zp(out), i8, &q.amin, &q.amax);
+  q.in_zp = Dom(in);
+  q.w_zp = i8 ? 0 : Dom(w);  // int8 kernels ignore the filter zero point
+  q.bias = g.bias >= 0 ? reinterpret_cast<const int32_t*>(d.tensors[g.bias].data) : nullptr;
+  return q;
+}
+
+// A 1x1 stride-1 conv over a handful of pixels (the classifier at batch 1)
+// is a GEMV: it runs on the weight-streaming FC kernel with the same packed
+// operands (Bt rows are K-contiguous, bias_eff identical).  True when *L was
+// rewritten.
+bool GemvAsFc(Launch* L) {
+  const bh_conv_params c = L->conv;
+  const long M = static_cast<long>(c.batch) * c.out_h * c.out_w;
+  if (c.k_h != 1 || c.k_w != 1 || c.stride_h != 1 || c.stride_w != 1 || M > 4) return false;
+  Launch F;
+  F.kind = Launch::kFc;
+  F.op_index = L->op_index;
+  F.out_tensor = L->out_tensor;
+  bh_fc_params& f = F.fc;
+  f = bh_fc_params{};
+  f.rows = static_cast<int>(M); f.depth = c.in_c; f.depth_pad = c.k_pad; f.units = c.out_c;
+  f.in_xor = c.in_xor; f.in_zp = c.in_zp; f.w_zp = c.w_zp; f.out_zp = c.out_zp;
+  f.act_min = c.act_min; f.act_max = c.act_max; f.input = c.input; f.output = c.output;
+  f.weights = c.weights; f.bias_eff = c.bias_eff; f.mult = c.mult; f.shift = c.shift;
+  F.kernel = "fc_kernel";
+  F.alg_bytes = L->alg_bytes;
+  F.alg_ops = L->alg_ops;
+  *L = F;
+  return true;
+}
+
+// the geometry fields bh_conv_params, bh_dwconv_params and bh_conv_f32_params share
+template <class Params>
+void SetGeometry(const ConvGeometry& g, Params* p) {
+  p->batch = g.batch; p->in_h = g.in_h; p->in_w = g.in_w; p->in_c = g.in_c;
+  p->out_h = g.out_h; p->out_w = g.out_w; p->out_c = g.out_c; p->k_h = g.k_h; p->k_w = g.k_w;
+  p->stride_h = g.stride_h; p->stride_w = g.stride_w; p->dil_h = g.dil_h; p->dil_w = g.dil_w;
+  p->pad_h = g.pad_h; p->pad_w = g.pad_w;
+}
+// ... and bh_pool_params and bh_pool_f32_params
+template <class Params>
+void SetGeometry(const PoolGeometry& g, Params* p) {
+  p->batch = g.batch; p->in_h = g.in_h; p->in_w = g.in_w; p->channels = g.channels;
+  p->out_h = g.out_h; p->out_w = g.out_w; p->f_h = g.f_h; p->f_w = g.f_w;
+  p->stride_h = g.stride_h; p->stride_w = g.stride_w; p->pad_h = g.pad_h; p->pad_w = g.pad_w;
+}
+
+absl::Status Refused(const TflOperator& op, const char* why) {
+  return absl::InternalError(std::string("unsupported ") + TflBuiltinName(op.builtin) + ": " + why);
+}
+
+}  // namespace
+
+absl::Status HipModelExecutor::ConstBlob(const std::string& key, size_t bytes, PreparedSubgraph* sg,
+                                         const std::function<absl::Status(uint8_t*)>& fill,
+                                         std::shared_ptr<DeviceBlob>* out) {
+  auto blob = DeviceRegistry::Get().FindConst(ordinal_, key);
+  if (!blob) {
+    std::vector<uint8_t> host(bytes, 0);
+    RETURN_STATUS_IF(fill(host.data()));
+    blob = std::make_shared<DeviceBlob>(ordinal_, bytes);
+    if (!blob->ok() || !blob->Upload(0, host.data(), bytes)) return HipErr(1, ("upload constant " + key).c_str());
+    DeviceRegistry::Get().PutConst(ordinal_, key, blob);
+  }
+  sg->consts.push_back(blob);
+  *out = blob;
+  return absl::OkStatus();
+}
+
+absl::Status HipModelExecutor::UploadConst(const std::string& key, const void* data, size_t bytes,
+                                           PreparedSubgraph* sg, const void** dev) {
+  std::shared_ptr<DeviceBlob> blob;
+  RETURN_STATUS_IF(ConstBlob(key, bytes, sg, [&](uint8_t* host) {
+    if (bytes) std::memcpy(host, data, bytes);
+    return absl::OkStatus();
+  }, &blob));
+  *dev = blob->ptr();
+  return absl::OkStatus();
+}
+
 absl::Status HipModelExecutor::DevicePtr(const HipModel& model, int t, PreparedSubgraph* sg, void** ptr) {
   const TflTensor& tt = model.desc().tensors[t];
   if (!tt.is_const()) {
@@ -16,30 +113,77 @@ absl::Status HipModelExecutor::DevicePtr(const HipModel& model, int t, PreparedS
     *ptr = static_cast<char*>(sg->arena->ptr()) + it->second;
     return absl::OkStatus();
   }
-  const std::string key = "m" + Hex(model.serial()) + "/t" + std::to_string(t);
-  auto blob = DeviceRegistry::Get().FindConst(ordinal_, key);
-  if (!blob) {
-    blob = std::make_shared<DeviceBlob>(ordinal_, tt.data_size);
-    if (!blob->ok() || !blob->Upload(0, tt.data, tt.data_size))
-      return HipErr(1, "upload constant");
-    DeviceRegistry::Get().PutConst(ordinal_, key, blob);
-  }
-  sg->consts.push_back(blob);
-  *ptr = blob->ptr();
+  const void* dev = nullptr;
+  RETURN_STATUS_IF(UploadConst("m" + Hex(model.serial()) + "/t" + std::to_string(t), tt.data, tt.data_size, sg, &dev));
+  *ptr = const_cast<void*>(dev);
   return absl::OkStatus();
 }
 
-absl::Status HipModelExecutor::UploadConst(const std::string& key, const void* data, size_t bytes,
-                                           PreparedSubgraph* sg, const void** dev) {
-  auto blob = DeviceRegistry::Get().FindConst(ordinal_, key);
-  if (!blob) {
-    blob = std::make_shared<DeviceBlob>(ordinal_, bytes);
-    if (!blob->ok() || !blob->Upload(0, data, bytes)) return HipErr(1, "upload table");
-    DeviceRegistry::Get().PutConst(ordinal_, key, blob);
+// The kConv / kConvGrouped launch of geometry g: filters packed with K = kh kw
+// icg (one row per output channel) next to the folded bias and the
+// multipliers, then the 1x1-GEMV-to-FC rewrite or the residual-ADD fold.
+// `flip` packs the filters spatially flipped (TRANSPOSE_CONV).
+absl::Status HipModelExecutor::PackedConv(const HipModel& model, int oi, const ConvGeometry& g, bool flip,
+                                          const void* in_ptr, void* out_ptr, const std::string& ckey,
+                                          PreparedSubgraph* sg, Launch* L) {
+  const TflModel& d = model.desc();
+  const TflTensor& w = d.tensors[g.filter];
+  const TflTensor& out = d.tensors[d.ops[oi].outputs[0]];
+  const bool i8 = w.type == DataType::kInt8;
+  const ConvQuant q = QuantOf(d, g, out);
+  const int oc = g.out_c, kh = g.k_h, kw = g.k_w, icg = g.in_c / g.groups, K = kh * kw * icg;
+  int kp = 0, np = 0;
+  bh_conv_packed_geometry(oc, K, &kp, &np);
+  const size_t wbytes = static_cast<size_t>(kp) * np;
+  std::shared_ptr<DeviceBlob> blob;
+  RETURN_STATUS_IF(ConstBlob(ckey, wbytes + 12ull * oc, sg, [&](uint8_t* host) {
+    std::vector<uint8_t> flipped(flip ? static_cast<size_t>(oc) * K : 0);
+    for (size_t i = 0; i < flipped.size(); ++i) {
+      const size_t ci = i % icg, fx = i / icg % kw, fy = i / icg / kw % kh, co = i / K;
+      flipped[i] = w.data[((co * kh + (kh - 1 - fy)) * kw + (kw - 1 - fx)) * icg + ci];
+    }
+    int32_t* tables = reinterpret_cast<int32_t*>(host + wbytes);
+    if (bh_pack_conv_weights(flip ? flipped.data() : w.data, i8 ? 1 : 0, oc, K, kp, np, q.bias, q.in_zp, q.w_zp,
+                             reinterpret_cast<int8_t*>(host), tables) != 0)
+      return absl::InternalError("weight packing failed");
+    std::copy(q.mult.begin(), q.mult.end(), tables + oc);
+    std::copy(q.shift.begin(), q.shift.end(), tables + 2 * oc);
+    return absl::OkStatus();
+  }, &blob));
+  const int32_t* tab = reinterpret_cast<const int32_t*>(static_cast<char*>(blob->ptr()) + wbytes);
+  bh_conv_params& p = L->conv;
+  p = bh_conv_params{};
+  SetGeometry(g, &p);
+  p.k_pad = kp; p.n_pad = np; p.in_xor = i8 ? 0 : 0x80;
+  p.in_zp = q.in_zp; p.w_zp = q.w_zp; p.out_zp = Zp(out); p.act_min = q.amin; p.act_max = q.amax;
+  p.input = in_ptr; p.output = out_ptr;
+  p.weights = static_cast<const int8_t*>(blob->ptr());
+  p.bias_eff = tab; p.mult = tab + oc; p.shift = tab + 2 * oc;
+  p.requant_fast = bh_conv_requant_fast_ok(q.mult.data(), q.shift.data(), oc, K, MaxAbs(q.bias, oc));
+  const double M = static_cast<double>(g.batch) * g.out_h * g.out_w;
+  L->alg_ops = 2.0 * M * oc * K;
+  L->alg_bytes = static_cast<double>(g.batch) * g.in_h * g.in_w * g.in_c + M * oc + static_cast<double>(oc) * K +
+                 12.0 * oc;
+  if (g.groups == 1) {
+    L->kind = Launch::kConv;
+    L->kernel = bh_conv2d_i8_kernel(&p);  // the kernel bh_conv2d_i8 dispatches to
+    if (GemvAsFc(L)) return absl::OkStatus();
+  } else {
+    L->kind = Launch::kConvGrouped;
+    L->conv_groups = g.groups;
+    const bh_conv_grouped_params gp{p, g.groups};
+    L->kernel = device_flag_ == DeviceFlag::kCPU ? "conv_grouped_host" : bh_conv2d_grouped_i8_kernel(&gp);
   }
-  sg->consts.push_back(blob);
-  *dev = blob->ptr();
+  TryFuseResidualAdd(model, oi, sg, L);  // the grouped kernel shares the dense epilogue
   return absl::OkStatus();
+}
+
+absl::Status HipModelExecutor::LowerConv(const HipModel& model, int oi, void* in_ptr, void* out_ptr,
+                                         const std::string& ckey, PreparedSubgraph* sg, Launch* L) {
+  ConvGeometry g;
+  const char* why = "";
+  if (!ConvArgs(model.desc(), model.desc().ops[oi], &g, &why)) return Refused(model.desc().ops[oi], why);
+  return PackedConv(model, oi, g, false, in_ptr, out_ptr, ckey, sg, L);
 }
 
 // TRANSPOSE_CONV (int8; reference_integer_ops::TransposeConv scatters
@@ -52,27 +196,16 @@ absl::Status HipModelExecutor::UploadConst(const std::string& key, const void* d
 absl::Status HipModelExecutor::LowerTransposeConv(const HipModel& model, int oi, void* out_ptr,
                                                   const std::string& ckey, PreparedSubgraph* sg, Launch* L) {
   const TflModel& d = model.desc();
-  const TflOperator& op = d.ops[oi];
-  const TflTensor& w = d.tensors[op.inputs[1]];
-  const TflTensor& x = d.tensors[op.inputs[2]];
-  const TflTensor& out = d.tensors[op.outputs[0]];
+  ConvGeometry g;
+  const char* why = "";
+  if (!ConvArgs(d, d.ops[oi], &g, &why)) return Refused(d.ops[oi], why);
+  const TflTensor& x = d.tensors[g.input];
   void* x_ptr = nullptr;
-  RETURN_STATUS_IF(DevicePtr(model, op.inputs[2], sg, &x_ptr));
-  const int32_t* bias = nullptr;
-  if (op.inputs.size() > 3 && op.inputs[3] >= 0) bias = reinterpret_cast<const int32_t*>(d.tensors[op.inputs[3]].data);
-  const FbTable& o = op.options;
-  const bool same = !o.valid() || o.Int8(0, 0) == 0;
-  const int sw = o.valid() ? o.Int(1, 1) : 1, sh = o.valid() ? o.Int(2, 1) : 1;
-  const int b = x.shape[0], ih = x.shape[1], iw = x.shape[2], ic = x.shape[3];
-  const int oc = w.shape[0], kh = w.shape[1], kw = w.shape[2];
-  const int oh = out.shape[1], ow = out.shape[2];
-  if (out.shape[0] != b || out.shape[3] != oc) return absl::InternalError("TRANSPOSE_CONV shape mismatch");
-  // transpose_conv.cc: padding computed as for a conv whose input is the output
-  const int ph = ComputePadding(sh, 1, oh, kh, ComputeOutSize(same, oh, kh, sh, 1));
-  const int pw = ComputePadding(sw, 1, ow, kw, ComputeOutSize(same, ow, kw, sw, 1));
-  const int uh = (ih - 1) * sh + 1, uw = (iw - 1) * sw + 1;
+  RETURN_STATUS_IF(DevicePtr(model, g.input, sg, &x_ptr));
+  const int uh = (g.in_h - 1) * g.stride_h + 1, uw = (g.in_w - 1) * g.stride_w + 1;
+  const size_t ubytes = static_cast<size_t>(g.batch) * uh * uw * g.in_c;
   // zero-inserted input in a scratch buffer owned by this subgraph
-  auto scratch = std::make_shared<DeviceBlob>(ordinal_, static_cast<size_t>(b) * uh * uw * ic);
+  auto scratch = std::make_shared<DeviceBlob>(ordinal_, ubytes);
   if (!scratch->ok()) return absl::InternalError("HBM scratch allocation failed");
   sg->consts.push_back(scratch);
   Launch Z;
@@ -80,62 +213,19 @@ absl::Status HipModelExecutor::LowerTransposeConv(const HipModel& model, int oi,
   Z.op_index = oi;
   Z.kernel = "zero_insert_kernel";
   Z.zi = bh_zero_insert_params{};
-  Z.zi.batch = b; Z.zi.in_h = ih; Z.zi.in_w = iw; Z.zi.channels = ic;
-  Z.zi.stride_h = sh; Z.zi.stride_w = sw; Z.zi.out_h = uh; Z.zi.out_w = uw;
+  Z.zi.batch = g.batch; Z.zi.in_h = g.in_h; Z.zi.in_w = g.in_w; Z.zi.channels = g.in_c;
+  Z.zi.stride_h = g.stride_h; Z.zi.stride_w = g.stride_w; Z.zi.out_h = uh; Z.zi.out_w = uw;
   Z.zi.fill = static_cast<uint32_t>(Zp(x)) & 0xffu;
   Z.zi.input = x_ptr;
   Z.zi.output = scratch->ptr();
-  Z.alg_bytes = static_cast<double>(x.num_elements()) + static_cast<double>(b) * uh * uw * ic;
+  Z.alg_bytes = static_cast<double>(x.num_elements()) + static_cast<double>(ubytes);
   sg->launches.push_back(Z);
-  // flipped, packed filters + folded bias (int8 filters: zero point 0)
-  const int K = kh * kw * ic;
-  int kp = 0, np = 0;
-  bh_conv_packed_geometry(oc, K, &kp, &np);
-  const size_t wbytes = static_cast<size_t>(kp) * np;
-  const size_t tbytes = 12ull * oc;
-  std::vector<int32_t> mult, shift;
-  ConvMultipliers(Scale(x), w.scale, oc, Scale(out), false, &mult, &shift);
-  auto blob = DeviceRegistry::Get().FindConst(ordinal_, ckey);
-  if (!blob) {
-    std::vector<int8_t> flipped(static_cast<size_t>(oc) * K);
-    for (int co = 0; co < oc; ++co)
-      for (int fy = 0; fy < kh; ++fy)
-        for (int fx = 0; fx < kw; ++fx)
-          for (int ci = 0; ci < ic; ++ci)
-            flipped[((static_cast<size_t>(co) * kh + fy) * kw + fx) * ic + ci] = static_cast<int8_t>(
-                w.data[((static_cast<size_t>(co) * kh + (kh - 1 - fy)) * kw + (kw - 1 - fx)) * ic + ci]);
-    std::vector<int8_t> packed(wbytes);
-    std::vector<int32_t> tables(3ull * oc);
-    if (bh_pack_conv_weights(flipped.data(), 1, oc, K, kp, np, bias, Zp(x), 0, packed.data(), tables.data()) != 0)
-      return absl::InternalError("weight packing failed");
-    std::copy(mult.begin(), mult.end(), tables.begin() + oc);
-    std::copy(shift.begin(), shift.end(), tables.begin() + 2 * oc);
-    blob = std::make_shared<DeviceBlob>(ordinal_, wbytes + tbytes);
-    if (!blob->ok() || !blob->Upload(0, packed.data(), wbytes) ||
-        !blob->Upload(wbytes, tables.data(), tbytes))
-      return HipErr(1, "upload transpose-conv operands");
-    DeviceRegistry::Get().PutConst(ordinal_, ckey, blob);
-  }
-  sg->consts.push_back(blob);
-  const int32_t* tab = reinterpret_cast<const int32_t*>(static_cast<char*>(blob->ptr()) + wbytes);
-  bh_conv_params& p = L->conv;
-  p = bh_conv_params{};
-  p.batch = b; p.in_h = uh; p.in_w = uw; p.in_c = ic;
-  p.out_h = oh; p.out_w = ow; p.out_c = oc; p.k_h = kh; p.k_w = kw;
-  p.stride_h = 1; p.stride_w = 1; p.dil_h = 1; p.dil_w = 1;
-  p.pad_h = kh - 1 - ph; p.pad_w = kw - 1 - pw;
-  p.k_pad = kp; p.n_pad = np; p.in_xor = 0;
-  p.in_zp = Zp(x); p.w_zp = 0; p.out_zp = Zp(out); p.act_min = -128; p.act_max = 127;
-  p.input = scratch->ptr(); p.output = out_ptr;
-  p.weights = static_cast<const int8_t*>(blob->ptr());
-  p.bias_eff = tab; p.mult = tab + oc; p.shift = tab + 2 * oc;
-  p.requant_fast = bh_conv_requant_fast_ok(mult.data(), shift.data(), oc, K, MaxAbs(bias, oc));
-  L->kind = Launch::kConv;
-  L->kernel = bh_conv2d_i8_kernel(&p);
-  const double M = static_cast<double>(b) * oh * ow;
-  L->alg_ops = 2.0 * M * oc * K;
-  L->alg_bytes = static_cast<double>(b) * uh * uw * ic + M * oc + static_cast<double>(oc) * K + 12.0 * oc;
-  return absl::OkStatus();
+  // the stride-1 conv over U: flipped filters, folded bias (int8 filters: zero point 0)
+  ConvGeometry u = g;
+  u.in_h = uh; u.in_w = uw;
+  u.stride_h = u.stride_w = 1;
+  u.pad_h = g.k_h - 1 - g.pad_h; u.pad_w = g.k_w - 1 - g.pad_w;
+  return PackedConv(model, oi, u, true, scratch->ptr(), out_ptr, ckey, sg, L);
 }
 
 // Glue ops.  Every 8-bit unary op becomes a 256-entry
@@ -255,24 +345,14 @@ absl::Status HipModelExecutor::LowerGlue(const HipModel& model, int oi, void* in
     case kTflPad:
     case kTflPadV2:
     case kTflMirrorPad: {
-      const TflTensor& pt = T(op.inputs[1]);
       const int rank = static_cast<int>(in.shape.size());
       std::vector<int64_t> pads(2 * static_cast<size_t>(rank), 0);
       int mirror = 0;
       if (op.builtin == kTflMirrorPad && !MirrorPadArgs(d, op, &pads, &mirror))
         return absl::InternalError("MIRROR_PAD arguments");
-      for (size_t i = 0; !mirror && i < pads.size() && i * (pt.type == DataType::kInt64 ? 8 : 4) < pt.data_size;
-           ++i) {
-        if (pt.type == DataType::kInt64) {
-          int64_t v;
-          std::memcpy(&v, pt.data + 8 * i, 8);
-          pads[i] = v;
-        } else {
-          int32_t v;
-          std::memcpy(&v, pt.data + 4 * i, 4);
-          pads[i] = v;
-        }
-      }
+      std::vector<int64_t> given;
+      if (!mirror && ConstInts(T(op.inputs[1]), &given))  // PAD / PADV2
+        std::copy_n(given.begin(), std::min(given.size(), pads.size()), pads.begin());
       bh_pad_params& p = L->pad;
       p = bh_pad_params{};
       p.elem_bytes = static_cast<int>(GetDataTypeBytes(in.type));
@@ -453,9 +533,10 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
   const TflTensor& out = T(op.outputs[0]);
   const double io_bytes = 4.0 * (static_cast<double>(in.num_elements()) + out.num_elements());
   L->alg_bytes = io_bytes;
-  auto upload = [&](const std::string& key, const std::vector<float>& v, const void** dev) {
-    return UploadConst(key, v.data(), v.size() * sizeof(float), sg, dev);
+  auto upload = [&](const std::string& key, const std::vector<float>& v, const float** dev) {
+    return UploadConst(key, v.data(), v.size() * sizeof(float), sg, reinterpret_cast<const void**>(dev));
   };
+  const char* why = "";
   switch (op.builtin) {
     case kTflDequantize: {
       const int t = op.outputs[0];
@@ -473,7 +554,7 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
         *emit = false;
         return absl::OkStatus();
       }
-      const void* dev = nullptr;
+      const float* dev = nullptr;
       RETURN_STATUS_IF(upload(ckey + "/f32", FloatData(d, t), &dev));
       L->kind = Launch::kCopy;
       L->kernel = "copy";
@@ -486,82 +567,59 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
     case kTflConv2D:
     case kTflDepthwiseConv2D: {
       const bool dw = op.builtin == kTflDepthwiseConv2D;
-      const TflTensor& w = T(op.inputs[1]);
-      const FbTable& o = op.options;
-      const bool same = o.Int8(0, 0) == 0;
-      const int sw = o.Int(1, 1), sh = o.Int(2, 1);
-      const int act = dw ? o.Int8(4, 0) : o.Int8(3, 0);
-      const int dlw = dw ? o.Int(5, 1) : o.Int(4, 1);
-      const int dlh = dw ? o.Int(6, 1) : o.Int(5, 1);
-      const int b = in.shape[0], ih = in.shape[1], iw = in.shape[2], ic = in.shape[3];
-      const int oc = dw ? w.shape[3] : w.shape[0];
-      const int kh = w.shape[1], kw = w.shape[2];
-      const int oh = ComputeOutSize(same, ih, kh, sh, dlh), ow = ComputeOutSize(same, iw, kw, sw, dlw);
-      if (out.shape != std::vector<int>{b, oh, ow, oc}) return absl::InternalError("conv output shape mismatch");
-      std::vector<float> wf = FloatData(d, op.inputs[1]);
+      ConvGeometry g;
+      if (!ConvArgs(d, op, &g, &why)) return Refused(op, why);
+      const int oc = g.out_c;
+      std::vector<float> wf = FloatData(d, g.filter);
       std::vector<float> laid(wf.size());
       if (dw) {
         laid = wf;  // [1][kh][kw][oc] is already [kh*kw][oc]
       } else {
-        const int K = kh * kw * ic;  // OHWI -> [K][oc]
+        const int K = g.k_h * g.k_w * g.in_c;  // OHWI -> [K][oc]
         for (int c = 0; c < oc; ++c)
           for (int k = 0; k < K; ++k) laid[static_cast<size_t>(k) * oc + c] = wf[static_cast<size_t>(c) * K + k];
       }
       bh_conv_f32_params& p = L->convf;
       p = bh_conv_f32_params{};
-      const void* wdev = nullptr;
-      RETURN_STATUS_IF(upload(ckey + "/w", laid, &wdev));
-      p.weights = static_cast<const float*>(wdev);
-      if (op.inputs.size() > 2 && op.inputs[2] >= 0) {
-        const void* bdev = nullptr;
-        RETURN_STATUS_IF(upload(ckey + "/b", FloatData(d, op.inputs[2]), &bdev));
-        p.bias = static_cast<const float*>(bdev);
-      }
-      p.batch = b; p.in_h = ih; p.in_w = iw; p.in_c = ic; p.out_h = oh; p.out_w = ow; p.out_c = oc;
-      p.k_h = kh; p.k_w = kw; p.stride_h = sh; p.stride_w = sw; p.dil_h = dlh; p.dil_w = dlw;
-      p.pad_h = ComputePadding(sh, dlh, ih, kh, oh);
-      p.pad_w = ComputePadding(sw, dlw, iw, kw, ow);
+      RETURN_STATUS_IF(upload(ckey + "/w", laid, &p.weights));
+      if (g.bias >= 0) RETURN_STATUS_IF(upload(ckey + "/b", FloatData(d, g.bias), &p.bias));
+      SetGeometry(g, &p);
       p.depthwise = dw ? 1 : 0;
-      p.depth_multiplier = dw ? oc / ic : 1;
-      FloatActRange(act, &p.act_min, &p.act_max);
+      p.depth_multiplier = g.depth_multiplier;
+      FloatActRange(g.act, &p.act_min, &p.act_max);
       p.input = static_cast<const float*>(in_ptr);
       p.output = static_cast<float*>(out_ptr);
       L->kind = Launch::kConvF32;
       L->kernel = dw ? "dwconv_f32_kernel" : "conv_f32_kernel";
-      L->alg_ops = 2.0 * b * oh * ow * oc * kh * kw * (dw ? 1 : ic);
+      L->alg_ops = 2.0 * g.batch * g.out_h * g.out_w * oc * g.k_h * g.k_w * (dw ? 1 : g.in_c);
       L->alg_bytes = io_bytes + 4.0 * laid.size() + 4.0 * oc;
       return absl::OkStatus();
     }
     case kTflFullyConnected: {
-      const TflTensor& w = T(op.inputs[1]);
-      const int units = w.shape[0], depth = w.shape[1];
+      FcGeometry g;
+      if (!FcArgs(d, op, &g, &why)) return Refused(op, why);
       bh_fc_f32_params& p = L->fcf;
       p = bh_fc_f32_params{};
-      const void* wdev = nullptr;
-      RETURN_STATUS_IF(upload(ckey + "/w", FloatData(d, op.inputs[1]), &wdev));
-      p.weights = static_cast<const float*>(wdev);
-      if (op.inputs.size() > 2 && op.inputs[2] >= 0) {
-        const void* bdev = nullptr;
-        RETURN_STATUS_IF(upload(ckey + "/b", FloatData(d, op.inputs[2]), &bdev));
-        p.bias = static_cast<const float*>(bdev);
-      }
-      p.rows = static_cast<int>(in.num_elements() / depth);
-      p.depth = depth;
-      p.units = units;
-      FloatActRange(op.options.valid() ? op.options.Int8(0, 0) : 0, &p.act_min, &p.act_max);
+      RETURN_STATUS_IF(upload(ckey + "/w", FloatData(d, g.filter), &p.weights));
+      if (g.bias >= 0) RETURN_STATUS_IF(upload(ckey + "/b", FloatData(d, g.bias), &p.bias));
+      p.rows = g.rows;
+      p.depth = g.depth;
+      p.units = g.units;
+      FloatActRange(g.act, &p.act_min, &p.act_max);
       p.input = static_cast<const float*>(in_ptr);
       p.output = static_cast<float*>(out_ptr);
       L->kind = Launch::kFcF32;
       L->kernel = "fc_f32_kernel";
-      L->alg_ops = 2.0 * p.rows * units * depth;
-      L->alg_bytes = io_bytes + 4.0 * units * depth;
+      L->alg_ops = 2.0 * p.rows * g.units * g.depth;
+      L->alg_bytes = io_bytes + 4.0 * g.units * g.depth;
       return absl::OkStatus();
     }
     case kTflAdd:
     case kTflSub:
     case kTflMul:
     case kTflSquaredDifference: {
-      const TflTensor& bt = T(op.inputs[1]);
+      BroadcastShapes s;
+      if (!BroadcastArgs(d, op, &s, &why)) return Refused(op, why);
       void* b_ptr = nullptr;
       RETURN_STATUS_IF(DevicePtr(model, op.inputs[1], sg, &b_ptr));
       bh_eltwise_f32_params& p = L->eltf;
@@ -570,33 +628,25 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
                : op.builtin == kTflSub ? BH_ELTF_SUB
                : op.builtin == kTflMul ? BH_ELTF_MUL
                                        : BH_ELTF_SQDIFF;
-      Shape4(in.shape, p.shape_a);
-      Shape4(bt.shape, p.shape_b);
-      Shape4(out.shape, p.shape_o);
-      FloatActRange(op.options.valid() ? op.options.Int8(0, 0) : 0, &p.act_min, &p.act_max);
+      std::copy_n(s.a, 4, p.shape_a); std::copy_n(s.b, 4, p.shape_b); std::copy_n(s.o, 4, p.shape_o);
+      FloatActRange(op.options.Int8(0, 0), &p.act_min, &p.act_max);
       p.a = static_cast<const float*>(in_ptr);
       p.b = static_cast<const float*>(b_ptr);
       p.out = static_cast<float*>(out_ptr);
       L->kind = Launch::kEltwiseF32;
       L->kernel = "eltwise_f32_kernel";
-      L->alg_bytes += 4.0 * bt.num_elements();
+      L->alg_bytes += 4.0 * T(op.inputs[1]).num_elements();
       return absl::OkStatus();
     }
     case kTflAveragePool2D:
     case kTflMaxPool2D: {
-      const FbTable& o = op.options;
-      const bool same = o.Int8(0, 0) == 0;
-      const int sw = o.Int(1, 1), sh = o.Int(2, 1), fw = o.Int(3, 1), fh = o.Int(4, 1);
+      PoolGeometry g;
+      if (!PoolArgs(d, op, &g, &why)) return Refused(op, why);
       bh_pool_f32_params& p = L->poolf;
       p = bh_pool_f32_params{};
       p.kind = op.builtin == kTflAveragePool2D ? BH_POOL_AVG : BH_POOL_MAX;
-      p.batch = in.shape[0]; p.in_h = in.shape[1]; p.in_w = in.shape[2]; p.channels = in.shape[3];
-      p.out_h = ComputeOutSize(same, p.in_h, fh, sh, 1);
-      p.out_w = ComputeOutSize(same, p.in_w, fw, sw, 1);
-      p.f_h = fh; p.f_w = fw; p.stride_h = sh; p.stride_w = sw;
-      p.pad_h = ComputePadding(sh, 1, p.in_h, fh, p.out_h);
-      p.pad_w = ComputePadding(sw, 1, p.in_w, fw, p.out_w);
-      FloatActRange(o.Int8(5, 0), &p.act_min, &p.act_max);
+      SetGeometry(g, &p);
+      FloatActRange(g.act, &p.act_min, &p.act_max);
       p.input = static_cast<const float*>(in_ptr);
       p.output = static_cast<float*>(out_ptr);
       L->kind = Launch::kPoolF32;
@@ -784,6 +834,240 @@ absl::Status HipModelExecutor::LowerBatchMatMul(const HipModel& model, int oi, v
   return absl::OkStatus();
 }
 
+absl::Status HipModelExecutor::LowerDepthwise(const HipModel& model, int oi, void* in_ptr, void* out_ptr,
+                                              const std::string& ckey, PreparedSubgraph* sg, Launch* L) {
+  const TflModel& d = model.desc();
+  const TflOperator& op = d.ops[oi];
+  ConvGeometry g;
+  const char* why = "";
+  if (!ConvArgs(d, op, &g, &why)) return Refused(op, why);
+  const TflTensor& in = d.tensors[g.input];
+  const TflTensor& w = d.tensors[g.filter];
+  const TflTensor& out = d.tensors[op.outputs[0]];
+  const bool i8 = in.type == DataType::kInt8;
+  const ConvQuant q = QuantOf(d, g, out);
+  const int oc = g.out_c, kh = g.k_h, kw = g.k_w;
+  const size_t wbytes = static_cast<size_t>(kh) * kw * oc;
+  const size_t wpad = (wbytes + 15) / 16 * 16;
+  const size_t tbytes = 12ull * oc;
+  // 3x3 / dm 1 layers also get the dot4 kernel's tap table (bh_pack_dw_taps)
+  const bool dot = kh == 3 && kw == 3 && g.depth_multiplier == 1 && oc % 4 == 0;
+  const size_t pbytes = dot ? 16ull * oc : 0;
+  std::shared_ptr<DeviceBlob> blob;
+  RETURN_STATUS_IF(ConstBlob(ckey, wpad + tbytes + pbytes, sg, [&](uint8_t* host) {
+    for (size_t i = 0; i < wbytes; ++i) host[i] = i8 ? w.data[i] : static_cast<uint8_t>(w.data[i] ^ 0x80);
+    int32_t* tables = reinterpret_cast<int32_t*>(host + wpad);
+    for (int c = 0; c < oc; ++c) tables[c] = q.bias ? q.bias[c] : 0;
+    std::copy(q.mult.begin(), q.mult.end(), tables + oc);
+    std::copy(q.shift.begin(), q.shift.end(), tables + 2 * oc);
+    if (dot && bh_pack_dw_taps(reinterpret_cast<const int8_t*>(host), oc, tables, q.in_zp, q.w_zp, tables + 3 * oc) != 0)
+      return absl::InternalError("depthwise tap packing failed");
+    return absl::OkStatus();
+  }, &blob));
+  const int32_t* tab = reinterpret_cast<const int32_t*>(static_cast<char*>(blob->ptr()) + wpad);
+  bh_dwconv_params& p = L->dw;
+  p = bh_dwconv_params{};
+  SetGeometry(g, &p);
+  p.depth_multiplier = g.depth_multiplier;
+  p.in_xor = i8 ? 0 : 0x80; p.in_zp = q.in_zp; p.w_zp = q.w_zp; p.out_zp = Zp(out);
+  p.act_min = q.amin; p.act_max = q.amax; p.input = in_ptr; p.output = out_ptr;
+  p.weights = static_cast<const int8_t*>(blob->ptr());
+  p.bias = tab; p.mult = tab + oc; p.shift = tab + 2 * oc;
+  if (dot && !blob->host()) p.taps = tab + 3 * oc;
+  p.requant_fast = bh_conv_requant_fast_ok(q.mult.data(), q.shift.data(), oc, kh * kw, MaxAbs(q.bias, oc));
+  L->kind = Launch::kDwConv;
+  L->kernel = bh_dwconv2d_i8_kernel(&p);  // the kernel bh_dwconv2d_i8 dispatches to
+  const double M = static_cast<double>(g.batch) * g.out_h * g.out_w;
+  L->alg_ops = 2.0 * M * oc * kh * kw;
+  L->alg_bytes = static_cast<double>(in.num_elements()) + M * oc + static_cast<double>(wbytes) + 12.0 * oc;
+  return absl::OkStatus();
+}
+
+absl::Status HipModelExecutor::LowerFc(const HipModel& model, int oi, void* in_ptr, void* out_ptr,
+                                       const std::string& ckey, PreparedSubgraph* sg, Launch* L) {
+  const TflModel& d = model.desc();
+  const TflOperator& op = d.ops[oi];
+  FcGeometry g;
+  const char* why = "";
+  if (!FcArgs(d, op, &g, &why)) return Refused(op, why);
+  const TflTensor& in = d.tensors[op.inputs[0]];
+  const TflTensor& w = d.tensors[g.filter];
+  const TflTensor& out = d.tensors[op.outputs[0]];
+  const bool i8 = in.type == DataType::kInt8;
+  const int32_t* bias = g.bias >= 0 ? reinterpret_cast<const int32_t*>(d.tensors[g.bias].data) : nullptr;
+  const int units = g.units, depth = g.depth, rows = g.rows;
+  const int depth_pad = (depth + 15) / 16 * 16;
+  int32_t mult, shift, amin, amax;
+  FullyConnectedMultiplier(Scale(in), Scale(w), Scale(out), &mult, &shift);
+  ActivationRangeQuantized(g.act, Scale(out), Zp(out), i8, &amin, &amax);
+  const int32_t in_zp = Dom(in), w_zp = Dom(w);
+  const size_t wbytes = static_cast<size_t>(units) * depth_pad;
+  std::shared_ptr<DeviceBlob> blob;
+  RETURN_STATUS_IF(ConstBlob(ckey, wbytes + 12ull * units, sg, [&](uint8_t* host) {
+    int8_t* packed = reinterpret_cast<int8_t*>(host);
+    int32_t* tables = reinterpret_cast<int32_t*>(host + wbytes);
+    for (int u = 0; u < units; ++u) {
+      int64_t s = 0;
+      for (int k = 0; k < depth; ++k) {
+        const uint8_t raw = w.data[static_cast<size_t>(u) * depth + k];
+        const int v = i8 ? static_cast<int>(static_cast<int8_t>(raw)) : static_cast<int>(raw) - 128;
+        packed[static_cast<size_t>(u) * depth_pad + k] = static_cast<int8_t>(v);
+        s += v;
+      }
+      tables[u] = static_cast<int32_t>((bias ? bias[u] : 0) - static_cast<int64_t>(in_zp) * s +
+                                       static_cast<int64_t>(depth) * in_zp * w_zp);
+      tables[units + u] = mult;
+      tables[2 * units + u] = shift;
+    }
+    return absl::OkStatus();
+  }, &blob));
+  const int32_t* tab = reinterpret_cast<const int32_t*>(static_cast<char*>(blob->ptr()) + wbytes);
+  bh_fc_params& p = L->fc;
+  p = bh_fc_params{};
+  p.rows = rows; p.depth = depth; p.depth_pad = depth_pad; p.units = units;
+  p.in_xor = i8 ? 0 : 0x80; p.in_zp = in_zp; p.w_zp = w_zp; p.out_zp = Zp(out);
+  p.act_min = amin; p.act_max = amax; p.input = in_ptr; p.output = out_ptr;
+  p.weights = static_cast<const int8_t*>(blob->ptr());
+  p.bias_eff = tab; p.mult = tab + units; p.shift = tab + 2 * units;
+  L->kind = Launch::kFc;
+  L->kernel = "fc_kernel";
+  L->alg_ops = 2.0 * rows * units * depth;
+  L->alg_bytes = static_cast<double>(rows) * depth + static_cast<double>(rows) * units +
+                 static_cast<double>(units) * depth + 12.0 * units;
+  return absl::OkStatus();
+}
+
+// ADD / SUB / MUL int8 / uint8
+absl::Status HipModelExecutor::LowerEltwise(const HipModel& model, int oi, void* in_ptr, void* out_ptr,
+                                            PreparedSubgraph* sg, Launch* L) {
+  const TflModel& d = model.desc();
+  const TflOperator& op = d.ops[oi];
+  BroadcastShapes s;
+  const char* why = "";
+  if (!BroadcastArgs(d, op, &s, &why)) return Refused(op, why);
+  const TflTensor& in = d.tensors[op.inputs[0]];
+  const TflTensor& b = d.tensors[op.inputs[1]];
+  const TflTensor& out = d.tensors[op.outputs[0]];
+  const bool i8 = in.type == DataType::kInt8;
+  void* b_ptr = nullptr;
+  RETURN_STATUS_IF(DevicePtr(model, op.inputs[1], sg, &b_ptr));
+  bh_eltwise_params& p = L->elt;
+  p = bh_eltwise_params{};
+  p.in_signed = i8 ? 1 : 0;
+  std::copy_n(s.a, 4, p.shape_a); std::copy_n(s.b, 4, p.shape_b); std::copy_n(s.o, 4, p.shape_o);
+  p.a_off = -Zp(in); p.b_off = -Zp(b); p.o_off = Zp(out);
+  ActivationRangeQuantized(op.options.Int8(0, 0), Scale(out), Zp(out), i8, &p.act_min, &p.act_max);
+  if (op.builtin == kTflMul) {
+    p.kind = BH_ELT_MUL;
+    MulMultiplier(Scale(in), Scale(b), Scale(out), &p.o_mult, &p.o_shift);
+  } else {
+    p.kind = BH_ELT_ADD;
+    const AddParams ap = AddSubParams(Scale(in), Scale(b), Scale(out), op.builtin == kTflSub);
+    p.left_shift = ap.left_shift;
+    p.a_mult = ap.m1; p.a_shift = ap.s1;
+    p.b_mult = ap.m2; p.b_shift = ap.s2;
+    p.o_mult = ap.mo; p.o_shift = ap.so;
+  }
+  p.a = in_ptr; p.b = b_ptr; p.out = out_ptr;
+  L->kind = Launch::kEltwise;
+  L->kernel = "eltwise_kernel";
+  L->alg_bytes = static_cast<double>(in.num_elements() + b.num_elements() + out.num_elements());
+  return absl::OkStatus();
+}
+
+// AVERAGE_POOL_2D / MAX_POOL_2D int8 / uint8
+absl::Status HipModelExecutor::LowerPool(const HipModel& model, int oi, void* in_ptr, void* out_ptr, Launch* L) {
+  const TflModel& d = model.desc();
+  const TflOperator& op = d.ops[oi];
+  PoolGeometry g;
+  const char* why = "";
+  if (!PoolArgs(d, op, &g, &why)) return Refused(op, why);
+  const TflTensor& in = d.tensors[op.inputs[0]];
+  const TflTensor& out = d.tensors[op.outputs[0]];
+  const bool i8 = in.type == DataType::kInt8;
+  bh_pool_params& p = L->pool;
+  p = bh_pool_params{};
+  p.kind = op.builtin == kTflAveragePool2D ? BH_POOL_AVG : BH_POOL_MAX;
+  p.in_signed = i8 ? 1 : 0;
+  SetGeometry(g, &p);
+  ActivationRangeQuantized(g.act, Scale(out), Zp(out), i8, &p.act_min, &p.act_max);
+  p.input = in_ptr; p.output = out_ptr;
+  L->kind = Launch::kPool;
+  L->kernel = "pool_kernel";
+  L->alg_bytes = static_cast<double>(in.num_elements() + out.num_elements());
+  return absl::OkStatus();
+}
+
+// MEAN: host kernel on a CPU worker, mean_kernel on the GPU
+absl::Status HipModelExecutor::LowerMean(const HipModel& model, int oi, void* in_ptr, void* out_ptr, Launch* L) {
+  const TflModel& d = model.desc();
+  const TflOperator& op = d.ops[oi];
+  const TflTensor& in = d.tensors[op.inputs[0]];
+  const TflTensor& out = d.tensors[op.outputs[0]];
+  CpuMeanParams& p = L->mean;
+  p = CpuMeanParams{};
+  if (!MeanArgs(d, op, &p.outer, &p.reduce, &p.inner)) return absl::InternalError("unsupported MEAN");
+  p.type = in.type == DataType::kFloat32 ? 0 : (in.type == DataType::kInt8 ? 1 : 2);
+  if (p.type) {
+    // optimized_integer_ops::Mean (TFLite 2.9.2): the float products as
+    // written there, then QuantizeMultiplier of the float scale
+    const float in_scale = Scale(in), out_scale = Scale(out);
+    const float n = static_cast<float>(p.reduce);
+    p.bias = Zp(out) - static_cast<int32_t>(Zp(in) * in_scale / out_scale);
+    const float real_scale = in_scale / (n * out_scale);
+    int shift = 0;
+    QuantizeMultiplier(static_cast<double>(real_scale), &p.multiplier, &shift);
+    p.shift = shift;
+  }
+  p.input = in_ptr; p.output = out_ptr;
+  L->kind = Launch::kMean;
+  L->kernel = device_flag_ == DeviceFlag::kGPU ? "mean_kernel" : "mean_host";
+  L->alg_bytes = static_cast<double>(meta_[op.inputs[0]]->bytes + meta_[op.outputs[0]]->bytes);
+  return absl::OkStatus();
+}
+
+absl::Status HipModelExecutor::LowerArgMinMax(const HipModel& model, int oi, void* in_ptr, void* out_ptr, Launch* L) {
+  const TflModel& d = model.desc();
+  const TflOperator& op = d.ops[oi];
+  const DataType type = d.tensors[op.inputs[0]].type;
+  bh_argminmax_params& p = L->argmm;
+  p = bh_argminmax_params{};
+  if (!ArgMinMaxArgs(d, op, &p.outer, &p.axis_len, &p.inner, &p.out_bytes))
+    return absl::InternalError("unsupported ARG_MAX / ARG_MIN");
+  p.in_type = type == DataType::kFloat32 ? BH_ARG_F32 : (type == DataType::kInt8 ? BH_ARG_I8 : BH_ARG_U8);
+  p.is_min = op.builtin == kTflArgMin ? 1 : 0;
+  p.input = in_ptr; p.output = out_ptr;
+  L->kind = Launch::kArgMinMax;
+  L->kernel = device_flag_ == DeviceFlag::kCPU ? "argminmax_host" : bh_argminmax_kernel(&p);
+  L->alg_bytes = static_cast<double>(meta_[op.inputs[0]]->bytes + meta_[op.outputs[0]]->bytes);
+  return absl::OkStatus();
+}
+
+// TFLite_Detection_PostProcess on the CPU worker (CpuSupports)
+absl::Status HipModelExecutor::LowerDetectionHost(const HipModel& model, int oi, void* in_ptr, PreparedSubgraph* sg,
+                                                  Launch* L) {
+  const TflModel& d = model.desc();
+  const TflOperator& op = d.ops[oi];
+  CpuDetectionParams& p = L->det;
+  if (!DetectionSupported(d, op, &p)) return absl::InternalError("unsupported custom op " + op.custom_code);
+  void* scores = nullptr;
+  void* anchors = nullptr;
+  void* outs[4];
+  RETURN_STATUS_IF(DevicePtr(model, op.inputs[1], sg, &scores));
+  RETURN_STATUS_IF(DevicePtr(model, op.inputs[2], sg, &anchors));
+  for (int k = 0; k < 4; ++k) RETURN_STATUS_IF(DevicePtr(model, op.outputs[k], sg, &outs[k]));
+  p.box_encodings = static_cast<const float*>(in_ptr);
+  p.class_scores = static_cast<const float*>(scores);
+  p.anchors = static_cast<const float*>(anchors);
+  p.out_boxes = static_cast<float*>(outs[0]);
+  p.out_classes = static_cast<float*>(outs[1]);
+  p.out_scores = static_cast<float*>(outs[2]);
+  p.out_num = static_cast<float*>(outs[3]);
+  L->kind = Launch::kDetectionPost;
+  L->kernel = "detection_postprocess_host";
+  return absl::OkStatus();
+}
+
 absl::Status HipModelExecutor::Lower(const HipModel& model, int oi, PreparedSubgraph* sg) {
   const TflModel& d = model.desc();
   const TflOperator& op = d.ops[oi];
@@ -798,346 +1082,44 @@ absl::Status HipModelExecutor::Lower(const HipModel& model, int oi, PreparedSubg
     return absl::OkStatus();
   }
   if (IsReindexOp(op.builtin)) return LowerReindex(model, oi, sg);
-  auto T = [&](int i) -> const TflTensor& { return d.tensors[i]; };
-  const TflTensor& in = T(op.inputs[0]);
-  const TflTensor& out = T(op.outputs[0]);
   void* in_ptr = nullptr;
   void* out_ptr = nullptr;
   RETURN_STATUS_IF(DevicePtr(model, op.inputs[0], sg, &in_ptr));
   RETURN_STATUS_IF(DevicePtr(model, op.outputs[0], sg, &out_ptr));
-  const bool i8 = in.type == DataType::kInt8;
   const std::string ckey = "m" + Hex(model.serial()) + "/op" + std::to_string(oi);
   Launch L;
   L.op_index = oi;
   L.out_tensor = op.outputs[0];
-
-  if (IsFloatOp(d, op)) {
-    bool emit = true;
-    RETURN_STATUS_IF(LowerFloat(model, oi, in_ptr, out_ptr, ckey, sg, &L, &emit));
-    if (emit) sg->launches.push_back(L);
-    return absl::OkStatus();
-  }
-  if (op.builtin == kTflConv2D || op.builtin == kTflDepthwiseConv2D) {
-    const bool dw = op.builtin == kTflDepthwiseConv2D;
-    const TflTensor& w = T(op.inputs[1]);
-    const int32_t* bias = nullptr;
-    if (op.inputs.size() > 2 && op.inputs[2] >= 0) bias = reinterpret_cast<const int32_t*>(T(op.inputs[2]).data);
-    const FbTable& o = op.options;
-    const bool same = o.Int8(0, 0) == 0;
-    const int sw = o.Int(1, 1), sh = o.Int(2, 1);
-    const int act = dw ? o.Int8(4, 0) : o.Int8(3, 0);
-    const int dlw = dw ? o.Int(5, 1) : o.Int(4, 1);
-    const int dlh = dw ? o.Int(6, 1) : o.Int(5, 1);
-    const int b = in.shape[0], ih = in.shape[1], iw = in.shape[2], ic = in.shape[3];
-    const int oc = dw ? w.shape[3] : w.shape[0];
-    const int kh = w.shape[1], kw = w.shape[2];
-    const int oh = ComputeOutSize(same, ih, kh, sh, dlh);
-    const int ow = ComputeOutSize(same, iw, kw, sw, dlw);
-    if (out.shape != std::vector<int>{b, oh, ow, oc}) return absl::InternalError("conv output shape mismatch");
-    const int ph = ComputePadding(sh, dlh, ih, kh, oh);
-    const int pw = ComputePadding(sw, dlw, iw, kw, ow);
-    std::vector<int32_t> mult, shift;
-    ConvMultipliers(Scale(in), w.scale, oc, Scale(out), !i8, &mult, &shift);
-    int32_t amin, amax;
-    ActivationRangeQuantized(act, Scale(out), Zp(out), i8, &amin, &amax);
-    const int32_t in_zp = Dom(in);
-    const int32_t w_zp = i8 ? 0 : Dom(w);  // int8 kernels ignore the filter zero point
-    const double M = static_cast<double>(b) * oh * ow;
-    if (!dw) {
-      // grouped (filter [oc][kh][kw][icg], icg != ic): the same packed layout
-      // with K = K_g, one row per output channel (GpuSupports checked that
-      // the group count divides both channel counts)
-      const int icg = w.shape[3];
-      const int groups = icg == ic ? 1 : ic / icg;
-      const int K = kh * kw * icg;
-      int kp = 0, np = 0;
-      bh_conv_packed_geometry(oc, K, &kp, &np);
-      const size_t wbytes = static_cast<size_t>(kp) * np;
-      const size_t tbytes = 12ull * oc;
-      auto blob = DeviceRegistry::Get().FindConst(ordinal_, ckey);
-      if (!blob) {
-        std::vector<int8_t> packed(wbytes);
-        std::vector<int32_t> tables(3ull * oc);
-        if (bh_pack_conv_weights(w.data, i8 ? 1 : 0, oc, K, kp, np, bias, in_zp, w_zp, packed.data(), tables.data()) != 0)
-          return absl::InternalError("weight packing failed");
-        std::copy(mult.begin(), mult.end(), tables.begin() + oc);
-        std::copy(shift.begin(), shift.end(), tables.begin() + 2 * oc);
-        blob = std::make_shared<DeviceBlob>(ordinal_, wbytes + tbytes);
-        if (!blob->ok() || !blob->Upload(0, packed.data(), wbytes) ||
-            !blob->Upload(wbytes, tables.data(), tbytes))
-          return HipErr(1, "upload conv operands");
-        DeviceRegistry::Get().PutConst(ordinal_, ckey, blob);
-      }
-      sg->consts.push_back(blob);
-      const int32_t* tab = reinterpret_cast<const int32_t*>(static_cast<char*>(blob->ptr()) + wbytes);
-      bh_conv_params& p = L.conv;
-      p = bh_conv_params{};
-      p.batch = b; p.in_h = ih; p.in_w = iw; p.in_c = ic;
-      p.out_h = oh; p.out_w = ow; p.out_c = oc; p.k_h = kh; p.k_w = kw;
-      p.stride_h = sh; p.stride_w = sw; p.dil_h = dlh; p.dil_w = dlw; p.pad_h = ph; p.pad_w = pw;
-      p.k_pad = kp; p.n_pad = np; p.in_xor = i8 ? 0 : 0x80;
-      p.in_zp = in_zp; p.w_zp = w_zp; p.out_zp = Zp(out); p.act_min = amin; p.act_max = amax;
-      p.input = in_ptr; p.output = out_ptr;
-      p.weights = static_cast<const int8_t*>(blob->ptr());
-      p.bias_eff = tab; p.mult = tab + oc; p.shift = tab + 2 * oc;
-      p.requant_fast = bh_conv_requant_fast_ok(mult.data(), shift.data(), oc, K, MaxAbs(bias, oc));
-      if (groups == 1) {
-        L.kind = Launch::kConv;
-        L.kernel = bh_conv2d_i8_kernel(&p);  // the kernel bh_conv2d_i8 dispatches to
-      } else {
-        L.kind = Launch::kConvGrouped;
-        L.conv_groups = groups;
-        const bh_conv_grouped_params gp{p, groups};
-        L.kernel = cpu ? "conv_grouped_host" : bh_conv2d_grouped_i8_kernel(&gp);
-      }
-      L.alg_ops = 2.0 * M * oc * K;
-      L.alg_bytes = static_cast<double>(in.num_elements()) + M * oc + static_cast<double>(oc) * K + 12.0 * oc;
-    } else {
-      const int dm = oc / ic;
-      const size_t wbytes = static_cast<size_t>(kh) * kw * oc;
-      const size_t wpad = (wbytes + 15) / 16 * 16;
-      const size_t tbytes = 12ull * oc;
-      // 3x3 / dm 1 layers also get the dot4 kernel's tap table (bh_pack_dw_taps)
-      const bool dot = kh == 3 && kw == 3 && dm == 1 && oc % 4 == 0;
-      const size_t pbytes = dot ? 16ull * oc : 0;
-      auto blob = DeviceRegistry::Get().FindConst(ordinal_, ckey);
-      if (!blob) {
-        std::vector<uint8_t> wd(wpad, 0);
-        for (size_t i = 0; i < wbytes; ++i) wd[i] = i8 ? w.data[i] : static_cast<uint8_t>(w.data[i] ^ 0x80);
-        std::vector<int32_t> tables(3ull * oc, 0);
-        for (int c = 0; c < oc; ++c) tables[c] = bias ? bias[c] : 0;
-        std::copy(mult.begin(), mult.end(), tables.begin() + oc);
-        std::copy(shift.begin(), shift.end(), tables.begin() + 2 * oc);
-        std::vector<int32_t> taps(pbytes / 4);
-        if (dot && bh_pack_dw_taps(reinterpret_cast<const int8_t*>(wd.data()), oc, tables.data(), in_zp, w_zp,
-                                   taps.data()) != 0)
-          return absl::InternalError("depthwise tap packing failed");
-        blob = std::make_shared<DeviceBlob>(ordinal_, wpad + tbytes + pbytes);
-        if (!blob->ok() || !blob->Upload(0, wd.data(), wpad) ||
-            !blob->Upload(wpad, tables.data(), tbytes) || (dot && !blob->Upload(wpad + tbytes, taps.data(), pbytes)))
-          return HipErr(1, "upload depthwise operands");
-        DeviceRegistry::Get().PutConst(ordinal_, ckey, blob);
-      }
-      sg->consts.push_back(blob);
-      const int32_t* tab = reinterpret_cast<const int32_t*>(static_cast<char*>(blob->ptr()) + wpad);
-      bh_dwconv_params& p = L.dw;
-      p = bh_dwconv_params{};
-      p.batch = b; p.in_h = ih; p.in_w = iw; p.in_c = ic;
-      p.out_h = oh; p.out_w = ow; p.out_c = oc; p.depth_multiplier = dm; p.k_h = kh; p.k_w = kw;
-      p.stride_h = sh; p.stride_w = sw; p.dil_h = dlh; p.dil_w = dlw; p.pad_h = ph; p.pad_w = pw;
-      p.in_xor = i8 ? 0 : 0x80; p.in_zp = in_zp; p.w_zp = w_zp; p.out_zp = Zp(out);
-      p.act_min = amin; p.act_max = amax; p.input = in_ptr; p.output = out_ptr;
-      p.weights = static_cast<const int8_t*>(blob->ptr());
-      p.bias = tab; p.mult = tab + oc; p.shift = tab + 2 * oc;
-      if (dot && !blob->host()) p.taps = tab + 3 * oc;
-      p.requant_fast = bh_conv_requant_fast_ok(mult.data(), shift.data(), oc, kh * kw, MaxAbs(bias, oc));
-      L.kind = Launch::kDwConv;
-      L.kernel = bh_dwconv2d_i8_kernel(&p);  // the kernel bh_dwconv2d_i8 dispatches to
-      L.alg_ops = 2.0 * M * oc * kh * kw;
-      L.alg_bytes = static_cast<double>(in.num_elements()) + M * oc + static_cast<double>(wbytes) + 12.0 * oc;
+  bool emit = true;
+  auto lower = [&]() -> absl::Status {
+    switch (op.builtin) {
+      case kTflConv2D: return LowerConv(model, oi, in_ptr, out_ptr, ckey, sg, &L);
+      case kTflDepthwiseConv2D: return LowerDepthwise(model, oi, in_ptr, out_ptr, ckey, sg, &L);
+      case kTflFullyConnected: return LowerFc(model, oi, in_ptr, out_ptr, ckey, sg, &L);
+      case kTflTransposeConv: return LowerTransposeConv(model, oi, out_ptr, ckey, sg, &L);
+      case kTflAdd: case kTflSub: case kTflMul: return LowerEltwise(model, oi, in_ptr, out_ptr, sg, &L);
+      case kTflAveragePool2D: case kTflMaxPool2D: return LowerPool(model, oi, in_ptr, out_ptr, &L);
+      case kTflMean: return LowerMean(model, oi, in_ptr, out_ptr, &L);
+      case kTflArgMax: case kTflArgMin: return LowerArgMinMax(model, oi, in_ptr, out_ptr, &L);
+      case kTflBatchMatMul: return LowerBatchMatMul(model, oi, in_ptr, out_ptr, sg, &L);
+      case kTflCustom:
+        return cpu ? LowerDetectionHost(model, oi, in_ptr, sg, &L) : LowerDetectionGpu(model, oi, sg, &L);
+      case kTflReshape: case kTflSqueeze:  // same bytes, new dims
+        L.kind = Launch::kCopy;
+        L.kernel = "copy";
+        L.src = in_ptr;
+        L.dst = out_ptr;
+        L.bytes = meta_[op.outputs[0]]->bytes;
+        L.alg_bytes = 2.0 * L.bytes;
+        emit = L.src != L.dst;  // aliased slot: nothing to move
+        return absl::OkStatus();
+      default: return LowerGlue(model, oi, in_ptr, out_ptr, ckey, sg, &L);
     }
-  } else if (op.builtin == kTflFullyConnected) {
-    const TflTensor& w = T(op.inputs[1]);
-    const int32_t* bias = nullptr;
-    if (op.inputs.size() > 2 && op.inputs[2] >= 0) bias = reinterpret_cast<const int32_t*>(T(op.inputs[2]).data);
-    const int act = op.options.valid() ? op.options.Int8(0, 0) : 0;
-    const int units = w.shape[0], depth = w.shape[1];
-    const int rows = static_cast<int>(in.num_elements() / depth);
-    const int depth_pad = (depth + 15) / 16 * 16;
-    int32_t mult, shift, amin, amax;
-    FullyConnectedMultiplier(Scale(in), Scale(w), Scale(out), &mult, &shift);
-    ActivationRangeQuantized(act, Scale(out), Zp(out), i8, &amin, &amax);
-    const int32_t in_zp = Dom(in), w_zp = Dom(w);
-    const size_t wbytes = static_cast<size_t>(units) * depth_pad;
-    const size_t tbytes = 12ull * units;
-    auto blob = DeviceRegistry::Get().FindConst(ordinal_, ckey);
-    if (!blob) {
-      std::vector<int8_t> packed(wbytes, 0);
-      std::vector<int32_t> tables(3ull * units);
-      for (int u = 0; u < units; ++u) {
-        int64_t s = 0;
-        for (int k = 0; k < depth; ++k) {
-          const uint8_t raw = w.data[static_cast<size_t>(u) * depth + k];
-          const int v = i8 ? static_cast<int>(static_cast<int8_t>(raw)) : static_cast<int>(raw) - 128;
-          packed[static_cast<size_t>(u) * depth_pad + k] = static_cast<int8_t>(v);
-          s += v;
-        }
-        tables[u] = static_cast<int32_t>((bias ? bias[u] : 0) - static_cast<int64_t>(in_zp) * s +
-                                         static_cast<int64_t>(depth) * in_zp * w_zp);
-        tables[units + u] = mult;
-        tables[2 * units + u] = shift;
-      }
-      blob = std::make_shared<DeviceBlob>(ordinal_, wbytes + tbytes);
-      if (!blob->ok() || !blob->Upload(0, packed.data(), wbytes) ||
-          !blob->Upload(wbytes, tables.data(), tbytes))
-        return HipErr(1, "upload fc operands");
-      DeviceRegistry::Get().PutConst(ordinal_, ckey, blob);
-    }
-    sg->consts.push_back(blob);
-    const int32_t* tab = reinterpret_cast<const int32_t*>(static_cast<char*>(blob->ptr()) + wbytes);
-    bh_fc_params& p = L.fc;
-    p = bh_fc_params{};
-    p.rows = rows; p.depth = depth; p.depth_pad = depth_pad; p.units = units;
-    p.in_xor = i8 ? 0 : 0x80; p.in_zp = in_zp; p.w_zp = w_zp; p.out_zp = Zp(out);
-    p.act_min = amin; p.act_max = amax; p.input = in_ptr; p.output = out_ptr;
-    p.weights = static_cast<const int8_t*>(blob->ptr());
-    p.bias_eff = tab; p.mult = tab + units; p.shift = tab + 2 * units;
-    L.kind = Launch::kFc;
-    L.kernel = "fc_kernel";
-    L.alg_ops = 2.0 * rows * units * depth;
-    L.alg_bytes = static_cast<double>(rows) * depth + static_cast<double>(rows) * units +
-                  static_cast<double>(units) * depth + 12.0 * units;
-  } else if (op.builtin == kTflAdd || op.builtin == kTflSub || op.builtin == kTflMul) {
-    const TflTensor& b = T(op.inputs[1]);
-    void* b_ptr = nullptr;
-    RETURN_STATUS_IF(DevicePtr(model, op.inputs[1], sg, &b_ptr));
-    const int act = op.options.valid() ? op.options.Int8(0, 0) : 0;
-    bh_eltwise_params& p = L.elt;
-    p = bh_eltwise_params{};
-    p.in_signed = i8 ? 1 : 0;
-    Shape4(in.shape, p.shape_a);
-    Shape4(b.shape, p.shape_b);
-    Shape4(out.shape, p.shape_o);
-    p.a_off = -Zp(in);
-    p.b_off = -Zp(b);
-    p.o_off = Zp(out);
-    ActivationRangeQuantized(act, Scale(out), Zp(out), i8, &p.act_min, &p.act_max);
-    if (op.builtin == kTflMul) {
-      p.kind = BH_ELT_MUL;
-      MulMultiplier(Scale(in), Scale(b), Scale(out), &p.o_mult, &p.o_shift);
-    } else {
-      p.kind = BH_ELT_ADD;
-      const AddParams ap = AddSubParams(Scale(in), Scale(b), Scale(out), op.builtin == kTflSub);
-      p.left_shift = ap.left_shift;
-      p.a_mult = ap.m1; p.a_shift = ap.s1;
-      p.b_mult = ap.m2; p.b_shift = ap.s2;
-      p.o_mult = ap.mo; p.o_shift = ap.so;
-    }
-    p.a = in_ptr; p.b = b_ptr; p.out = out_ptr;
-    L.kind = Launch::kEltwise;
-    L.kernel = "eltwise_kernel";
-    L.alg_bytes = static_cast<double>(in.num_elements() + b.num_elements() + out.num_elements());
-  } else if (op.builtin == kTflAveragePool2D || op.builtin == kTflMaxPool2D) {
-    const FbTable& o = op.options;
-    const bool same = o.Int8(0, 0) == 0;
-    const int sw = o.Int(1, 1), sh = o.Int(2, 1), fw = o.Int(3, 1), fh = o.Int(4, 1);
-    const int act = o.Int8(5, 0);
-    bh_pool_params& p = L.pool;
-    p = bh_pool_params{};
-    p.kind = op.builtin == kTflAveragePool2D ? BH_POOL_AVG : BH_POOL_MAX;
-    p.in_signed = i8 ? 1 : 0;
-    p.batch = in.shape[0]; p.in_h = in.shape[1]; p.in_w = in.shape[2]; p.channels = in.shape[3];
-    p.out_h = ComputeOutSize(same, p.in_h, fh, sh, 1);
-    p.out_w = ComputeOutSize(same, p.in_w, fw, sw, 1);
-    p.f_h = fh; p.f_w = fw; p.stride_h = sh; p.stride_w = sw;
-    p.pad_h = ComputePadding(sh, 1, p.in_h, fh, p.out_h);
-    p.pad_w = ComputePadding(sw, 1, p.in_w, fw, p.out_w);
-    ActivationRangeQuantized(act, Scale(out), Zp(out), i8, &p.act_min, &p.act_max);
-    p.input = in_ptr; p.output = out_ptr;
-    L.kind = Launch::kPool;
-    L.kernel = "pool_kernel";
-    L.alg_bytes = static_cast<double>(in.num_elements() + out.num_elements());
-  } else if (op.builtin == kTflCustom && !cpu) {
-    RETURN_STATUS_IF(LowerDetectionGpu(model, oi, sg, &L));
-  } else if (op.builtin == kTflCustom) {
-    // TFLite_Detection_PostProcess on the CPU worker (CpuSupports)
-    CpuDetectionParams& p = L.det;
-    if (!DetectionSupported(d, op, &p)) return absl::InternalError("unsupported custom op " + op.custom_code);
-    void* scores = nullptr;
-    void* anchors = nullptr;
-    void* outs[4];
-    RETURN_STATUS_IF(DevicePtr(model, op.inputs[1], sg, &scores));
-    RETURN_STATUS_IF(DevicePtr(model, op.inputs[2], sg, &anchors));
-    for (int k = 0; k < 4; ++k) RETURN_STATUS_IF(DevicePtr(model, op.outputs[k], sg, &outs[k]));
-    p.box_encodings = static_cast<const float*>(in_ptr);
-    p.class_scores = static_cast<const float*>(scores);
-    p.anchors = static_cast<const float*>(anchors);
-    p.out_boxes = static_cast<float*>(outs[0]);
-    p.out_classes = static_cast<float*>(outs[1]);
-    p.out_scores = static_cast<float*>(outs[2]);
-    p.out_num = static_cast<float*>(outs[3]);
-    L.kind = Launch::kDetectionPost;
-    L.kernel = "detection_postprocess_host";
-  } else if (op.builtin == kTflMean) {
-    // MEAN: host kernel on a CPU worker, mean_kernel on the GPU
-    CpuMeanParams& p = L.mean;
-    p = CpuMeanParams{};
-    if (!MeanArgs(d, op, &p.outer, &p.reduce, &p.inner)) return absl::InternalError("unsupported MEAN");
-    p.type = in.type == DataType::kFloat32 ? 0 : (in.type == DataType::kInt8 ? 1 : 2);
-    if (p.type) {
-      // optimized_integer_ops::Mean (TFLite 2.9.2): the float products as
-      // written there, then QuantizeMultiplier of the float scale
-      const float in_scale = Scale(in), out_scale = Scale(out);
-      const float n = static_cast<float>(p.reduce);
-      p.bias = Zp(out) - static_cast<int32_t>(Zp(in) * in_scale / out_scale);
-      const float real_scale = in_scale / (n * out_scale);
-      int shift = 0;
-      QuantizeMultiplier(static_cast<double>(real_scale), &p.multiplier, &shift);
-      p.shift = shift;
-    }
-    p.input = in_ptr;
-    p.output = out_ptr;
-    L.kind = Launch::kMean;
-    L.kernel = device_flag_ == DeviceFlag::kGPU ? "mean_kernel" : "mean_host";
-    L.alg_bytes = static_cast<double>(meta_[op.inputs[0]]->bytes + meta_[op.outputs[0]]->bytes);
-  } else if (op.builtin == kTflArgMax || op.builtin == kTflArgMin) {
-    bh_argminmax_params& p = L.argmm;
-    p = bh_argminmax_params{};
-    if (!ArgMinMaxArgs(d, op, &p.outer, &p.axis_len, &p.inner, &p.out_bytes))
-      return absl::InternalError("unsupported ARG_MAX / ARG_MIN");
-    p.in_type = in.type == DataType::kFloat32 ? BH_ARG_F32 : (i8 ? BH_ARG_I8 : BH_ARG_U8);
-    p.is_min = op.builtin == kTflArgMin ? 1 : 0;
-    p.input = in_ptr;
-    p.output = out_ptr;
-    L.kind = Launch::kArgMinMax;
-    L.kernel = cpu ? "argminmax_host" : bh_argminmax_kernel(&p);
-    L.alg_bytes = static_cast<double>(meta_[op.inputs[0]]->bytes + meta_[op.outputs[0]]->bytes);
-  } else if (op.builtin == kTflBatchMatMul) {
-    RETURN_STATUS_IF(LowerBatchMatMul(model, oi, in_ptr, out_ptr, sg, &L));
-  } else if (op.builtin == kTflTransposeConv) {
-    RETURN_STATUS_IF(LowerTransposeConv(model, oi, out_ptr, ckey, sg, &L));
-  } else if (op.builtin != kTflReshape && op.builtin != kTflSqueeze) {
-    RETURN_STATUS_IF(LowerGlue(model, oi, in_ptr, out_ptr, ckey, sg, &L));
-  } else {  // RESHAPE / SQUEEZE: same bytes, new dims
-    L.kind = Launch::kCopy;
-    L.kernel = "copy";
-    L.src = in_ptr;
-    L.dst = out_ptr;
-    L.bytes = meta_[op.outputs[0]]->bytes;
-    L.alg_bytes = 2.0 * L.bytes;
-    if (L.src == L.dst) return absl::OkStatus();  // aliased slot: nothing to move
-  }
-  if (L.kind == Launch::kConv) {
-    const bh_conv_params c = L.conv;
-    const long M = static_cast<long>(c.batch) * c.out_h * c.out_w;
-    if (c.k_h == 1 && c.k_w == 1 && c.stride_h == 1 && c.stride_w == 1 && M <= 4) {
-      // a 1x1 conv over a handful of pixels (the classifier at batch 1) is
-      // a GEMV: run it on the weight-streaming FC kernel with the same
-      // packed operands (Bt rows are K-contiguous, bias_eff identical)
-      Launch F;
-      F.kind = Launch::kFc;
-      F.op_index = oi;
-      F.out_tensor = L.out_tensor;
-      bh_fc_params& f = F.fc;
-      f = bh_fc_params{};
-      f.rows = static_cast<int>(M); f.depth = c.in_c; f.depth_pad = c.k_pad; f.units = c.out_c;
-      f.in_xor = c.in_xor; f.in_zp = c.in_zp; f.w_zp = c.w_zp; f.out_zp = c.out_zp;
-      f.act_min = c.act_min; f.act_max = c.act_max; f.input = c.input; f.output = c.output;
-      f.weights = c.weights; f.bias_eff = c.bias_eff; f.mult = c.mult; f.shift = c.shift;
-      F.kernel = "fc_kernel";
-      F.alg_bytes = L.alg_bytes;
-      F.alg_ops = L.alg_ops;
-      L = F;
-    } else {
-      TryFuseResidualAdd(model, oi, sg, &L);
-    }
-  } else if (L.kind == Launch::kConvGrouped) {
-    TryFuseResidualAdd(model, oi, sg, &L);  // the grouped kernel shares the dense epilogue
-  }
-  sg->launches.push_back(L);
+  };
+  RETURN_STATUS_IF(IsFloatOp(d, op) ? LowerFloat(model, oi, in_ptr, out_ptr, ckey, sg, &L, &emit) : lower());
+  if (emit) sg->launches.push_back(L);
   return absl::OkStatus();
 }
-
 
 }  // namespace hip
 }  // namespace band

@@ -1,0 +1,149 @@
+// One Args function per op family: it resolves an op's shapes and options,
+// applies the limits of the kernels and names what it refuses.  The support
+// checks (GpuSupports / FloatSupports), the lowering (lower.cc) and the
+// job-batch rule (model.cc) all call the same function, so what a worker
+// accepts is what the lowering can handle.  Needs only the TFLite reader and
+// quant.cc: no device, no executor.
+#pragma once
+
+#include <cstdint>
+#include <vector>
+
+#include "backend/hip/cpu_kernels.h"
+#include "backend/hip/quant.h"
+#include "backend/hip/tflite_reader.h"
+#include "band_hip_kernels.h"
+
+namespace band {
+namespace hip {
+namespace ex {
+
+inline bool IsQ8(DataType t) { return t == DataType::kInt8 || t == DataType::kUInt8; }
+
+// zero point in the kernels' int8 domain (uint8 values are XOR 0x80 = x-128)
+inline int32_t Dom(const TflTensor& t) {
+  const int32_t zp = t.zero_point.empty() ? 0 : static_cast<int32_t>(t.zero_point[0]);
+  return t.type == DataType::kUInt8 ? zp - 128 : zp;
+}
+inline int32_t Zp(const TflTensor& t) { return t.zero_point.empty() ? 0 : static_cast<int32_t>(t.zero_point[0]); }
+inline float Scale(const TflTensor& t) { return t.scale.empty() ? 0.0f : t.scale[0]; }
+inline bool HasQ(const TflTensor& t) { return !t.scale.empty(); }
+
+inline void Shape4(const std::vector<int>& s, int* out) {
+  const int pad = 4 - static_cast<int>(s.size());
+  for (int i = 0; i < 4; ++i) out[i] = i < pad ? 1 : s[i - pad];
+}
+
+// TFLite fp16 post-training quantization keeps constants in float16 behind
+// DEQUANTIZE ops; such a tensor is a constant of the float graph
+const TflOperator* ProducerOf(const TflModel& m, int t);
+bool FoldableF16(const TflModel& m, int t);
+inline bool ConstFloat(const TflModel& m, int t) {
+  return t >= 0 && ((m.tensors[t].is_const() && m.tensors[t].type == DataType::kFloat32) || FoldableF16(m, t));
+}
+
+// CONV_2D (dense and grouped), DEPTHWISE_CONV_2D and TRANSPOSE_CONV, int8 /
+// uint8 and float32.  TRANSPOSE_CONV: in_* is the op's input, out_* its output
+// tensor (not the constant output_shape input: a job-batch variant scales axis
+// 0 of tensors, not of constants); pad_* as transpose_conv.cc computes it, for
+// a conv whose input is the output.
+struct ConvGeometry {
+  int batch, in_h, in_w, in_c, out_h, out_w, out_c;
+  int k_h, k_w, stride_h, stride_w, dil_h, dil_w, pad_h, pad_w;
+  int act;               // schema ActivationFunctionType
+  int groups;            // CONV_2D: in_c / the filter's input channels
+  int depth_multiplier;  // DEPTHWISE_CONV_2D: out_c / in_c
+  int filter, input, bias;  // tensor indices; bias -1: none
+};
+// g may be null (a pure check); *why names what was refused
+bool ConvArgs(const TflModel& m, const TflOperator& op, ConvGeometry* g, const char** why = nullptr);
+
+// FULLY_CONNECTED: input viewed as [rows][depth], filter [units][depth]
+struct FcGeometry {
+  int rows, depth, units, act;
+  int filter, bias;  // tensor indices; bias -1: none
+};
+bool FcArgs(const TflModel& m, const TflOperator& op, FcGeometry* g, const char** why = nullptr);
+
+// AVERAGE_POOL_2D / MAX_POOL_2D
+struct PoolGeometry {
+  int batch, in_h, in_w, channels, out_h, out_w;
+  int f_h, f_w, stride_h, stride_w, pad_h, pad_w, act;
+};
+bool PoolArgs(const TflModel& m, const TflOperator& op, PoolGeometry* g, const char** why = nullptr);
+
+// the rank-4 shapes of a binary op's operands and output; each operand dim is
+// the output's or 1
+struct BroadcastShapes {
+  int a[4], b[4], o[4];
+};
+bool BroadcastArgs(const TflModel& m, const TflOperator& op, BroadcastShapes* s, const char** why = nullptr);
+
+// BATCH_MATMUL (int8 / float32): shapes, adj_x / adj_y and numpy-matmul
+// broadcasting of the leading dims resolved to the stride form of
+// bh_batch_matmul_params (pointers stay null) - the only place that does; the
+// support checks, the lowering, the host twin's caller and the job-batch rule
+// all come through here.  int8: one per-tensor (mult, shift) from
+// FullyConnectedMultiplier, the zero points of both operands and the output.
+// *batch_axis_ok: axis 0 of the output and of every non-constant operand is
+// the same matmul batch dim (rank >= 3, the output's rank) and a constant
+// operand broadcasts along it (lower rank, or a leading 1), so a job-batch
+// variant that scales axis 0 computes each job's product.  *why names what
+// was refused.
+bool BatchMatMulArgs(const TflModel& m, const TflOperator& op, bh_batch_matmul_params* p,
+                     const char** why = nullptr, bool* batch_axis_ok = nullptr);
+
+// MIRROR_PAD paddings (constant [rank][2] int32 / int64) and mode
+// (MirrorPadOptions.mode: 0 REFLECT, 1 SYMMETRIC -> bh_pad_params.mode 1 / 2)
+bool MirrorPadArgs(const TflModel& m, const TflOperator& op, std::vector<int64_t>* pads, int* mode);
+
+// MEAN: the reduced axes (constant int32, negatives resolved) must be one
+// contiguous run; 8-bit tensors only in the form TFLite 2.9.2 runs through
+// optimized_integer_ops::Mean / optimized_ops::Mean (4-D, keep_dims, axes
+// {1, 2}), the one restated by CpuMean.
+bool MeanArgs(const TflModel& m, const TflOperator& op, long* outer, long* reduce, long* inner);
+
+// ARG_MAX / ARG_MIN (arg_min_max.cc): int8 / uint8 / float32 input of rank
+// 1-4 viewed as [outer][axis_len][inner]; the axis is a constant int32 /
+// int64 scalar or one-element tensor (negatives resolved); the output is
+// int32 or int64 as ArgMaxOptions / ArgMinOptions.output_type says, with
+// outer * inner elements.  *why (optional) names what failed.
+bool ArgMinMaxArgs(const TflModel& m, const TflOperator& op, long* outer, long* axis_len, long* inner,
+                   int* out_bytes, int* axis_out = nullptr, const char** why = nullptr);
+
+// The re-indexing ops: TRANSPOSE, STRIDED_SLICE, SLICE, SPLIT, SPLIT_V,
+// SPACE_TO_DEPTH, DEPTH_TO_SPACE
+inline bool IsReindexOp(int builtin) {
+  return builtin == kTflTranspose || builtin == kTflStridedSlice || builtin == kTflSlice || builtin == kTflSplit ||
+         builtin == kTflSplitV || builtin == kTflSpaceToDepth || builtin == kTflDepthToSpace;
+}
+// the values of a constant int32 / int64 tensor
+bool ConstInts(const TflTensor& t, std::vector<int64_t>* v);
+
+// Resolves output `oi` of a re-indexing op to the map bh_reindex / CpuReindex
+// run (map->input / output stay null): the output's extents (rank <= 6),
+// signed input strides in elements and an input element offset.  Semantics
+// are numpy's: np.transpose(x, perm); x[b:b+s] per axis with size -1 = to the
+// end; basic indexing x[b:e:s] per axis (negative indices, out-of-range
+// clamping, negative strides; a begin_mask / end_mask bit makes the bound None,
+// a shrink_axis_mask bit makes the axis the index x[b]); np.split;
+// DEPTH_TO_SPACE out[n, h bs + by, w bs + bx, c] = in[n, h, w, (by bs + bx) C' + c]
+// and SPACE_TO_DEPTH its inverse.  Starts and strides come from the constants
+// and the input's shape, extents from the OUTPUT tensor's shape, which must be
+// what the constants resolve to - except that an output may take the whole of
+// input axis 0 from element 0 at stride 1 whatever end / size say (a job-batch
+// variant scales axis 0 of every tensor, not the constants).  *whole_batch:
+// the output's axis 0 is the input's, in full (the job-batch rule).  *why names
+// what was refused.
+bool ReindexArgs(const TflModel& m, const TflOperator& op, int oi, bh_reindex_params* map,
+                 const char** why = nullptr, bool* whole_batch = nullptr);
+
+// TFLite_Detection_PostProcess in the form the host kernel and the device
+// kernels (kernels/detection.hip) implement.  batch: the images of a
+// job-batch variant (the leading dimension of the op's tensors; the anchors
+// are shared) - without it only one image is accepted.
+bool DetectionSupported(const TflModel& m, const TflOperator& op, CpuDetectionParams* p, int* batch = nullptr);
+
+}  // namespace ex
+}  // namespace hip
+}  // namespace band

@@ -2,7 +2,7 @@
 
 #include <cstdio>
 
-#include "backend/hip/executor_internal.h"
+#include "backend/hip/lower_args.h"
 
 namespace band {
 namespace hip {

@@ -114,44 +114,27 @@ bool HipModelExecutor::GpuSupports(const TflModel& m, const TflOperator& op, std
         const TflTensor& b = T(op.inputs[2]);
         if (!b.is_const() || b.type != DataType::kInt32) return no("bias must be constant int32");
       }
-      if (op.builtin == kTflFullyConnected) {
-        if (w.shape.size() != 2 || w.shape[1] <= 0) return no("FC weights must be 2-D");
-        if (in.num_elements() % static_cast<size_t>(w.shape[1]) != 0) return no("FC input/depth mismatch");
-        return true;
-      }
-      if (in.shape.size() != 4 || w.shape.size() != 4 || out.shape.size() != 4) return no("conv needs 4-D");
-      if (op.builtin == kTflConv2D && w.shape[3] != in.shape[3]) {
-        // grouped: groups = in_c / filter_in_c must divide both channel counts
-        if (w.shape[3] <= 0 || in.shape[3] % w.shape[3] != 0)
-          return no("grouped conv: input channels not a multiple of the filter's");
-        if (w.shape[0] % (in.shape[3] / w.shape[3]) != 0)
-          return no("grouped conv: output channels not a multiple of the group count");
-      }
-      if (op.builtin == kTflDepthwiseConv2D && (in.shape[3] == 0 || w.shape[3] % in.shape[3] != 0))
-        return no("bad depth multiplier");
-      return true;
+      const char* r = "";
+      const bool ok = op.builtin == kTflFullyConnected ? FcArgs(m, op, nullptr, &r) : ConvArgs(m, op, nullptr, &r);
+      return ok ? true : no(r);
     }
     case kTflAdd:
     case kTflSub:
     case kTflMul: {
-      if (op.inputs.size() != 2 || op.inputs[1] < 0) return no("binary op needs 2 inputs");
+      const char* r = "";
+      if (!BroadcastArgs(m, op, nullptr, &r)) return no(r);
       const TflTensor& b = T(op.inputs[1]);
       if (!IsQ8(in.type) || b.type != in.type || out.type != in.type) return no("only int8/uint8 quantized");
       if (!HasQ(in) || !HasQ(b) || !HasQ(out)) return no("missing quantization");
-      if (in.shape.size() > 4 || b.shape.size() > 4 || out.shape.size() > 4) return no("rank > 4");
-      int sa[4], sb[4], so[4];
-      Shape4(in.shape, sa);
-      Shape4(b.shape, sb);
-      Shape4(out.shape, so);
-      for (int d = 0; d < 4; ++d)
-        if ((sa[d] != so[d] && sa[d] != 1) || (sb[d] != so[d] && sb[d] != 1)) return no("bad broadcast");
       return true;
     }
     case kTflAveragePool2D:
-    case kTflMaxPool2D:
-      if (!IsQ8(in.type) || out.type != in.type || in.shape.size() != 4) return no("only int8/uint8 4-D");
+    case kTflMaxPool2D: {
+      if (!IsQ8(in.type) || out.type != in.type) return no("only int8/uint8");
       if (!HasQ(out)) return no("missing quantization");
-      return true;
+      const char* r = "";
+      return PoolArgs(m, op, nullptr, &r) ? true : no(r);
+    }
     case kTflReshape:
     case kTflSqueeze:
       if (out.type != in.type || out.num_elements() != in.num_elements()) return no("size mismatch");
@@ -259,13 +242,12 @@ bool HipModelExecutor::GpuSupports(const TflModel& m, const TflOperator& op, std
       if (x.type != DataType::kInt8 || w.type != DataType::kInt8 || out.type != DataType::kInt8)
         return no("int8 only (reference_integer_ops::TransposeConv)");
       if (!HasQ(x) || !HasQ(w) || !HasQ(out)) return no("missing quantization");
-      if (x.shape.size() != 4 || w.shape.size() != 4 || out.shape.size() != 4 || w.shape[3] != x.shape[3])
-        return no("4-D, filter [oc][kh][kw][ic]");
       if (op.inputs.size() > 3 && op.inputs[3] >= 0) {
         const TflTensor& b = T(op.inputs[3]);
         if (!b.is_const() || b.type != DataType::kInt32) return no("bias must be constant int32");
       }
-      return true;
+      const char* r = "";
+      return ConvArgs(m, op, nullptr, &r) ? true : no(r);
     }
     case kTflResizeBilinear:
       if ((in.type != DataType::kInt8 && in.type != DataType::kUInt8) || out.type != in.type || in.shape.size() != 4 ||
@@ -363,10 +345,12 @@ absl::StatusOr<ModelSpec> HipModelExecutor::InvestigateModelSpec(interface::IMod
     const DeviceFlag flag = static_cast<DeviceFlag>(f);
     unsupported[flag] = {};
     if (flag == DeviceFlag::kCPU) continue;
-    if (flag != DeviceFlag::kGPU || !gpu) {
+    if (flag != DeviceFlag::kGPU) {
       unavailable.insert(flag);
       continue;
     }
+    // the kGPU set is host code: a machine without the device reports it too
+    if (!gpu) unavailable.insert(flag);
     for (int i = 0; i < num_ops; ++i)
       if (!GpuSupportsHere(d, d.ops[i], nullptr)) unsupported[flag].insert(i);
     // Placement at a CPU-only boundary: a DEQUANTIZE whose every consumer

@@ -18,6 +18,7 @@
 // band/worker.cc:274-291).
 #pragma once
 
+#include <functional>
 #include <map>
 #include <memory>
 #include <set>
@@ -31,6 +32,7 @@
 #include "backend/hip/model.h"
 #include "backend/hip/tensor.h"
 #include "backend/hip/job_batching.h"
+#include "backend/hip/lower_args.h"
 #include "band/interface/model_executor.h"
 #include "band_hip_kernels.h"
 
@@ -237,10 +239,32 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   // measured (no GPU stream, or a launch failed).
   double TimeLaunches(const std::vector<const Launch*>& ls, int iters);
   absl::Status DevicePtr(const HipModel& model, int tensor, PreparedSubgraph* sg, void** ptr);
-  // host-built constant (table) resident on this executor's device, shared
-  // across executors by `key`
+  // A constant of `bytes` resident on this executor's device, shared across
+  // executors by `key` and kept alive by sg: the registry's blob when one is
+  // there, else `fill` builds it in a zeroed host buffer and it is uploaded
+  absl::Status ConstBlob(const std::string& key, size_t bytes, PreparedSubgraph* sg,
+                         const std::function<absl::Status(uint8_t*)>& fill, std::shared_ptr<DeviceBlob>* blob);
+  // ConstBlob of bytes that exist already (a table, a model constant)
   absl::Status UploadConst(const std::string& key, const void* data, size_t bytes, PreparedSubgraph* sg,
                            const void** dev);
+  // Lower's cases: each takes its geometry from the family's Args function
+  // (lower_args.h) and fills *l; the int8 conv forms end in the 1x1-GEMV-to-FC
+  // rewrite or the residual-ADD fold
+  absl::Status LowerConv(const HipModel& model, int op_index, void* in_ptr, void* out_ptr, const std::string& ckey,
+                         PreparedSubgraph* sg, Launch* l);
+  // the packed int8 conv launch LowerConv and LowerTransposeConv end in
+  absl::Status PackedConv(const HipModel& model, int op_index, const ex::ConvGeometry& g, bool flip,
+                          const void* in_ptr, void* out_ptr, const std::string& ckey, PreparedSubgraph* sg, Launch* l);
+  absl::Status LowerDepthwise(const HipModel& model, int op_index, void* in_ptr, void* out_ptr,
+                              const std::string& ckey, PreparedSubgraph* sg, Launch* l);
+  absl::Status LowerFc(const HipModel& model, int op_index, void* in_ptr, void* out_ptr, const std::string& ckey,
+                       PreparedSubgraph* sg, Launch* l);
+  absl::Status LowerEltwise(const HipModel& model, int op_index, void* in_ptr, void* out_ptr, PreparedSubgraph* sg,
+                            Launch* l);
+  absl::Status LowerPool(const HipModel& model, int op_index, void* in_ptr, void* out_ptr, Launch* l);
+  absl::Status LowerMean(const HipModel& model, int op_index, void* in_ptr, void* out_ptr, Launch* l);
+  absl::Status LowerArgMinMax(const HipModel& model, int op_index, void* in_ptr, void* out_ptr, Launch* l);
+  absl::Status LowerDetectionHost(const HipModel& model, int op_index, void* in_ptr, PreparedSubgraph* sg, Launch* l);
   absl::Status LowerFloat(const HipModel& model, int op_index, void* in_ptr, void* out_ptr, const std::string& ckey,
                           PreparedSubgraph* sg, Launch* l, bool* emit);
   absl::Status LowerTransposeConv(const HipModel& model, int op_index, void* out_ptr, const std::string& ckey,
