@@ -91,6 +91,18 @@ class MeanParams(ctypes.Structure):
         (n, c_int32) for n in ("multiplier", "shift", "bias")] + [("input", c_void_p), ("output", c_void_p)]
 
 
+class MeanRowsParams(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_long), ("depth", c_int), ("type", c_int), ("exact", c_int),
+                ("scale", ctypes.c_float), ("bias", ctypes.c_float), ("out_zp", c_int32),
+                ("input", c_void_p), ("output", c_void_p)]
+
+
+class LayerNormParams(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_long), ("depth", c_int), ("mean_x", MeanRowsParams), ("mean_d", MeanRowsParams)] + [
+        (n, EltwiseParams) for n in ("sqdiff", "add_eps", "mul_gamma", "mul_x", "mul_m", "sub_beta", "add_out")] + [
+        ("eps_q", c_int32)] + [(n, c_void_p) for n in ("rsqrt_table", "input", "gamma", "beta", "output")]
+
+
 class DetectionParams(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("batch", "num_boxes", "num_classes", "num_classes_with_background",
                                      "max_detections")] + [
@@ -304,6 +316,12 @@ KERNEL_SYMBOLS = {
     "bh_irb_lds_bytes": (c_size_t, [ctypes.POINTER(IrbParams)]),
     "bh_chain_i8": (c_int, [ctypes.POINTER(ChainParams), c_void_p]),
     "bh_mean": (c_int, [ctypes.POINTER(MeanParams), c_void_p]),
+    "bh_mean_rows": (c_int, [ctypes.POINTER(MeanRowsParams), c_void_p]),
+    "bh_mean_rows_kernel": (ctypes.c_char_p, [ctypes.POINTER(MeanRowsParams)]),
+    "bh_mean_rows_check": (c_int, [ctypes.POINTER(MeanRowsParams)]),
+    "bh_layernorm_i8": (c_int, [ctypes.POINTER(LayerNormParams), c_void_p]),
+    "bh_layernorm_i8_kernel": (ctypes.c_char_p, [ctypes.POINTER(LayerNormParams)]),
+    "bh_layernorm_i8_check": (c_int, [ctypes.POINTER(LayerNormParams)]),
     "bh_detection_scratch_bytes": (c_size_t, [c_int, c_int]),
     "bh_detection_postprocess": (c_int, [ctypes.POINTER(DetectionParams), c_void_p]),
     "bh_chain_lds_bytes": (c_size_t, [ctypes.POINTER(ChainParams)]),

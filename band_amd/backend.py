@@ -84,6 +84,13 @@ _abi.BACKEND_SYMBOLS.update({
     "bhx_launch_kernels": (c_int, _KEY + [ctypes.POINTER(ctypes.c_char_p), c_int, ctypes.POINTER(c_int)]),
     "bhx_cpu_conv_grouped": (c_int, [ctypes.POINTER(_abi.ConvGroupedParams)]),
     "bhx_cpu_batch_matmul": (c_int, [ctypes.POINTER(_abi.BatchMatMulParams), c_int]),
+    "bhx_cpu_mean_rows": (c_int, [ctypes.POINTER(_abi.MeanRowsParams)]),
+    "bhx_cpu_eltwise": (c_int, [ctypes.POINTER(_abi.EltwiseParams)]),
+    "bhx_cpu_unary_f32": (c_int, [c_int, c_void_p, c_void_p, ctypes.c_long]),
+    "bhx_rsqrt_table": (c_int, [ctypes.c_float, c_int, ctypes.c_float, c_int, c_void_p]),
+    "bhx_gelu_table": (c_int, [c_int, c_int, ctypes.c_float, c_int, ctypes.c_float, c_int, c_void_p]),
+    "bhx_squared_difference_params": (c_int, [ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                              ctypes.POINTER(ctypes.c_int32)]),
     "bhx_prepare_job_batches": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_uint64, c_int]),
     "bhx_max_job_batch": (c_int, _KEY + [ctypes.POINTER(c_int)]),
     "bhx_job_slot_view": (c_int, _KEY + [c_int, c_int, c_int, ctypes.POINTER(TensorInfo)]),

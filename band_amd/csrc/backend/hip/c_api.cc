@@ -488,4 +488,54 @@ int bhx_cpu_batch_matmul(const void* batch_matmul_params, int is_float32) {
   return 0;
 }
 
+int bhx_cpu_mean_rows(const void* mean_rows_params) {
+  const auto* p = static_cast<const bh_mean_rows_params*>(mean_rows_params);
+  if (bh_mean_rows_check(p) != 0) return Fail((std::string("CpuMeanRows: ") + bh_last_error()).c_str());
+  band::hip::CpuPool pool(1);
+  band::hip::CpuMeanRows(*p, pool);
+  return 0;
+}
+
+int bhx_cpu_eltwise(const void* eltwise_params) {
+  const auto* p = static_cast<const bh_eltwise_params*>(eltwise_params);
+  if (!p || !p->a || !p->b || !p->out || p->kind < BH_ELT_ADD || p->kind > BH_ELT_SQDIFF)
+    return Fail("CpuEltwise: invalid parameters");
+  for (int d = 0; d < 4; ++d)
+    if (p->shape_o[d] <= 0 || (p->shape_a[d] != p->shape_o[d] && p->shape_a[d] != 1) ||
+        (p->shape_b[d] != p->shape_o[d] && p->shape_b[d] != 1))
+      return Fail("CpuEltwise: bad shape");
+  band::hip::CpuPool pool(1);
+  band::hip::CpuEltwise(*p, pool);
+  return 0;
+}
+
+int bhx_cpu_unary_f32(int kind, const float* in, float* out, long n) {
+  if (!in || !out || n < 0 || kind < BH_UNARY_LOGISTIC || kind > BH_UNARY_GELU_TANH)
+    return Fail("CpuUnaryF32: invalid parameters");
+  band::hip::CpuUnaryF32(kind, in, out, n, 0.f, 0.f);
+  return 0;
+}
+
+int bhx_rsqrt_table(float in_scale, int in_zp, float out_scale, int out_zp, uint8_t* table) {
+  if (!table) return Fail("null argument");
+  return band::hip::RsqrtTable(in_scale, in_zp, out_scale, out_zp, table) ? 0 : Fail("RSQRT: output multiplier out of range");
+}
+
+int bhx_gelu_table(int is_signed, int approximate, float in_scale, int in_zp, float out_scale, int out_zp,
+                   uint8_t* table) {
+  if (!table) return Fail("null argument");
+  band::hip::GeluTable(is_signed != 0, approximate != 0, in_scale, in_zp, out_scale, out_zp, table);
+  return 0;
+}
+
+int bhx_squared_difference_params(float s1, float s2, float so, int32_t* out7) {
+  band::hip::AddParams p;
+  const char* why = "";
+  if (!out7) return Fail("null argument");
+  if (!band::hip::SquaredDifferenceParams(s1, s2, so, &p, &why)) return Fail(why);
+  const int32_t v[7] = {p.m1, p.s1, p.m2, p.s2, p.mo, p.so, p.left_shift};
+  std::copy(v, v + 7, out7);
+  return 0;
+}
+
 }  // extern "C"

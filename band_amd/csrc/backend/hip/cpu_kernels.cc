@@ -351,6 +351,11 @@ void CpuEltwise(const bh_eltwise_params& p, CpuPool& pool) {
         const int32_t sa = RequantLt1(xa * (1 << p.left_shift), p.a_mult, p.a_shift);
         const int32_t sb = RequantLt1(xb * (1 << p.left_shift), p.b_mult, p.b_shift);
         o = RequantLt1(sa + sb, p.o_mult, p.o_shift) + p.o_off;
+      } else if (p.kind == BH_ELT_SQDIFF) {  // squared_difference.cc, left_shift 7
+        const int32_t sa = RequantLt1(xa * (1 << p.left_shift), p.a_mult, p.a_shift);
+        const int32_t sb = RequantLt1(xb * (1 << p.left_shift), p.b_mult, p.b_shift);
+        const int32_t df = sa - sb;
+        o = RequantLt1(df * df, p.o_mult, p.o_shift) + p.o_off;
       } else {
         o = Requant(xa * xb, p.o_mult, p.o_shift) + p.o_off;
       }
@@ -708,6 +713,15 @@ void CpuPoolF32(const bh_pool_f32_params& p) {
 }
 
 void CpuUnaryF32(int kind, const float* in, float* out, long n, float lo, float hi) {
+  if (kind == BH_UNARY_GELU || kind == BH_UNARY_GELU_TANH) {
+    for (long i = 0; i < n; ++i) {
+      const float x = in[i];
+      out[i] = kind == BH_UNARY_GELU
+                   ? 0.5f * x * (1.0f + std::erf(x * 0.70710678118654752440f))
+                   : 0.5f * x * (1.0f + std::tanh(0.79788456080286535588f * x * (1.0f + 0.044715f * x * x)));
+    }
+    return;
+  }
   for (long i = 0; i < n; ++i)
     out[i] = kind == BH_UNARY_LOGISTIC ? 1.0f / (1.0f + std::exp(-in[i]))
              : kind == BH_UNARY_RSQRT  ? 1.0f / std::sqrt(in[i])
@@ -845,6 +859,29 @@ void CpuMean(const CpuMeanParams& p, CpuPool& pool) {
       acc = MultiplyByQuantizedMultiplier(acc, p.multiplier, p.shift) + p.bias;
       if (p.type == 1) static_cast<int8_t*>(p.output)[o] = static_cast<int8_t>(std::min(std::max(acc, -128), 127));
       else static_cast<uint8_t*>(p.output)[o] = static_cast<uint8_t>(std::min(std::max(acc, 0), 255));
+    }
+  });
+}
+
+void CpuMeanRows(const bh_mean_rows_params& p, CpuPool& pool) {
+  const uint8_t* in = static_cast<const uint8_t*>(p.input);
+  uint8_t* out = static_cast<uint8_t*>(p.output);
+  const bool sg = p.type == 1;
+  pool.ParallelFor(p.rows, [&](long lo, long hi) {
+    for (long r = lo; r < hi; ++r) {
+      int32_t sum = 0;
+      for (int k = 0; k < p.depth; ++k) sum += Load8(in, r * p.depth + k, sg);
+      int32_t v;
+      if (p.exact) {
+        v = sum / p.depth;  // reference_ops::Mean: C++ integer division
+      } else {
+        // QuantizedMeanOrSum: every float32 result is stored before it is used again
+        volatile float mean = static_cast<float>(sum) / static_cast<float>(p.depth);
+        volatile float prod = mean * p.scale;
+        volatile float biased = prod + p.bias;
+        v = Clamp(static_cast<int32_t>(std::round(static_cast<float>(biased))) + p.out_zp, sg ? -128 : 0, sg ? 127 : 255);
+      }
+      out[r] = static_cast<uint8_t>(v);
     }
   });
 }

@@ -103,6 +103,11 @@ struct CpuMeanParams {
   void* output;
 };
 void CpuMean(const CpuMeanParams& p, CpuPool& pool);
+// MEAN of an 8-bit tensor over its last axis (bh_mean_rows's host twin):
+// reference_ops::Mean when p.exact, else reference_ops::QuantizedMeanOrSum in
+// float32, one rounding per operation (this library's host code is built with
+// -ffp-contract=off, and the steps go through volatile besides)
+void CpuMeanRows(const bh_mean_rows_params& p, CpuPool& pool);
 
 // ARG_MAX / ARG_MIN: reference_ops::ArgMinMax's loop over [outer][axis_len]
 // [inner] - start at element 0, replace only on > (< for min): the first

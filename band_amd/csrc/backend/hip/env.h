@@ -57,7 +57,7 @@ inline const char* TuneFile() { return Str("BAND_HIP_TUNE_FILE"); }
 // 0: fused forms picked by the static model, nothing measured
 inline bool Autotune() { return Flag("BAND_HIP_AUTOTUNE", true); }
 // 0 | noirb | noadd | nochain | nogroup | noargmax | notile | nodeep | nosplit |
-// nostage | forcechain | forcetile | forcedeep | forcestage | forcedense
+// nostage | nolayernorm | forcechain | forcetile | forcedeep | forcestage | forcedense
 inline const char* Fusion() { return Str("BAND_HIP_FUSION"); }
 // 0: threads that drive a GPU stay off its NUMA node's CPUs
 inline bool NumaPin() { return Flag("BANDX_NUMA_PIN", true); }

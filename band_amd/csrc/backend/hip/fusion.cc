@@ -794,6 +794,109 @@ void HipModelExecutor::FuseGlue(const HipModel& model, PreparedSubgraph* sg) {
   sg->launches.swap(out);
 }
 
+// The ten ops a converter makes of an int8 LayerNormalization over the last
+// axis, in the order and with the operand order the synthesiser emits:
+//   m = MEAN(x)  d = SQUARED_DIFFERENCE(x, m)  v = MEAN(d)  e = ADD(v, eps)
+//   r = RSQRT(e)  g = MUL(r, gamma)  a = MUL(x, g)  b = MUL(m, g)
+//   c = SUB(beta, b)  y = ADD(a, c)
+// on x [..., C], row statistics [..., 1] and constants gamma / beta [C], eps
+// [1].  Op by op that is ten launches at the dispatch floor; matched, they
+// become one layernorm_i8_kernel launch that carries the ten parameter blocks
+// as they were lowered, so it stores the same bytes.  Ten consecutive launches
+// qualify when every intermediate is read only inside the pattern, is no
+// subgraph or model output, is not viewed (no_fuse / extra_d2h), and the
+// launcher's check takes the row (C <= BH_LAYERNORM_MAX_DEPTH).
+void HipModelExecutor::FuseLayerNorm(const HipModel& model, PreparedSubgraph* sg) {
+  const TflModel& d = model.desc();
+  static const int kPattern[10] = {kTflMean, kTflSquaredDifference, kTflMean, kTflAdd, kTflRsqrt,
+                                   kTflMul,  kTflMul,               kTflMul,  kTflSub, kTflAdd};
+  static const Launch::Kind kKinds[10] = {Launch::kMeanRows, Launch::kEltwise, Launch::kMeanRows, Launch::kEltwise,
+                                          Launch::kLutU8,    Launch::kEltwise, Launch::kEltwise,  Launch::kEltwise,
+                                          Launch::kEltwise,  Launch::kEltwise};
+  auto in_outputs = [&](int t) {
+    return std::find(sg->outputs.begin(), sg->outputs.end(), t) != sg->outputs.end() ||
+           std::find(d.outputs.begin(), d.outputs.end(), t) != d.outputs.end();
+  };
+  std::vector<Launch> out;
+  for (size_t i = 0; i < sg->launches.size(); ++i) {
+    const std::vector<Launch>& ls = sg->launches;
+    bool ok = i + 10 <= ls.size();
+    const TflOperator* o[10] = {};
+    for (int k = 0; ok && k < 10; ++k) {
+      const Launch& l = ls[i + k];
+      ok = l.kind == kKinds[k] && l.op_index >= 0 && d.ops[l.op_index].builtin == kPattern[k] &&
+           d.ops[l.op_index].outputs.size() == 1 && l.out_tensor == d.ops[l.op_index].outputs[0];
+      if (ok) o[k] = &d.ops[l.op_index];
+    }
+    if (!ok) {
+      out.push_back(ls[i]);
+      continue;
+    }
+    auto in = [&](int k, int j) { return o[k]->inputs[j]; };
+    auto res = [&](int k) { return o[k]->outputs[0]; };
+    const int x = in(0, 0), m = res(0), dd = res(1), v = res(2), e = res(3), r = res(4), g = res(5), a = res(6),
+              b = res(7), c = res(8);
+    const int eps = in(3, 1), gamma = in(5, 1), beta = in(8, 0);
+    ok = in(1, 0) == x && in(1, 1) == m && in(2, 0) == dd && in(3, 0) == v && in(4, 0) == e && in(5, 0) == r &&
+         in(6, 0) == x && in(6, 1) == g && in(7, 0) == m && in(7, 1) == g && in(8, 1) == b && in(9, 0) == a &&
+         in(9, 1) == c && eps >= 0 && gamma >= 0 && beta >= 0;
+    const TflTensor& tx = d.tensors[x];
+    const long depth = ok && !tx.shape.empty() ? tx.shape.back() : 0;
+    ok = ok && depth >= 1 && tx.type == DataType::kInt8 && d.tensors[res(9)].shape == tx.shape &&
+         d.tensors[eps].is_const() && d.tensors[eps].num_elements() == 1 && d.tensors[eps].data_size >= 1 &&
+         d.tensors[gamma].is_const() && d.tensors[gamma].shape == std::vector<int>{static_cast<int>(depth)} &&
+         d.tensors[beta].is_const() && d.tensors[beta].shape == std::vector<int>{static_cast<int>(depth)};
+    // the row statistics hold one value per row, the per-element tensors the input's shape
+    for (int t : {m, v, e, r})
+      ok = ok && d.tensors[t].num_elements() * static_cast<size_t>(depth) == tx.num_elements();
+    for (int t : {dd, g, a, b, c}) ok = ok && d.tensors[t].shape == tx.shape;
+    const std::set<int> inside = {ls[i].op_index,     ls[i + 1].op_index, ls[i + 2].op_index, ls[i + 3].op_index,
+                                  ls[i + 4].op_index, ls[i + 5].op_index, ls[i + 6].op_index, ls[i + 7].op_index,
+                                  ls[i + 8].op_index, ls[i + 9].op_index};
+    for (int t : {m, dd, v, e, r, g, a, b, c}) {
+      ok = ok && !in_outputs(t) && !sg->no_fuse.count(t) && !sg->extra_d2h.count(t);
+      for (int consumer : consumers_[t]) ok = ok && inside.count(consumer) > 0;
+    }
+    Launch F;
+    if (ok) {
+      F.kind = Launch::kLayerNorm;
+      F.op_index = ls[i].op_index;
+      F.out_tensor = res(9);
+      bh_layernorm_params& p = F.ln;
+      p = bh_layernorm_params{};
+      p.rows = ls[i].mrows.rows;
+      p.depth = static_cast<int>(depth);
+      p.mean_x = ls[i].mrows;
+      p.sqdiff = ls[i + 1].elt;
+      p.mean_d = ls[i + 2].mrows;
+      p.add_eps = ls[i + 3].elt;
+      p.rsqrt_table = ls[i + 4].table;
+      p.mul_gamma = ls[i + 5].elt;
+      p.mul_x = ls[i + 6].elt;
+      p.mul_m = ls[i + 7].elt;
+      p.sub_beta = ls[i + 8].elt;
+      p.add_out = ls[i + 9].elt;
+      p.eps_q = static_cast<int8_t>(d.tensors[eps].data[0]);
+      p.input = ls[i].mrows.input;
+      p.gamma = ls[i + 5].elt.b;
+      p.beta = ls[i + 8].elt.a;
+      p.output = ls[i + 9].elt.out;
+      ok = p.mean_d.rows == p.rows && bh_layernorm_i8_check(&p) == 0;
+    }
+    if (!ok) {
+      out.push_back(ls[i]);
+      continue;
+    }
+    F.kernel = bh_layernorm_i8_kernel(&F.ln);
+    F.alg_bytes = 2.0 * static_cast<double>(tx.num_elements()) + 2.0 * depth + 256.0;
+    for (int k = 1; k < 10; ++k) sg->fused_ops.insert(ls[i + k].op_index);
+    for (int t : {m, dd, v, e, r, g, a, b, c}) sg->fused_tensors.insert(t);
+    out.push_back(F);
+    i += 9;
+  }
+  sg->launches.swap(out);
+}
+
 // Folds `conv -> ADD/SUB(conv_out, residual)` into the conv epilogue when the
 // conv output has no other reader and nobody needs it materialised.  The
 // epilogue reproduces both TFLite ops exactly (conv requant + clamp to the

@@ -248,7 +248,9 @@ absl::Status HipModelExecutor::LowerGlue(const HipModel& model, int oi, void* in
     case kTflRelu6:
     case kTflReluN1To1:
     case kTflLogistic:
-    case kTflHardSwish: {
+    case kTflHardSwish:
+    case kTflRsqrt:
+    case kTflGelu: {
       L->src = in_ptr;
       L->dst = out_ptr;
       L->count = static_cast<long>(out.num_elements());
@@ -268,6 +270,11 @@ absl::Status HipModelExecutor::LowerGlue(const HipModel& model, int oi, void* in
       } else if (op.builtin == kTflHardSwish) {
         if (!HardSwishTable(i8, Scale(in), Zp(in), Scale(out), Zp(out), table))
           return absl::InternalError("HARD_SWISH: output multiplier exponent > 0");
+      } else if (op.builtin == kTflRsqrt) {
+        if (!RsqrtTable(Scale(in), Zp(in), Scale(out), Zp(out), table))
+          return absl::InternalError("RSQRT: output multiplier out of range");
+      } else if (op.builtin == kTflGelu) {
+        GeluTable(i8, op.options.valid() && op.options.Bool(0, false), Scale(in), Zp(in), Scale(out), Zp(out), table);
       } else {
         const float lo = op.builtin == kTflReluN1To1 ? -1.0f : 0.0f;
         const float hi = op.builtin == kTflRelu6 ? 6.0f : 1.0f;
@@ -462,6 +469,7 @@ absl::Status HipModelExecutor::BuildLaunches(const HipModel& model, PreparedSubg
   // first (they cut more launches), blocks over what the chains left
   if (allow_fusion_ && allow_chain_ && device_flag_ == DeviceFlag::kGPU) FuseChains(model, sg);
   if (allow_fusion_ && allow_irb_ && device_flag_ == DeviceFlag::kGPU) FuseBlocks(model, sg);
+  if (allow_fusion_ && allow_layernorm_ && device_flag_ == DeviceFlag::kGPU) FuseLayerNorm(model, sg);
   if (allow_fusion_) FuseGlue(model, sg);
   if (allow_fusion_ && allow_group_ && device_flag_ == DeviceFlag::kGPU) RETURN_STATUS_IF(GroupConvs(sg));
   return absl::OkStatus();
@@ -664,11 +672,13 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
       return absl::OkStatus();
     case kTflBatchMatMul:
       return LowerBatchMatMul(model, oi, in_ptr, out_ptr, sg, L);
-    default: {  // RELU / RELU6 / RELU_N1_TO_1 / LOGISTIC / RSQRT
+    default: {  // RELU / RELU6 / RELU_N1_TO_1 / LOGISTIC / RSQRT / GELU
       L->kind = Launch::kUnaryF32;
       L->kernel = "unary_f32_kernel";
+      const bool approximate = op.builtin == kTflGelu && op.options.valid() && op.options.Bool(0, false);
       L->unary_kind = op.builtin == kTflLogistic ? BH_UNARY_LOGISTIC
                       : op.builtin == kTflRsqrt  ? BH_UNARY_RSQRT
+                      : op.builtin == kTflGelu   ? (approximate ? BH_UNARY_GELU_TANH : BH_UNARY_GELU)
                                                  : BH_UNARY_CLAMP;
       L->lo = op.builtin == kTflReluN1To1 ? -1.f : 0.f;
       L->hi = op.builtin == kTflRelu6 ? 6.f : (op.builtin == kTflReluN1To1 ? 1.f : std::numeric_limits<float>::infinity());
@@ -937,7 +947,7 @@ absl::Status HipModelExecutor::LowerFc(const HipModel& model, int oi, void* in_p
   return absl::OkStatus();
 }
 
-// ADD / SUB / MUL int8 / uint8
+// ADD / SUB / MUL int8 / uint8, SQUARED_DIFFERENCE int8
 absl::Status HipModelExecutor::LowerEltwise(const HipModel& model, int oi, void* in_ptr, void* out_ptr,
                                             PreparedSubgraph* sg, Launch* L) {
   const TflModel& d = model.desc();
@@ -957,7 +967,16 @@ absl::Status HipModelExecutor::LowerEltwise(const HipModel& model, int oi, void*
   std::copy_n(s.a, 4, p.shape_a); std::copy_n(s.b, 4, p.shape_b); std::copy_n(s.o, 4, p.shape_o);
   p.a_off = -Zp(in); p.b_off = -Zp(b); p.o_off = Zp(out);
   ActivationRangeQuantized(op.options.Int8(0, 0), Scale(out), Zp(out), i8, &p.act_min, &p.act_max);
-  if (op.builtin == kTflMul) {
+  if (op.builtin == kTflSquaredDifference) {
+    AddParams ap;
+    if (!SquaredDifferenceArgs(d, op, nullptr, &ap, &why)) return Refused(op, why);
+    p.kind = BH_ELT_SQDIFF;
+    p.left_shift = ap.left_shift;
+    p.a_mult = ap.m1; p.a_shift = ap.s1;
+    p.b_mult = ap.m2; p.b_shift = ap.s2;
+    p.o_mult = ap.mo; p.o_shift = ap.so;
+    p.act_min = -128; p.act_max = 127;  // SquaredDifferenceOptions has no fused activation
+  } else if (op.builtin == kTflMul) {
     p.kind = BH_ELT_MUL;
     MulMultiplier(Scale(in), Scale(b), Scale(out), &p.o_mult, &p.o_shift);
   } else {
@@ -970,7 +989,9 @@ absl::Status HipModelExecutor::LowerEltwise(const HipModel& model, int oi, void*
   }
   p.a = in_ptr; p.b = b_ptr; p.out = out_ptr;
   L->kind = Launch::kEltwise;
-  L->kernel = "eltwise_kernel";
+  L->kernel = p.kind != BH_ELT_SQDIFF                 ? "eltwise_kernel"
+              : device_flag_ == DeviceFlag::kCPU ? "eltwise_sqdiff_host"
+                                                 : "eltwise_sqdiff_kernel";
   L->alg_bytes = static_cast<double>(in.num_elements() + b.num_elements() + out.num_elements());
   return absl::OkStatus();
 }
@@ -1004,9 +1025,31 @@ absl::Status HipModelExecutor::LowerMean(const HipModel& model, int oi, void* in
   const TflOperator& op = d.ops[oi];
   const TflTensor& in = d.tensors[op.inputs[0]];
   const TflTensor& out = d.tensors[op.outputs[0]];
+  MeanGeometry g;
+  const char* why = "";
+  if (!MeanArgs(d, op, &g, &why)) return Refused(op, why);
+  L->alg_bytes = static_cast<double>(meta_[op.inputs[0]]->bytes + meta_[op.outputs[0]]->bytes);
+  if (g.rows) {
+    // the last axis of an 8-bit tensor: one wave per row (mean_rows_kernel / CpuMeanRows)
+    bh_mean_rows_params& q = L->mrows;
+    q = bh_mean_rows_params{};
+    q.rows = g.outer;
+    q.depth = static_cast<int>(g.reduce);
+    q.type = in.type == DataType::kInt8 ? 1 : 2;
+    q.exact = g.exact ? 1 : 0;
+    // reference_ops::QuantizedMeanOrSum: float32, each operation on its own
+    q.scale = Scale(in) / Scale(out);
+    q.bias = -static_cast<float>(Zp(in)) * q.scale + 0.5f;
+    q.out_zp = Zp(out);
+    q.input = in_ptr; q.output = out_ptr;
+    if (bh_mean_rows_check(&q) != 0) return absl::InternalError(std::string("MEAN: ") + bh_last_error());
+    L->kind = Launch::kMeanRows;
+    L->kernel = device_flag_ == DeviceFlag::kGPU ? bh_mean_rows_kernel(&q) : "mean_rows_host";
+    return absl::OkStatus();
+  }
   CpuMeanParams& p = L->mean;
   p = CpuMeanParams{};
-  if (!MeanArgs(d, op, &p.outer, &p.reduce, &p.inner)) return absl::InternalError("unsupported MEAN");
+  p.outer = g.outer; p.reduce = g.reduce; p.inner = g.inner;
   p.type = in.type == DataType::kFloat32 ? 0 : (in.type == DataType::kInt8 ? 1 : 2);
   if (p.type) {
     // optimized_integer_ops::Mean (TFLite 2.9.2): the float products as
@@ -1097,7 +1140,7 @@ absl::Status HipModelExecutor::Lower(const HipModel& model, int oi, PreparedSubg
       case kTflDepthwiseConv2D: return LowerDepthwise(model, oi, in_ptr, out_ptr, ckey, sg, &L);
       case kTflFullyConnected: return LowerFc(model, oi, in_ptr, out_ptr, ckey, sg, &L);
       case kTflTransposeConv: return LowerTransposeConv(model, oi, out_ptr, ckey, sg, &L);
-      case kTflAdd: case kTflSub: case kTflMul: return LowerEltwise(model, oi, in_ptr, out_ptr, sg, &L);
+      case kTflAdd: case kTflSub: case kTflMul: case kTflSquaredDifference: return LowerEltwise(model, oi, in_ptr, out_ptr, sg, &L);
       case kTflAveragePool2D: case kTflMaxPool2D: return LowerPool(model, oi, in_ptr, out_ptr, &L);
       case kTflMean: return LowerMean(model, oi, in_ptr, out_ptr, &L);
       case kTflArgMax: case kTflArgMin: return LowerArgMinMax(model, oi, in_ptr, out_ptr, &L);

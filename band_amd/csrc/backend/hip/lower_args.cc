@@ -317,33 +317,84 @@ bool MirrorPadArgs(const TflModel& m, const TflOperator& op, std::vector<int64_t
   return true;
 }
 
-bool MeanArgs(const TflModel& m, const TflOperator& op, long* outer, long* reduce, long* inner) {
-  if (op.builtin != kTflMean || op.inputs.size() < 2 || op.inputs[1] < 0 || op.outputs.empty()) return false;
+bool MeanArgs(const TflModel& m, const TflOperator& op, MeanGeometry* g, const char** why) {
+  auto no = [&](const char* w) {
+    if (why) *why = w;
+    return false;
+  };
+  if (op.builtin != kTflMean || op.inputs.size() < 2 || op.inputs[0] < 0 || op.inputs[1] < 0 || op.outputs.empty() ||
+      op.outputs[0] < 0)
+    return no("MEAN needs an input, an axes tensor and an output");
   const TflTensor& in = m.tensors[op.inputs[0]];
   const TflTensor& out = m.tensors[op.outputs[0]];
   const TflTensor& ax = m.tensors[op.inputs[1]];
-  if (!ax.is_const() || ax.type != DataType::kInt32 || out.type != in.type) return false;
+  if (!ax.is_const() || ax.type != DataType::kInt32) return no("MEAN axes must be a constant int32 tensor");
+  if (out.type != in.type) return no("MEAN output type differs from the input's");
   const int rank = static_cast<int>(in.shape.size());
   std::set<int> axes;
   for (size_t i = 0; i * 4 < ax.data_size; ++i) {
     int32_t v;
     std::memcpy(&v, ax.data + 4 * i, 4);
     if (v < 0) v += rank;
-    if (v < 0 || v >= rank) return false;
+    if (v < 0 || v >= rank) return no("MEAN axis out of range");
     axes.insert(v);
   }
-  if (axes.empty() || *axes.rbegin() - *axes.begin() + 1 != static_cast<int>(axes.size())) return false;
+  if (axes.empty() || *axes.rbegin() - *axes.begin() + 1 != static_cast<int>(axes.size()))
+    return no("MEAN over one contiguous run of axes only");
+  MeanGeometry r{};
   if (in.type != DataType::kFloat32) {
     const bool keep = op.options.valid() && op.options.Int8(0, 0) != 0;
-    if (!IsQ8(in.type) || !HasQ(in) || !HasQ(out) || rank != 4 || !keep || axes != std::set<int>{1, 2}) return false;
+    if (!IsQ8(in.type)) return no("MEAN: int8, uint8 and float32 only");
+    if (!HasQ(in) || !HasQ(out)) return no("missing quantization");
+    const bool hw = rank == 4 && keep && axes == std::set<int>{1, 2};
+    r.rows = !hw && rank >= 1 && rank <= 4 && axes == std::set<int>{rank - 1};
+    if (!hw && !r.rows)
+      return no("8-bit MEAN: 4-D keep_dims over axes {1, 2}, or rank 1-4 over the last axis");
+    r.exact = Scale(in) == Scale(out) && Zp(in) == Zp(out);
   }
-  *outer = *reduce = *inner = 1;
+  r.outer = r.reduce = r.inner = 1;
   for (int dd = 0; dd < rank; ++dd) {
-    if (dd < *axes.begin()) *outer *= in.shape[dd];
-    else if (dd > *axes.rbegin()) *inner *= in.shape[dd];
-    else *reduce *= in.shape[dd];
+    if (dd < *axes.begin()) r.outer *= in.shape[dd];
+    else if (dd > *axes.rbegin()) r.inner *= in.shape[dd];
+    else r.reduce *= in.shape[dd];
   }
-  return *reduce > 0 && out.num_elements() == static_cast<size_t>(*outer * *inner);
+  r.reduces_axis0 = *axes.begin() == 0;
+  if (r.reduce <= 0 || r.outer <= 0 || r.inner <= 0) return no("MEAN of an empty tensor");
+  if (out.num_elements() != static_cast<size_t>(r.outer * r.inner))
+    return no("MEAN output must hold outer * inner elements");
+  // bh_mean_rows_check's limits, so that a refusal surfaces here and not at prepare time
+  if (r.rows && r.reduce * 255 >= (1l << 31)) return no("8-bit MEAN: a row of 2^31 / 255 or more elements");
+  if (g) *g = r;
+  return true;
+}
+
+bool MeanArgs(const TflModel& m, const TflOperator& op, long* outer, long* reduce, long* inner) {
+  MeanGeometry g;
+  if (!MeanArgs(m, op, &g)) return false;
+  *outer = g.outer;
+  *reduce = g.reduce;
+  *inner = g.inner;
+  return true;
+}
+
+bool SquaredDifferenceArgs(const TflModel& m, const TflOperator& op, BroadcastShapes* s, AddParams* q,
+                           const char** why) {
+  auto no = [&](const char* w) {
+    if (why) *why = w;
+    return false;
+  };
+  if (op.builtin != kTflSquaredDifference) return no("not a SQUARED_DIFFERENCE");
+  if (!BroadcastArgs(m, op, s, why)) return false;
+  const TflTensor& a = m.tensors[op.inputs[0]];
+  const TflTensor& b = m.tensors[op.inputs[1]];
+  const TflTensor& out = m.tensors[op.outputs[0]];
+  if (a.type != DataType::kInt8 || b.type != DataType::kInt8 || out.type != DataType::kInt8)
+    return no("SQUARED_DIFFERENCE: int8 and float32 only (no uint8, no int16)");
+  if (!HasQ(a) || !HasQ(b) || !HasQ(out)) return no("missing quantization");
+  AddParams p;
+  if (!SquaredDifferenceParams(Scale(a), Scale(b), Scale(out), &p, why)) return false;
+  if (q) *q = p;
+  return true;
 }
 
 bool ArgMinMaxArgs(const TflModel& m, const TflOperator& op, long* outer, long* axis_len, long* inner,

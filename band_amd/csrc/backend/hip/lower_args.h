@@ -100,8 +100,25 @@ bool MirrorPadArgs(const TflModel& m, const TflOperator& op, std::vector<int64_t
 // MEAN: the reduced axes (constant int32, negatives resolved) must be one
 // contiguous run; 8-bit tensors only in the form TFLite 2.9.2 runs through
 // optimized_integer_ops::Mean / optimized_ops::Mean (4-D, keep_dims, axes
-// {1, 2}), the one restated by CpuMean.
+// {1, 2}), the one restated by CpuMean - or, `rows`, over the last axis alone
+// (rank 1-4, keep_dims either way), the other two branches of reduce.cc
+// EvalMean, restated by CpuMeanRows / mean_rows_kernel: `exact` when input and
+// output share scale and zero point (reference_ops::Mean), else
+// reference_ops::QuantizedMeanOrSum.  *why names what was refused.
+struct MeanGeometry {
+  long outer, reduce, inner;  // the input viewed as [outer][reduce][inner]
+  bool rows;                  // 8-bit, last axis: [outer][reduce], inner 1
+  bool exact;                 // 8-bit: input and output quantisation are equal
+  bool reduces_axis0;         // the job-batch rule: axis 0 is among the reduced ones
+};
+bool MeanArgs(const TflModel& m, const TflOperator& op, MeanGeometry* g, const char** why = nullptr);
 bool MeanArgs(const TflModel& m, const TflOperator& op, long* outer, long* reduce, long* inner);
+
+// SQUARED_DIFFERENCE int8: BroadcastArgs' shapes and squared_difference.cc's
+// multipliers (SquaredDifferenceParams); uint8 / int16 and an output
+// multiplier >= 1 are refused with a reason
+bool SquaredDifferenceArgs(const TflModel& m, const TflOperator& op, BroadcastShapes* s, AddParams* q,
+                           const char** why = nullptr);
 
 // ARG_MAX / ARG_MIN (arg_min_max.cc): int8 / uint8 / float32 input of rank
 // 1-4 viewed as [outer][axis_len][inner]; the axis is a constant int32 /

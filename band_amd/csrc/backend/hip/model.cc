@@ -70,6 +70,13 @@ absl::Status HipModel::CloneWithJobBatch(int batch, std::unique_ptr<HipModel>* o
       if (ex::ArgMinMaxArgs(desc_, op, &outer, &len, &inner, &out_bytes, &axis) && axis == 0)
         return absl::InternalError(std::string("job batching: ") + TflBuiltinName(op.builtin) + " on the batch axis");
     }
+    if (op.builtin == kTflMean) {
+      // an 8-bit MEAN over the last axis never reduces axis 0 of a tensor of
+      // rank >= 2; a rank-1 one (or a float MEAN from axis 0 on) would
+      ex::MeanGeometry g;
+      if (ex::MeanArgs(desc_, op, &g) && g.reduces_axis0)
+        return absl::InternalError("job batching: MEAN over the batch axis");
+    }
     if (op.builtin == kTflBatchMatMul) {
       // axis 0 must be a matmul batch dim of the output and of every
       // activation operand; a constant operand has to broadcast along it

@@ -160,10 +160,25 @@ bool HipModelExecutor::GpuSupports(const TflModel& m, const TflOperator& op, std
       }
       return true;
     case kTflMean: {
-      long o, r, i;
-      if (!MeanArgs(m, op, &o, &r, &i)) return no("MEAN over one contiguous run of axes, 4-D keep_dims");
+      MeanGeometry g;
+      const char* w = "";
+      return MeanArgs(m, op, &g, &w) ? true : no(w);
+    }
+    case kTflSquaredDifference: {
+      const char* w = "";
+      return SquaredDifferenceArgs(m, op, nullptr, nullptr, &w) ? true : no(w);
+    }
+    case kTflRsqrt: {
+      if (in.type != DataType::kInt8 || out.type != DataType::kInt8) return no("RSQRT: int8 and float32 only");
+      if (!HasQ(in) || !HasQ(out)) return no("missing quantization");
+      uint8_t t[256];
+      if (!RsqrtTable(Scale(in), Zp(in), Scale(out), Zp(out), t)) return no("RSQRT: output multiplier out of range");
       return true;
     }
+    case kTflGelu:
+      if (!IsQ8(in.type) || out.type != in.type) return no("GELU: int8, uint8 and float32 only");
+      if (!HasQ(in) || !HasQ(out)) return no("missing quantization");
+      return true;
     case kTflArgMax:
     case kTflArgMin: {
       long o, l, i;
@@ -263,8 +278,6 @@ bool HipModelExecutor::GpuSupports(const TflModel& m, const TflOperator& op, std
 bool HipModelExecutor::CpuSupports(const TflModel& m, const TflOperator& op, std::string* why) {
   if (GpuSupports(m, op, nullptr)) return true;
   if (DetectionSupported(m, op, nullptr)) return true;
-  long o, r, i;
-  if (MeanArgs(m, op, &o, &r, &i)) return true;
   return GpuSupports(m, op, why);
 }
 
@@ -302,6 +315,7 @@ absl::Status HipModelExecutor::EnsureMeta(const HipModel& model) {
   if (std::strcmp(f, "nochain") == 0) allow_chain_ = false;
   if (std::strcmp(f, "nogroup") == 0) allow_group_ = false;
   if (std::strcmp(f, "noargmax") == 0) allow_argmax_ = false;
+  if (std::strcmp(f, "nolayernorm") == 0) allow_layernorm_ = false;
   if (std::strcmp(f, "forcechain") == 0) forced_chain_ = ForcedChain::kPlain;  // parity tests: every feasible chain
   if (std::strcmp(f, "forcetile") == 0) forced_chain_ = ForcedChain::kTile;  // ... in the tile form
   if (std::strcmp(f, "notile") == 0) no_tile_chain_ = true;  // A-B: the raster chain forms only
@@ -633,6 +647,8 @@ absl::Status HipModelExecutor::EnqueueLaunch(const Launch& l) {
     case Launch::kReindex: rc = bh_reindex(&l.reindex, stream_); break;
     case Launch::kBatchMatMul: rc = bh_batch_matmul_i8(&l.bmm, stream_); break;
     case Launch::kBatchMatMulF32: rc = bh_batch_matmul_f32(&l.bmm, stream_); break;
+    case Launch::kMeanRows: rc = bh_mean_rows(&l.mrows, stream_); break;
+    case Launch::kLayerNorm: rc = bh_layernorm_i8(&l.ln, stream_); break;
     case Launch::kMean: {
       bh_mean_params q{};
       q.outer = l.mean.outer;
@@ -833,6 +849,7 @@ absl::Status HipModelExecutor::ExecuteOnHost(PreparedSubgraph* sg) {
         break;
       case Launch::kDetectionPost: CpuDetectionPostprocess(l.det, pool); break;
       case Launch::kMean: CpuMean(l.mean, pool); break;
+      case Launch::kMeanRows: CpuMeanRows(l.mrows, pool); break;
       case Launch::kArgMinMax: CpuArgMinMax(l.argmm, pool); break;
       case Launch::kReindex: CpuReindex(l.reindex); break;
       case Launch::kBatchMatMul: CpuBatchMatMul(l.bmm, pool); break;

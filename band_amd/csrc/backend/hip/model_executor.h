@@ -46,7 +46,8 @@ struct Launch {
     kConvF32, kFcF32, kEltwiseF32, kPoolF32, kUnaryF32, kSoftmaxF32,  // float32 graphs
     kResizeBilinearU8,
     kDetectionPost,  // CPU-only TFLite_Detection_PostProcess
-    kMean,           // CPU-only MEAN
+    kMean,           // MEAN: float32 over a run of axes, 8-bit over H, W
+    kMeanRows,       // MEAN of an 8-bit tensor over its last axis (`mrows`)
     kConvGroup,      // independent small convs in one dispatch (GroupConvs)
     kDetectionGpu,   // TFLite_Detection_PostProcess on the device (BAND_HIP_GPU_DETECTION=1)
     kArgMinMax,      // ARG_MAX / ARG_MIN
@@ -54,7 +55,8 @@ struct Launch {
     kReindex,         // one output of TRANSPOSE / STRIDED_SLICE / SLICE / SPLIT / SPLIT_V / SPACE_TO_DEPTH / DEPTH_TO_SPACE
     kConvGrouped,     // grouped CONV_2D: `conv` with the total channel counts + conv_groups (never chained / grouped / blocked)
     kBatchMatMul,     // BATCH_MATMUL int8 (BatchMatMulArgs -> `bmm`; never chained / grouped / blocked, no epilogue folds)
-    kBatchMatMulF32   // BATCH_MATMUL float32
+    kBatchMatMulF32,  // BATCH_MATMUL float32
+    kLayerNorm        // the ten ops of an int8 LayerNorm as one launch (FuseLayerNorm; kGPU)
   } kind;
   int op_index = -1;
   int out_tensor = -1;  // tensor this launch materialises (after epilogue fusions)
@@ -86,6 +88,8 @@ struct Launch {
   CpuDetectionParams det{};
   bh_detection_params detg{};  // kDetectionGpu
   CpuMeanParams mean{};
+  bh_mean_rows_params mrows{};
+  bh_layernorm_params ln{};
   bh_argminmax_params argmm{};
   bh_resize_argminmax_params rzarg{};
   bh_reindex_params reindex{};
@@ -232,6 +236,7 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   // CONCATENATION with outer size 1 elided (producers write their slices);
   // int8 RESIZE_BILINEAR -> ARG_MAX / ARG_MIN over channels as one launch (kGPU)
   void FuseGlue(const HipModel& model, PreparedSubgraph* sg);
+  void FuseLayerNorm(const HipModel& model, PreparedSubgraph* sg);
   // independent small convs (detector / pose heads) deferred past later
   // launches that do not touch them and issued as one conv_group launch
   absl::Status GroupConvs(PreparedSubgraph* sg);
@@ -328,6 +333,7 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   bool allow_chain_ = true;   // BAND_HIP_FUSION=nochain
   bool allow_group_ = true;   // BAND_HIP_FUSION=nogroup: one launch per conv
   bool allow_argmax_ = true;  // BAND_HIP_FUSION=noargmax: RESIZE_BILINEAR and ARG_MAX / ARG_MIN as two launches
+  bool allow_layernorm_ = true;  // BAND_HIP_FUSION=nolayernorm: a LayerNorm's ten ops as ten launches
   // BAND_HIP_FUSION=forcechain / forcetile / forcedeep / forcestage / forcedense (parity
   // tests): every feasible chain fused, in the named form where that fits
   ForcedChain forced_chain_ = ForcedChain::kNone;

@@ -184,6 +184,114 @@ void LogisticTable(bool is_signed, float in_scale, int32_t in_zp, float out_scal
   }
 }
 
+void GeluTable(bool is_signed, bool approximate, float in_scale, int32_t in_zp, float out_scale, int32_t out_zp,
+               uint8_t table[256]) {
+  const float inverse_scale = 1.0f / out_scale;
+  const int32_t minval = is_signed ? -128 : 0, maxval = is_signed ? 127 : 255;
+  for (int32_t val = minval; val <= maxval; ++val) {
+    const float dequantized = in_scale * static_cast<float>(val - in_zp);
+    const double x = static_cast<double>(dequantized);
+    const double y = approximate ? 0.5 * x * (1.0 + std::tanh(0.7978845608028654 * x * (1.0 + 0.044715 * x * x)))
+                                 : 0.5 * x * (1.0 + std::erf(x * 0.7071067811865476));
+    const float transformed = static_cast<float>(y);
+    const float rescaled = std::round(transformed * inverse_scale);
+    const int32_t quantized = static_cast<int32_t>(rescaled + static_cast<float>(out_zp));
+    table[static_cast<uint8_t>(val)] = static_cast<uint8_t>(Clamp(quantized, minval, maxval));
+  }
+}
+
+bool SquaredDifferenceParams(float s1, float s2, float so, AddParams* p, const char** why) {
+  auto no = [&](const char* w) {
+    if (why) *why = w;
+    return false;
+  };
+  if (!(s1 > 0.0f) || !(s2 > 0.0f) || !(so > 0.0f)) return no("SQUARED_DIFFERENCE: scales must be positive");
+  AddParams a{};
+  a.left_shift = 7;
+  const double twice_max = 2.0 * static_cast<double>(std::max(s1, s2));
+  const double r1 = static_cast<double>(s1) / twice_max;
+  const double r2 = static_cast<double>(s2) / twice_max;
+  const double ro =
+      (twice_max * twice_max) / static_cast<double>(static_cast<float>(1 << (a.left_shift * 2)) * so);
+  // QuantizeMultiplierSmallerThanOneExp: TFLITE_CHECK_LT(multiplier, 1.)
+  if (!(ro < 1.0)) return no("SQUARED_DIFFERENCE: output multiplier >= 1 (TFLite's Prepare refuses it)");
+  int e;
+  QuantizeMultiplier(r1, &a.m1, &e);
+  a.s1 = e;
+  QuantizeMultiplier(r2, &a.m2, &e);
+  a.s2 = e;
+  QuantizeMultiplier(ro, &a.mo, &e);
+  a.so = e;
+  if (a.s1 > 0 || a.s2 > 0 || a.so > 0) return no("SQUARED_DIFFERENCE: a multiplier's shift is positive");
+  *p = a;
+  return true;
+}
+
+namespace {
+// gemmlowp SaturatingRoundingMultiplyByPOT<e>, e > 0
+int32_t SatShl(int32_t x, int e) {
+  const int32_t threshold = static_cast<int32_t>((1u << (31 - e)) - 1u);
+  if (x > threshold) return INT32_MAX;
+  if (x < -threshold) return INT32_MIN;
+  return static_cast<int32_t>(static_cast<uint32_t>(x) << e);
+}
+}  // namespace
+
+void GetInvSqrtQuantizedMultiplierExp(int32_t input, int reverse_shift, int32_t* inv_sqrt, int* shift) {
+  if (input <= 1) {  // 1 (and 0, as if it were 1): handled apart, the iteration below would overflow
+    *inv_sqrt = INT32_MAX;
+    *shift = 0;
+    return;
+  }
+  *shift = 11;
+  while (input >= (1 << 29)) {
+    input /= 4;
+    ++*shift;
+  }
+  const unsigned max_left_shift_bits = static_cast<unsigned>(__builtin_clz(static_cast<uint32_t>(input))) - 1;
+  const unsigned left_shift_bit_pairs = max_left_shift_bits / 2 - 1;
+  *shift -= static_cast<int>(left_shift_bit_pairs);
+  input = static_cast<int32_t>(static_cast<uint32_t>(input) << (2 * left_shift_bit_pairs));
+  // fixed point with 3 integer bits (raw / 2^28); x = 1.5 x - (in / 2) x^3 from x = 1, five times
+  const int32_t half_input = Rdbypot(input >> 1, 1);
+  const int32_t half_three = (1 << 28) + (1 << 27);
+  int32_t x = 1 << 28;
+  for (int i = 0; i < 5; ++i) {
+    const int32_t x3 = SatShl(Srdhm(Srdhm(x, x), x), 6);
+    x = SatShl(Srdhm(half_three, x) - Srdhm(half_input, x3), 3);
+  }
+  x = Srdhm(x, 1518500250);  // sqrt(2) / 2
+  if (*shift < 0) {
+    x = static_cast<int32_t>(static_cast<uint32_t>(x) << -*shift);
+    *shift = 0;
+  }
+  *inv_sqrt = x;
+  *shift *= reverse_shift;
+}
+
+bool RsqrtTable(float in_scale, int32_t in_zp, float out_scale, int32_t out_zp, uint8_t table[256]) {
+  if (!(in_scale > 0.0f) || !(out_scale > 0.0f)) return false;
+  const float denom = std::sqrt(in_scale) * out_scale;
+  int32_t mult;
+  int shift;
+  QuantizeMultiplier(1.0 / static_cast<double>(denom), &mult, &shift);
+  const int kShift = 20;
+  if (shift - kShift > 31 || shift - kShift < -31) return false;
+  for (int32_t val = -128; val <= 127; ++val) {
+    const int32_t v = val - in_zp;
+    int32_t out = 127;  // v == 0; and v < 0, which TFLite refuses at invoke
+    if (v > 0) {
+      int32_t m;
+      int e;
+      GetInvSqrtQuantizedMultiplierExp(v, -1, &m, &e);
+      const int32_t data = MultiplyByQuantizedMultiplier(1, m, e + kShift);
+      out = Clamp(MultiplyByQuantizedMultiplier(data, mult, shift - kShift) + out_zp, -128, 127);
+    }
+    table[static_cast<uint8_t>(val)] = static_cast<uint8_t>(out);
+  }
+  return true;
+}
+
 namespace {
 // int16 fixed-point primitives of reference_ops::HardSwish (TFLite 2.9.2
 // kernels/internal/reference/hard_swish.h and gemmlowp fixedpoint.h)

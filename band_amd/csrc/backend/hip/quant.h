@@ -62,6 +62,30 @@ void ReluTable(bool is_signed, float in_scale, int32_t in_zp, float out_scale, i
 // activations.cc PopulateLookupTable<T> with 1 / (1 + exp(-x))
 void LogisticTable(bool is_signed, float in_scale, int32_t in_zp, float out_scale, int32_t out_zp,
                    uint8_t table[256]);
+// activations.cc PopulateLookupTable<T> with GELU (GeluOptions.approximate:
+// the tanh form): dequantise in float32, transform, round(y * (1 / s_out)),
+// add the zero point, clamp.  The transform 0.5 x (1 + erf(x / sqrt 2)) is
+// evaluated in double on the float32 x and rounded to float32 once (TFLite
+// evaluates it in float32; a double erf is what an independent restatement
+// can reproduce bit for bit).
+void GeluTable(bool is_signed, bool approximate, float in_scale, int32_t in_zp, float out_scale, int32_t out_zp,
+               uint8_t table[256]);
+// squared_difference.cc Prepare (int8): left_shift 7, twice_max = 2 max(s1, s2)
+// in double, the input multipliers s / twice_max and the output multiplier
+// twice_max^2 / (2^14 s_out), each through QuantizeMultiplierSmallerThanOneExp.
+// False (with *why) when the output multiplier is not below 1, which TFLite's
+// Prepare checks too.
+bool SquaredDifferenceParams(float s1, float s2, float so, AddParams* p, const char** why = nullptr);
+// elementwise.cc RSQRT int8, for every input byte q with v = q - in_zp:
+// v == 0 -> 127; v > 0 -> GetInvSqrtQuantizedMultiplierExp(v, -1) = (m, e),
+// data = MBQM(1, m, e + 20), out = clamp(MBQM(data, mult, shift - 20) + out_zp)
+// with (mult, shift) = QuantizeMultiplier(1.0 / (sqrtf(s_in) * s_out)) (the
+// square root and the product in float32).  TFLite fails the invoke for
+// v < 0; those entries hold 127 here, and a graph must not feed them.  False
+// when the multiplier's shift leaves MultiplyByQuantizedMultiplier's range.
+bool RsqrtTable(float in_scale, int32_t in_zp, float out_scale, int32_t out_zp, uint8_t table[256]);
+// common.h GetInvSqrtQuantizedMultiplierExp (gemmlowp fixed point, 5 Newton steps)
+void GetInvSqrtQuantizedMultiplierExp(int32_t input, int reverse_shift, int32_t* inv_sqrt, int* shift);
 // activations.cc HardSwishPrepare (16-bit fixed-point multipliers) +
 // reference_ops::HardSwish<T> evaluated for every input byte; false when
 // TFLite's Prepare would refuse the scales (output exponent > 0)

@@ -55,6 +55,7 @@ const char* TflBuiltinName(int c) {
     case kTflSlice: return "SLICE";
     case kTflSplitV: return "SPLIT_V";
     case kTflBatchMatMul: return "BATCH_MATMUL";
+    case kTflGelu: return "GELU";
     default: return "UNKNOWN";
   }
 }

@@ -36,6 +36,8 @@ enum TflBuiltin : int {
   kTflSlice = 65, kTflSplitV = 102,
   // BatchMatMulOptions: slots 0-2 adj_x, adj_y, asymmetric_quantize_inputs
   kTflBatchMatMul = 126,
+  // GeluOptions: slot 0 approximate (bool)
+  kTflGelu = 150,
 };
 
 const char* TflBuiltinName(int code);

@@ -11,27 +11,9 @@
 //   y   = MBQMSmallerThanOneExp(s_1 + s_2, M_o, sh_o) + zp_o
 // SUB is ADD with input2's multiplier negated (sub.cc).  MUL (mul.cc):
 //   y = MBQM((q_1 + off_1) * (q_2 + off_2), M, sh) + zp_o
-#include "common.hpp"
+#include "eltwise_ops.hpp"
 
 namespace bh {
-
-__device__ __forceinline__ int32_t ld8(const uint8_t* p, long i, bool sgn) {
-  return sgn ? (int32_t)(int8_t)p[i] : (int32_t)p[i];
-}
-
-__device__ __forceinline__ int32_t elt_op(const bh_eltwise_params& p, int32_t qa, int32_t qb) {
-  const int32_t xa = qa + p.a_off;
-  const int32_t xb = qb + p.b_off;
-  int32_t o;
-  if (p.kind == BH_ELT_ADD) {
-    const int32_t sa = requant_lt1(xa * (1 << p.left_shift), p.a_mult, p.a_shift);
-    const int32_t sb = requant_lt1(xb * (1 << p.left_shift), p.b_mult, p.b_shift);
-    o = requant_lt1(sa + sb, p.o_mult, p.o_shift) + p.o_off;
-  } else {
-    o = requant(xa * xb, p.o_mult, p.o_shift) + p.o_off;
-  }
-  return clamp_i32(o, p.act_min, p.act_max);
-}
 
 // same shape, 4 elements per lane (n % 4 == 0, pointers dword aligned)
 __global__ __launch_bounds__(256) void eltwise_flat4_kernel(bh_eltwise_params p, long n4) {
@@ -231,7 +213,11 @@ __global__ __launch_bounds__(NW * 64) void pool_wide_kernel(bh_pool_params p, Po
 
 }  // namespace bh
 
+// SQUARED_DIFFERENCE: eltwise_sqdiff_kernel (layernorm.hip)
+int bh_eltwise_sqdiff_i8(const bh_eltwise_params* pp, bh_stream_t stream);
+
 extern "C" int bh_eltwise_i8(const bh_eltwise_params* pp, bh_stream_t stream) {
+  if (pp && pp->kind == BH_ELT_SQDIFF) return bh_eltwise_sqdiff_i8(pp, stream);
   if (!pp || !pp->a || !pp->b || !pp->out || (pp->kind != BH_ELT_ADD && pp->kind != BH_ELT_MUL)) {
     bh_set_last_error("bh_eltwise_i8: invalid parameters");
     return BH_EINVAL;

@@ -32,6 +32,9 @@ OPTION_FIELDS = {
     79: [(0, "i")],                                                             # SplitV
     94: [(0, "i")],                                                             # DepthToSpace
     101: [(0, "b"), (1, "b"), (2, "b")],                                        # BatchMatMul
+    27: [(0, "b")],                                                             # Reducer (MEAN keep_dims)
+    76: [],                                                                     # SquaredDifference
+    116: [(0, "b")],                                                            # Gelu (approximate)
 }
 
 

@@ -29,7 +29,8 @@ OPC = dict(ADD=0, AVERAGE_POOL_2D=1, CONCATENATION=2, CONV_2D=3, DEPTHWISE_CONV_
            DEQUANTIZE=6, RELU=19, RELU_N1_TO_1=20, RELU6=21, PADV2=60, RESIZE_NEAREST_NEIGHBOR=97,
            TRANSPOSE_CONV=67, ARG_MAX=56, ARG_MIN=79,
            DEPTH_TO_SPACE=5, SPACE_TO_DEPTH=26, TRANSPOSE=39, STRIDED_SLICE=45, SPLIT=49, SLICE=65, SPLIT_V=102,
-           BATCH_MATMUL=126)
+           BATCH_MATMUL=126,
+           MEAN=40, RSQRT=76, SQUARED_DIFFERENCE=99, GELU=150)
 # BuiltinOptions union indices
 OPT = dict(Conv2DOptions=1, DepthwiseConv2DOptions=2, Pool2DOptions=5, FullyConnectedOptions=8,
            SoftmaxOptions=9, ConcatenationOptions=10, AddOptions=11, ReshapeOptions=17,
@@ -39,7 +40,9 @@ OPT = dict(Conv2DOptions=1, DepthwiseConv2DOptions=2, Pool2DOptions=5, FullyConn
            SpaceToDepthOptions=19, TransposeOptions=26, StridedSliceOptions=32, SplitOptions=35, SliceOptions=44,
            SplitVOptions=79, DepthToSpaceOptions=94,
            # written from memory of schema.fbs; the C++ reader never keys on the union number
-           BatchMatMulOptions=101)
+           BatchMatMulOptions=101,
+           # ... and so are these three
+           ReducerOptions=27, SquaredDifferenceOptions=76, GeluOptions=116)
 
 
 # ---------------------------------------------------------------------------
@@ -735,6 +738,115 @@ class QGraph(_ReindexOps):
         self.mb.op("QUANTIZE", [xf], [y], OPT["QuantizeOptions"], Table())
         return y
 
+    # --- the ops of a transformer's LayerNorm and MLP ---------------------------
+    def _range_q(self, lo, hi, headroom=1.15):
+        """(scale, zero point) covering the real interval [lo, hi] with headroom"""
+        qmin, qmax = (-128, 127) if self.dtype == np.int8 else (0, 255)
+        lo, hi = min(float(lo), 0.0) * headroom, max(float(hi), 0.0) * headroom
+        scale = max(hi - lo, 1e-6) / 255.0
+        return float(np.float32(scale)), int(np.clip(qmin - round(lo / scale), qmin, qmax))
+
+    def const(self, values, kind="const"):
+        """a constant 8-bit tensor holding the real `values` (its own scale and zero point)"""
+        v = np.asarray(values, np.float64)
+        scale, zp = self._range_q(v.min(), v.max(), 1.0)
+        qmin, qmax = (-128, 127) if self.dtype == np.int8 else (0, 255)
+        q = np.clip(np.round(v / scale) + zp, qmin, qmax).astype(self.dtype)
+        t = self.mb.tensor(self._name(kind), list(v.shape), self.dtype, scale=[scale], zero_point=[zp], data=q)
+        self.meta[t] = (list(v.shape), scale, zp)
+        return t
+
+    def _binary(self, kind, options, a, b, scale, zp, act="NONE"):
+        shape = [int(d) for d in np.broadcast_shapes(tuple(self.meta[a][0]), tuple(self.meta[b][0]))]
+        y = self.act_tensor(shape, float(scale), int(zp))
+        self.mb.op(kind, [a, b], [y], OPT[options], act_options(act) if options != "SquaredDifferenceOptions" else Table())
+        return y
+
+    def mul(self, a, b, scale, zp, act="NONE"):
+        """MUL with numpy broadcasting; b may be a constant (self.const)"""
+        return self._binary("MUL", "MulOptions", a, b, scale, zp, act)
+
+    def sub(self, a, b, scale, zp, act="NONE"):
+        return self._binary("SUB", "SubOptions", a, b, scale, zp, act)
+
+    def add_q(self, a, b, scale, zp, act="NONE"):
+        """ADD with broadcasting and an explicit output quantisation"""
+        return self._binary("ADD", "AddOptions", a, b, scale, zp, act)
+
+    def squared_difference(self, a, b, scale, zp):
+        return self._binary("SQUARED_DIFFERENCE", "SquaredDifferenceOptions", a, b, scale, zp)
+
+    def mean_last(self, x, keep_dims=True, scale=None, zp=None):
+        """MEAN over the last axis; the default output shares the input's
+        quantisation (reduce.cc's reference_ops::Mean branch)"""
+        shp, s, z = self.meta[x]
+        at = self.mb.tensor(self._name("axes"), [1], np.int32, data=np.array([-1], np.int32))
+        y = self.act_tensor(list(shp[:-1]) + ([1] if keep_dims else []), s if scale is None else float(scale),
+                            z if zp is None else int(zp))
+        self.mb.op("MEAN", [x, at], [y], OPT["ReducerOptions"], Table().set(0, "b", int(keep_dims)))
+        return y
+
+    def rsqrt(self, x, scale, zp):
+        y = self._like(x, scale=float(scale), zp=int(zp))
+        self.mb.op("RSQRT", [x], [y])
+        return y
+
+    def gelu(self, x, approximate=False):
+        """GELU at the input's scale; the zero point leaves room for the minimum, -0.17"""
+        _, s, _ = self.meta[x]
+        qmin = -128 if self.dtype == np.int8 else 0
+        y = self._like(x, zp=min(qmin + int(np.ceil(0.17 / s)), qmin + 128))
+        self.mb.op("GELU", [x], [y], OPT["GeluOptions"], Table().set(0, "b", int(approximate)))
+        return y
+
+    def layer_norm(self, x, eps=1e-6):
+        """The ten ops a converter makes of LayerNormalization over the last axis:
+        m = MEAN(x), d = SQUARED_DIFFERENCE(x, m), v = MEAN(d), e = ADD(v, eps),
+        r = RSQRT(e), g = MUL(r, gamma), a = MUL(x, g), b = MUL(m, g),
+        c = SUB(beta, b), y = ADD(a, c).  gamma ~ U(0.5, 1.5) and beta ~ N(0, 0.3)
+        per channel.  The scale of every intermediate comes from a float64 pass
+        over seeded calibration rows (spreads of 24 to 100 input LSBs around the
+        zero point), so that none of them saturates on such inputs; the
+        non-negative ones (d, v, e, r, g) sit at the bottom of the range, which
+        also keeps RSQRT's input at or above its zero point."""
+        assert self.dtype == np.int8, "layer_norm: int8 graphs only (SQUARED_DIFFERENCE and RSQRT are int8 ops)"
+        shp, s_x, z_x = self.meta[x]
+        C = shp[-1]
+        gamma = self.rng.uniform(0.5, 1.5, C)
+        beta = self.rng.normal(0.0, 0.3, C)
+        cal = np.random.default_rng(1000 + C)
+        spread = np.exp(np.linspace(np.log(24.0), np.log(100.0), 64))[:, None]
+        X = s_x * np.clip(np.round(cal.normal(0.0, 1.0, (64, C)) * spread / 2.0 + cal.normal(0.0, 10.0, (64, 1))),
+                          -128 - z_x, 127 - z_x)
+        M = X.mean(-1, keepdims=True)
+        D = (X - M) ** 2
+        V = D.mean(-1, keepdims=True)
+        E = V + eps
+        R = 1.0 / np.sqrt(E)
+        G = R * gamma
+        A, B = X * G, M * G
+        Cc = beta - B
+        Y = A + Cc
+        q = lambda t: self._range_q(t.min(), t.max())
+        m = self.mean_last(x)
+        # squared_difference.cc wants (2 max(s_x, s_m))^2 / (2^14 s_d) < 1 (a constant row has no spread)
+        d = self.squared_difference(x, m, max(q(D)[0], 1.01 * (2.0 * s_x) ** 2 / 16384.0), -128)
+        v = self.mean_last(d, scale=q(V)[0], zp=-128)
+        e = self.add_q(v, self.const([eps], "eps"), q(E)[0], -128)
+        # 1 / sqrt reaches its maximum on the smallest variance; twice the calibrated one leaves room
+        r = self.rsqrt(e, 2.0 * q(R)[0], -128)
+        g = self.mul(r, self.const(gamma, "gamma"), 2.0 * q(G)[0], -128)
+        a = self.mul(x, g, *q(2.0 * A))
+        b = self.mul(m, g, *q(2.0 * B))
+        c = self.sub(self.const(beta, "beta"), b, *q(2.0 * Cc))
+        return self.add_q(a, c, *q(Y))
+
+    def mlp(self, x, hidden, residual=None):
+        """FULLY_CONNECTED -> GELU -> FULLY_CONNECTED -> ADD with the input (or with `residual`)"""
+        c = self.meta[x][0][-1]
+        h = self.gelu(self.fully_connected(x, hidden, keep_num_dims=True))
+        return self.add(self.fully_connected(h, c, keep_num_dims=True), x if residual is None else residual)
+
     def build(self):
         return self.mb.build()
 
@@ -875,6 +987,60 @@ class FGraph(_ReindexOps):
         self.mb.op(kind, [x], [y])
         return y
 
+    # --- the ops of a transformer's LayerNorm and MLP (QGraph's names) ---------
+    def const(self, values, kind="const"):
+        v = np.asarray(values, np.float32)
+        t = self._const(v, kind)
+        self.meta[t] = (list(v.shape), None, None)
+        return t
+
+    def _binary(self, kind, options, a, b, act="NONE"):
+        shape = [int(d) for d in np.broadcast_shapes(tuple(self.meta[a][0]), tuple(self.meta[b][0]))]
+        y = self._act(shape)
+        self.mb.op(kind, [a, b], [y], OPT[options], act_options(act) if options != "SquaredDifferenceOptions" else Table())
+        return y
+
+    def sub(self, a, b, act="NONE"):
+        return self._binary("SUB", "SubOptions", a, b, act)
+
+    def squared_difference(self, a, b):
+        return self._binary("SQUARED_DIFFERENCE", "SquaredDifferenceOptions", a, b)
+
+    def mean_last(self, x, keep_dims=True):
+        shp = self.meta[x][0]
+        at = self.mb.tensor(self._name("axes"), [1], np.int32, data=np.array([-1], np.int32))
+        y = self._act(list(shp[:-1]) + ([1] if keep_dims else []))
+        self.mb.op("MEAN", [x, at], [y], OPT["ReducerOptions"], Table().set(0, "b", int(keep_dims)))
+        return y
+
+    def rsqrt(self, x):
+        y = self._act(self.meta[x][0])
+        self.mb.op("RSQRT", [x], [y])
+        return y
+
+    def gelu(self, x, approximate=False):
+        y = self._act(self.meta[x][0])
+        self.mb.op("GELU", [x], [y], OPT["GeluOptions"], Table().set(0, "b", int(approximate)))
+        return y
+
+    def layer_norm(self, x, eps=1e-6):
+        """QGraph.layer_norm's ten ops in float32"""
+        C = self.meta[x][0][-1]
+        gamma = self.const(self.rng.uniform(0.5, 1.5, C), "gamma")
+        beta = self.const(self.rng.normal(0.0, 0.3, C), "beta")
+        m = self.mean_last(x)
+        v = self.mean_last(self.squared_difference(x, m))
+        r = self.rsqrt(self._binary("ADD", "AddOptions", v, self.const([eps], "eps")))
+        g = self._binary("MUL", "MulOptions", r, gamma)
+        a = self._binary("MUL", "MulOptions", x, g)
+        b = self._binary("MUL", "MulOptions", m, g)
+        return self._binary("ADD", "AddOptions", a, self.sub(beta, b))
+
+    def mlp(self, x, hidden, residual=None):
+        c = self.meta[x][0][-1]
+        h = self.gelu(self.fully_connected(x, hidden, keep_num_dims=True))
+        return self.add(self.fully_connected(h, c, keep_num_dims=True), x if residual is None else residual)
+
     def build(self):
         return self.mb.build()
 
@@ -983,10 +1149,10 @@ def shufflenet_v1(dtype=np.int8, seed=5, size=224, groups=3, width=1.0, batch=1,
 # BASELINE C3 mix: detection / segmentation / pose heads on MobileNet trunks
 # (synthetic weights, 224x224 inputs - "synthetic 224x224 batches", §8(d))
 # ---------------------------------------------------------------------------
-def _attention(g, x, heads):
+def _attention(g, x, heads, residual=None):
     """One multi-head self-attention block on x [B, T, C] (no LayerNorm): Q, K, V
     projections, per-head softmax(Q K^T / sqrt(D)) V, output projection,
-    residual ADD.  The float model's 1 / sqrt(D) leaves no op: it is folded
+    residual ADD (with x, or with `residual`: a pre-norm block's input).  The float model's 1 / sqrt(D) leaves no op: it is folded
     into the Q projection (its output scale, so its filter scale, is the
     input's over sqrt(D); the fp16 model scales the Q weights), and the scores'
     scale then stands for Q K^T / sqrt(D)."""
@@ -1008,7 +1174,7 @@ def _attention(g, x, heads):
     ctx = g.batch_matmul(p, v, out_scale=g.meta[v][1] if quant else None)  # [B, H, T, D]
     ctx = g.reshape(g.transpose(ctx, (0, 2, 1, 3)), [b, t, c])
     y = g.fully_connected(ctx, c, keep_num_dims=True)
-    return g.add(y, x)
+    return g.add(y, x if residual is None else residual)
 
 
 def attention_block(dtype=np.int8, seed=6, tokens=196, dim=192, heads=3, batch=1):
@@ -1016,8 +1182,7 @@ def attention_block(dtype=np.int8, seed=6, tokens=196, dim=192, heads=3, batch=1
     (keep_num_dims), RESHAPE / TRANSPOSE to [batch, heads, tokens, dim / heads],
     BATCH_MATMUL(adj_y) -> SOFTMAX -> BATCH_MATMUL, TRANSPOSE / RESHAPE back,
     FULLY_CONNECTED, ADD with the input.  dtype float32 (or float16) builds the
-    fp16-constant float model.  LayerNorm is left out (its int8 MEAN over
-    channels / SQUARED_DIFFERENCE / RSQRT chain is not lowered yet)."""
+    fp16-constant float model.  No LayerNorm: encoder_block has it."""
     if np.dtype(dtype) in (np.dtype(np.float32), np.dtype(np.float16)):
         g = FGraph(seed, "attention_block_f32")
     else:
@@ -1027,17 +1192,42 @@ def attention_block(dtype=np.int8, seed=6, tokens=196, dim=192, heads=3, batch=1
     return g.build()
 
 
-def vit_tiny(dtype=np.int8, seed=7, size=224, dim=192, heads=3, blocks=2, batch=1):
+def _encoder(g, x, heads, hidden, layer_norm=True, mlp=True):
+    """The pre-norm transformer block on x [B, T, C]: x + attention(LN(x)),
+    then the same around the MLP (FULLY_CONNECTED -> GELU -> FULLY_CONNECTED)."""
+    y = _attention(g, g.layer_norm(x) if layer_norm else x, heads, residual=x)
+    if mlp:
+        y = g.mlp(g.layer_norm(y) if layer_norm else y, hidden, residual=y)
+    return y
+
+
+def encoder_block(dtype=np.int8, seed=8, tokens=196, dim=192, heads=3, hidden=768, batch=1):
+    """One pre-norm transformer encoder block on [batch, tokens, dim]:
+    LayerNorm (the converter's ten ops, see QGraph.layer_norm) -> attention
+    (attention_block's) -> LayerNorm -> MLP (FULLY_CONNECTED to `hidden`, GELU,
+    FULLY_CONNECTED back), with the residual ADDs.  dtype float32 (or float16)
+    builds the fp16-constant float model."""
+    if np.dtype(dtype) in (np.dtype(np.float32), np.dtype(np.float16)):
+        g = FGraph(seed, "encoder_block_f32")
+    else:
+        g = QGraph(dtype, seed, "encoder_block_%s" % np.dtype(dtype).name)
+    x = g.input([batch, tokens, dim], scale=0.05)
+    g.output(_encoder(g, x, heads, hidden))
+    return g.build()
+
+
+def vit_tiny(dtype=np.int8, seed=7, size=224, dim=192, heads=3, blocks=2, batch=1, layer_norm=False, mlp=False):
     """ViT-Tiny's front: a 16 x 16 stride-16 patch CONV_2D, RESHAPE to tokens
-    [batch, (size / 16)^2, dim] and `blocks` attention blocks.  No class token,
-    no position embedding, no MLP and no LayerNorm (see attention_block)."""
+    [batch, (size / 16)^2, dim] and `blocks` attention blocks; with layer_norm
+    / mlp, pre-norm encoder blocks (encoder_block's, hidden = 4 dim).  No
+    class token and no position embedding."""
     g = QGraph(dtype, seed, "vit_tiny_%s" % np.dtype(dtype).name)
     x = g.input([batch, size, size, 3], scale=0.05)
     y = g.conv(x, dim, k=16, stride=16, act="NONE", padding="VALID")
     n = (size // 16) ** 2
     y = g.reshape(y, [batch, n, dim])
     for _ in range(blocks):
-        y = _attention(g, y, heads)
+        y = _encoder(g, y, heads, 4 * dim, layer_norm, mlp) if (layer_norm or mlp) else _attention(g, y, heads)
     g.output(y)
     return g.build()
 

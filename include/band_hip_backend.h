@@ -195,6 +195,21 @@ int bhx_cpu_conv_grouped(const void* grouped_params);
  * `batch_matmul_params` is a bh_batch_matmul_params.  Refuses what the
  * launchers refuse (bh_batch_matmul_check). */
 int bhx_cpu_batch_matmul(const void* batch_matmul_params, int is_float32);
+/* CpuMeanRows, the host twin of bh_mean_rows (`mean_rows_params` is a
+ * bh_mean_rows_params over host pointers; refuses what bh_mean_rows_check
+ * refuses), CpuEltwise over a bh_eltwise_params (ADD / SUB / MUL and
+ * BH_ELT_SQDIFF) and CpuUnaryF32 for LOGISTIC / RSQRT / GELU. */
+int bhx_cpu_mean_rows(const void* mean_rows_params);
+int bhx_cpu_eltwise(const void* eltwise_params);
+int bhx_cpu_unary_f32(int kind, const float* in, float* out, long n);
+/* The 256-entry tables the 8-bit RSQRT (int8) and GELU lower to, indexed by
+ * the input byte, and squared_difference.cc's multipliers as {m1, s1, m2, s2,
+ * mo, so, left_shift}; non-zero (bhx_last_error names the reason) for scales
+ * TFLite's Prepare refuses. */
+int bhx_rsqrt_table(float in_scale, int in_zp, float out_scale, int out_zp, uint8_t* table);
+int bhx_gelu_table(int is_signed, int approximate, float in_scale, int in_zp, float out_scale, int out_zp,
+                   uint8_t* table);
+int bhx_squared_difference_params(float s1, float s2, float so, int32_t* out7);
 
 /* --- job batching (extension, backend/hip/job_batching.h) -------------
  * Not in the reference interface: Band runs one job per ExecuteSubgraph

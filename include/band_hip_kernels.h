@@ -32,6 +32,9 @@
  *   bh_resize_bilinear_u8 <- RESIZE_BILINEAR uint8 (optimized_ops::ResizeBilinear, float path)
  *   bh_softmax_i8     <- SOFTMAX 8-bit      (optimized_ops::Softmax, lookup-table path)
  *   bh_mean           <- MEAN               (optimized_integer_ops::Mean / optimized_ops::Mean)
+ *   bh_mean_rows      <- MEAN 8-bit over the last axis (reference_ops::Mean / QuantizedMeanOrSum)
+ *   (SQUARED_DIFFERENCE int8 runs through bh_eltwise_i8, BH_ELT_SQDIFF; RSQRT int8 and
+ *    GELU 8-bit as bh_lut_u8 tables; GELU float32 through bh_unary_f32)
  *   bh_argminmax      <- ARG_MAX / ARG_MIN  (reference_ops::ArgMinMax: first extreme, strict compare)
  *   bh_resize_bilinear_argminmax_i8 <- RESIZE_BILINEAR int8 -> ARG_MAX / ARG_MIN over channels, fused
  *   bh_reindex        <- TRANSPOSE, STRIDED_SLICE, SLICE, SPLIT, SPLIT_V, SPACE_TO_DEPTH,
@@ -300,8 +303,14 @@ typedef struct bh_fc_params {
  * NEGATED zero points in each tensor's own domain (TFLite input*_offset). */
 #define BH_ELT_ADD 0
 #define BH_ELT_MUL 1
+/* SQUARED_DIFFERENCE int8 (squared_difference.cc, left_shift 7): both inputs
+ * scaled as ADD's, out = MBQMSmallerThanOneExp((a' - b')^2, o_mult, o_shift) +
+ * o_off, clamped to act_min / act_max (the type's range: no fused activation).
+ * bh_eltwise_i8 runs it through eltwise_sqdiff_kernel, an instantiation apart
+ * from the ADD / MUL kernels. */
+#define BH_ELT_SQDIFF 2
 typedef struct bh_eltwise_params {
-  int kind;                       /* BH_ELT_ADD (also SUB) or BH_ELT_MUL */
+  int kind;                       /* BH_ELT_ADD (also SUB), BH_ELT_MUL or BH_ELT_SQDIFF */
   int in_signed;                  /* 1 int8, 0 uint8 (both inputs, output) */
   int shape_a[4], shape_b[4], shape_o[4];
   int32_t a_off, b_off, o_off;
@@ -484,6 +493,73 @@ typedef struct bh_mean_params {
 } bh_mean_params;
 int bh_mean(const bh_mean_params* p, bh_stream_t s);
 
+/* MEAN of an int8 / uint8 tensor over its last axis (reduce.cc EvalMean, the
+ * two branches the 4-D {1, 2} form above does not take), the input viewed as
+ * [rows][depth] with an int32 sum per row:
+ *   exact != 0 (input and output share scale and zero point,
+ *     reference_ops::Mean): out = (T)(sum / depth), C++ integer division;
+ *   exact == 0 (reference_ops::QuantizedMeanOrSum, compute_sum false), every
+ *     step a float32 operation of its own:
+ *     out = clamp((int)roundf((float)sum / (float)depth * scale + bias) + out_zp)
+ *     with scale = s_in / s_out and bias = -zp_in * scale + 0.5f from the caller.
+ * mean_rows_kernel: one wave per row, 4 rows per workgroup, dword reads where
+ * the row is 4-byte aligned, a cross-lane sum.  Refused (BH_EINVAL,
+ * bh_last_error names the reason): null pointers, rows or depth < 1, type not
+ * 1 / 2, depth * 255 >= 2^31, rows >= 2^31. */
+typedef struct bh_mean_rows_params {
+  long rows;
+  int depth;
+  int type;                       /* 1 int8, 2 uint8 */
+  int exact;
+  float scale, bias;
+  int32_t out_zp;
+  const void* input;
+  void* output;
+} bh_mean_rows_params;
+int bh_mean_rows(const bh_mean_rows_params* p, bh_stream_t s);
+/* "mean_rows_kernel", or "" for parameters bh_mean_rows refuses; static storage */
+const char* bh_mean_rows_kernel(const bh_mean_rows_params* p);
+/* the launcher's parameter check alone; pure host */
+int bh_mean_rows_check(const bh_mean_rows_params* p);
+
+/* The ten ops a converter makes of an int8 LayerNormalization over the last
+ * axis of x [rows][depth], as one launch (layernorm_i8_kernel):
+ *   m = MEAN(x)  d = SQUARED_DIFFERENCE(x, m)  v = MEAN(d)  e = ADD(v, eps)
+ *   r = RSQRT(e)  g = MUL(r, gamma)  a = MUL(x, g)  b = MUL(m, g)
+ *   c = SUB(beta, b)  y = ADD(a, c)
+ * with the operand order as written.  Every op's requantisation is performed
+ * in that order with the device functions of the single-op kernels, each
+ * intermediate rounded and clamped to its own int8 value, so y is byte for
+ * byte what the ten launches store; the intermediates are not stored.  One
+ * wave per row, 4 rows per workgroup, the row in registers: 16 values per lane
+ * x 64 lanes, so depth <= BH_LAYERNORM_MAX_DEPTH = 1024.  The RSQRT table and
+ * the gamma / beta rows are staged in LDS once per workgroup.
+ * The parameter blocks are the single ops' own (lower.cc fills them the same
+ * way); their pointers and shapes are ignored, the tensors are:
+ *   input [rows][depth], gamma [depth], beta [depth], rsqrt_table [256],
+ *   eps_q the one byte of the eps constant, output [rows][depth].
+ * Refused (BH_EINVAL, bh_last_error names the reason): null pointers, rows or
+ * depth < 1, depth above the limit, rows >= 2^31, a MEAN block that disagrees
+ * on depth or is not int8, a binary block that is not int8 or of the wrong
+ * kind. */
+#define BH_LAYERNORM_MAX_DEPTH 1024
+typedef struct bh_layernorm_params {
+  long rows;
+  int depth;
+  bh_mean_rows_params mean_x, mean_d;
+  bh_eltwise_params sqdiff, add_eps, mul_gamma, mul_x, mul_m, sub_beta, add_out;
+  int32_t eps_q;
+  const void* rsqrt_table;
+  const void* input;
+  const void* gamma;
+  const void* beta;
+  void* output;
+} bh_layernorm_params;
+int bh_layernorm_i8(const bh_layernorm_params* p, bh_stream_t s);
+/* "layernorm_i8_kernel", or "" for parameters bh_layernorm_i8 refuses; static storage */
+const char* bh_layernorm_i8_kernel(const bh_layernorm_params* p);
+int bh_layernorm_i8_check(const bh_layernorm_params* p);
+
 /* ---- host-side operand packing (pure CPU, no device calls) -------------- */
 
 /* Pack OHWI conv weights ([out_c][k_h*k_w*in_c] bytes, signed or unsigned)
@@ -606,6 +682,8 @@ int bh_pool_f32(const bh_pool_f32_params* p, bh_stream_t s);
 #define BH_UNARY_CLAMP 0    /* RELU / RELU6 / RELU_N1_TO_1: min(max(x, lo), hi) */
 #define BH_UNARY_LOGISTIC 1 /* 1 / (1 + exp(-x)) */
 #define BH_UNARY_RSQRT 2    /* RSQRT: 1 / sqrt(x) */
+#define BH_UNARY_GELU 3     /* GELU: 0.5 x (1 + erf(x / sqrt 2)) */
+#define BH_UNARY_GELU_TANH 4 /* GELU, approximate: 0.5 x (1 + tanh(sqrt(2 / pi) x (1 + 0.044715 x^2))) */
 int bh_unary_f32(int kind, const float* in, float* out, long n, float lo, float hi, bh_stream_t s);
 
 /* reference_ops::Softmax (float): per row exp((x - max) * beta) / sum */
