@@ -191,6 +191,24 @@ class SoftmaxParams(ctypes.Structure):
                 ("out_scale", ctypes.c_float), ("out_zp", c_int32), ("input", c_void_p), ("output", c_void_p)]
 
 
+ATTENTION_MAX_KEYS, ATTENTION_MAX_DIM, ATTN_BYTES = 1024, 128, 1
+
+
+class AttentionQuant(ctypes.Structure):
+    """one product's quantisation, as BatchMatMulParams carries it"""
+    _fields_ = [(n, c_int32) for n in ("lhs_zp", "rhs_zp", "out_zp", "mult", "shift", "requant_fast")]
+
+
+class AttentionParams(ctypes.Structure):
+    """bh_attention_params: q, k, v and out by strides (elements); a batch stride of 0 broadcasts"""
+    _fields_ = [("batch", c_int32 * 2)] + [(n, c_int32) for n in ("rows", "keys", "head_dim", "out_dim")] + [
+        (n, ctypes.c_int64 * 2) for n in ("q_bstride", "k_bstride", "v_bstride", "out_bstride")] + [
+        (n, ctypes.c_int64) for n in ("q_row_stride", "k_row_stride", "v_row_stride", "out_row_stride",
+                                      "q_inner_stride", "k_inner_stride", "v_inner_stride", "out_inner_stride")] + [
+        ("qk", AttentionQuant), ("pv", AttentionQuant), ("table", c_void_p), ("sm_out_scale", ctypes.c_float),
+        ("sm_out_zp", c_int32), ("kernel_hint", c_int32)] + [(n, c_void_p) for n in ("q", "k", "v", "out")]
+
+
 class ZeroInsertParams(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("batch", "in_h", "in_w", "channels", "stride_h", "stride_w", "out_h",
                                      "out_w")] + [("fill", ctypes.c_uint32), ("input", c_void_p), ("output", c_void_p)]
@@ -300,6 +318,10 @@ KERNEL_SYMBOLS = {
     "bh_batch_matmul_f32": (c_int, [ctypes.POINTER(BatchMatMulParams), c_void_p]),
     "bh_batch_matmul_check": (c_int, [ctypes.POINTER(BatchMatMulParams), c_int]),
     "bh_softmax_i8": (c_int, [ctypes.POINTER(SoftmaxParams), c_void_p]),
+    "bh_attention_i8": (c_int, [ctypes.POINTER(AttentionParams), c_void_p]),
+    "bh_attention_i8_kernel": (ctypes.c_char_p, [ctypes.POINTER(AttentionParams)]),
+    "bh_attention_i8_check": (c_int, [ctypes.POINTER(AttentionParams)]),
+    "bh_attention_i8_lds_bytes": (c_size_t, [ctypes.POINTER(AttentionParams)]),
     "bh_zero_insert": (c_int, [ctypes.POINTER(ZeroInsertParams), c_void_p]),
     "bh_conv2d_f32": (c_int, [ctypes.POINTER(ConvF32Params), c_void_p]),
     "bh_conv2d_f32_split": (c_int, [ctypes.POINTER(ConvF32Params)]),

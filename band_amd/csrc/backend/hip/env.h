@@ -50,6 +50,8 @@ inline bool CoalesceFailBuild() { return Int("BAND_HIP_COALESCE_FAIL_BUILD", 0, 
 inline bool GpuDetection() { return Flag("BAND_HIP_GPU_DETECTION", false); }
 // 0: job-batch variants capture their graphs lazily
 inline bool Precapture() { return Flag("BAND_HIP_PRECAPTURE", true); }
+// 1: BATCH_MATMUL -> SOFTMAX -> BATCH_MATMUL (int8) as one attention_i8_kernel launch on kGPU executors
+inline bool FusedAttention() { return Flag("BAND_HIP_FUSED_ATTENTION", false); }
 // 1: kernels without the host copies (tools/concurrency_probe.py --no-io)
 inline bool ProbeNoIo() { return Flag("BAND_HIP_PROBE_NO_IO", false); }
 // file the chain tuner's decisions persist in (unset or empty: none)

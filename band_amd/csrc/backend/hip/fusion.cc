@@ -897,6 +897,187 @@ void HipModelExecutor::FuseLayerNorm(const HipModel& model, PreparedSubgraph* sg
   sg->launches.swap(out);
 }
 
+// The attention core of a converted int8 block, three consecutive launches
+//   scores = BATCH_MATMUL(q, k, adj_y)   p = SOFTMAX(scores)   ctx = BATCH_MATMUL(p, v)
+// becomes one attention_i8_kernel launch (BAND_HIP_FUSED_ATTENTION=1, kGPU)
+// that carries the three parameter blocks as they were lowered, so it stores
+// the same bytes.  They qualify when scores and p are int8, are read only
+// inside the pattern (scores by the SOFTMAX, p by the second product as its
+// lhs), are no subgraph or model output and are not viewed (no_fuse /
+// extra_d2h), the softmax runs over the scores' last axis, the first product
+// has a K-contiguous rhs and no adj_x, the second no adjoint, and the
+// launcher's check takes the result (keys <= 1024, head_dim, out_dim <= 128).
+//   Head TRANSPOSEs.  q, k or v produced by a kReindex launch that is a
+// TRANSPOSE leaving the last axis in place, whose output nothing else reads
+// and nobody needs materialised, is read through strides from the TRANSPOSE's
+// input and that launch is dropped; a TRANSPOSE of the same kind that is
+// ctx's only reader is absorbed into the output strides, and the fused launch
+// then writes the TRANSPOSE's output tensor.  An operand that cannot be
+// absorbed stays the dense tensor it was.
+void HipModelExecutor::FuseAttention(const HipModel& model, PreparedSubgraph* sg) {
+  const TflModel& d = model.desc();
+  std::vector<Launch>& ls = sg->launches;
+  std::vector<bool> dead(ls.size(), false);
+  // op is a TRANSPOSE of rank 2 .. 4 that leaves the last axis in place
+  auto head_perm = [&](const TflOperator& op, std::vector<int64_t>* perm) {
+    if (op.builtin != kTflTranspose || op.inputs.size() < 2 || op.inputs[0] < 0 || op.inputs[1] < 0 ||
+        op.outputs.size() != 1)
+      return false;
+    const size_t r = d.tensors[op.inputs[0]].shape.size();
+    if (r < 2 || r > 4 || !ConstInts(d.tensors[op.inputs[1]], perm) || perm->size() != r) return false;
+    std::vector<bool> seen(r, false);
+    for (int64_t p : *perm) {
+      if (p < 0 || p >= static_cast<int64_t>(r) || seen[p]) return false;
+      seen[p] = true;
+    }
+    return perm->back() == static_cast<int64_t>(r) - 1;
+  };
+  auto dense_strides = [](const std::vector<int>& shape) {
+    std::vector<int64_t> s(shape.size(), 1);
+    for (int k = static_cast<int>(shape.size()) - 2; k >= 0; --k) s[k] = s[k + 1] * shape[k + 1];
+    return s;
+  };
+  // a matrix operand of dims `dm` walked at strides `st`: its batch strides (0 for a dim of 1) and row stride
+  auto operand = [](const std::vector<int64_t>& dm, const std::vector<int64_t>& st, int64_t* bstride, int64_t* row) {
+    const int r = static_cast<int>(dm.size());
+    bstride[0] = bstride[1] = 0;
+    for (int k = 0; k < r - 2; ++k) bstride[2 - (r - 2) + k] = dm[k] == 1 ? 0 : st[k];
+    *row = st[r - 2];
+  };
+  // operand tensor t of op `reader`, at `ptr`: when a head TRANSPOSE launch made it for that op alone, the launch
+  // (its index) and the strides that read the TRANSPOSE's input instead
+  auto absorb_in = [&](size_t before, int t, int reader, const void* ptr, int64_t* bstride, int64_t* row,
+                       const void** src) -> int {
+    for (size_t j = before; j-- > 0;) {
+      const Launch& r = ls[j];
+      if (dead[j] || r.kind != Launch::kReindex || r.reindex.output != ptr || r.out_tensor != t) continue;
+      const TflOperator& op = d.ops[r.op_index];
+      std::vector<int64_t> perm;
+      if (!head_perm(op, &perm) || op.outputs[0] != t || !PrivateTensor(d, *sg, t, reader)) return -1;
+      const TflTensor& x = d.tensors[op.inputs[0]];
+      const std::vector<int64_t> xs = dense_strides(x.shape);
+      std::vector<int64_t> dm, st;
+      for (int64_t p : perm) {
+        dm.push_back(x.shape[p]);
+        st.push_back(xs[p]);
+      }
+      operand(dm, st, bstride, row);
+      *src = r.reindex.input;
+      return static_cast<int>(j);
+    }
+    return -1;
+  };
+  for (size_t i = 0; i + 2 < ls.size(); ++i) {
+    const Launch &A = ls[i], &S = ls[i + 1], &B = ls[i + 2];
+    if (A.kind != Launch::kBatchMatMul || S.kind != Launch::kSoftmax || B.kind != Launch::kBatchMatMul) continue;
+    if (A.op_index < 0 || S.op_index < 0 || B.op_index < 0) continue;
+    const TflOperator &oa = d.ops[A.op_index], &os = d.ops[S.op_index], &ob = d.ops[B.op_index];
+    if (oa.builtin != kTflBatchMatMul || os.builtin != kTflSoftmax || ob.builtin != kTflBatchMatMul) continue;
+    auto adj = [](const TflOperator& op, int k) { return op.options.valid() && op.options.Int8(k, 0) != 0; };
+    if (adj(oa, 0) || !adj(oa, 1) || adj(ob, 0) || adj(ob, 1)) continue;
+    const int sc = oa.outputs[0], pr = os.outputs[0], ctx = ob.outputs[0];
+    if (os.inputs[0] != sc || ob.inputs[0] != pr || ob.inputs[1] == pr || A.out_tensor != sc || S.out_tensor != pr ||
+        B.out_tensor != ctx)
+      continue;
+    if (d.tensors[sc].type != DataType::kInt8 || d.tensors[pr].type != DataType::kInt8) continue;
+    if (!PrivateTensor(d, *sg, sc, S.op_index) || !PrivateTensor(d, *sg, pr, B.op_index)) continue;
+    const bh_batch_matmul_params &a = A.bmm, &b = B.bmm;
+    const bh_softmax_params& s = S.softmax;
+    if (s.input != a.out || s.output != b.lhs || !s.is_signed || s.depth != a.n ||
+        s.rows != static_cast<long>(a.batch[0]) * a.batch[1] * a.m)
+      continue;
+    if (b.batch[0] != a.batch[0] || b.batch[1] != a.batch[1] || b.m != a.m || b.k != a.n) continue;
+    Launch F;
+    F.kind = Launch::kAttention;
+    F.op_index = A.op_index;
+    F.out_tensor = ctx;
+    bh_attention_params& p = F.attn;
+    p = bh_attention_params{};
+    p.batch[0] = a.batch[0];
+    p.batch[1] = a.batch[1];
+    p.rows = a.m;
+    p.keys = a.n;
+    p.head_dim = a.k;
+    p.out_dim = b.n;
+    p.q_inner_stride = p.k_inner_stride = p.v_inner_stride = p.out_inner_stride = 1;
+    for (int k = 0; k < 2; ++k) {
+      p.q_bstride[k] = a.lhs_bstride[k];
+      p.k_bstride[k] = a.rhs_bstride[k];
+      p.v_bstride[k] = b.rhs_bstride[k];
+    }
+    p.q_row_stride = a.lhs_row_stride;
+    p.k_row_stride = a.rhs_col_stride;
+    p.v_row_stride = b.rhs_k_stride;
+    p.out_bstride[1] = static_cast<int64_t>(b.m) * b.n;
+    p.out_bstride[0] = p.out_bstride[1] * b.batch[1];
+    p.out_row_stride = b.n;
+    p.qk = bh_attention_quant{a.lhs_zp, a.rhs_zp, a.out_zp, a.mult, a.shift, a.requant_fast};
+    p.pv = bh_attention_quant{b.lhs_zp, b.rhs_zp, b.out_zp, b.mult, b.shift, b.requant_fast};
+    p.table = s.table;
+    p.sm_out_scale = s.out_scale;
+    p.sm_out_zp = s.out_zp;
+    p.q = a.lhs;
+    p.k = a.rhs;
+    p.v = b.rhs;
+    p.out = b.out;
+    // the head TRANSPOSEs around the pattern
+    const int jq = absorb_in(i, oa.inputs[0], A.op_index, a.lhs, p.q_bstride, &p.q_row_stride, &p.q);
+    const int jk = oa.inputs[1] == oa.inputs[0] ? -1
+                                                : absorb_in(i, oa.inputs[1], A.op_index, a.rhs, p.k_bstride, &p.k_row_stride, &p.k);
+    const int jv = ob.inputs[1] == oa.inputs[0] || ob.inputs[1] == oa.inputs[1]
+                       ? -1
+                       : absorb_in(i, ob.inputs[1], B.op_index, b.rhs, p.v_bstride, &p.v_row_stride, &p.v);
+    int jo = -1;
+    for (size_t j = i + 3; j < ls.size() && jo < 0; ++j) {
+      const Launch& r = ls[j];
+      if (r.kind != Launch::kReindex || r.reindex.input != b.out) continue;
+      const TflOperator& op = d.ops[r.op_index];
+      std::vector<int64_t> perm;
+      if (!head_perm(op, &perm) || op.inputs[0] != ctx || r.out_tensor != op.outputs[0] ||
+          !PrivateTensor(d, *sg, ctx, r.op_index))
+        break;
+      // ctx axis perm[k] is the TRANSPOSE's output axis k
+      const std::vector<int64_t> ys = dense_strides(d.tensors[op.outputs[0]].shape);
+      std::vector<int64_t> dm(perm.size()), st(perm.size());
+      for (size_t k = 0; k < perm.size(); ++k) {
+        dm[perm[k]] = d.tensors[ctx].shape[perm[k]];
+        st[perm[k]] = ys[k];
+      }
+      operand(dm, st, p.out_bstride, &p.out_row_stride);
+      p.out = r.reindex.output;
+      F.out_tensor = r.out_tensor;
+      jo = static_cast<int>(j);
+    }
+    if (bh_attention_i8_check(&p) != 0) continue;  // over a limit: the three launches stay
+    F.kernel = bh_attention_i8_kernel(&p);
+    F.alg_ops = A.alg_ops + B.alg_ops;
+    F.alg_bytes = static_cast<double>(meta_[oa.inputs[0]]->bytes + meta_[oa.inputs[1]]->bytes + meta_[ob.inputs[1]]->bytes +
+                                      meta_[ctx]->bytes) + 1024.0;
+    sg->fused_ops.insert(S.op_index);
+    sg->fused_ops.insert(B.op_index);
+    sg->fused_tensors.insert(sc);
+    sg->fused_tensors.insert(pr);
+    for (int j : {jq, jk, jv}) {
+      if (j < 0) continue;
+      dead[j] = true;
+      sg->fused_ops.insert(ls[j].op_index);
+      sg->fused_tensors.insert(ls[j].out_tensor);
+    }
+    if (jo >= 0) {
+      dead[jo] = true;
+      sg->fused_ops.insert(ls[jo].op_index);
+      sg->fused_tensors.insert(ctx);
+    }
+    dead[i + 1] = dead[i + 2] = true;
+    ls[i] = F;
+    i += 2;
+  }
+  std::vector<Launch> out;
+  for (size_t i = 0; i < ls.size(); ++i)
+    if (!dead[i]) out.push_back(ls[i]);
+  sg->launches.swap(out);
+}
+
 // Folds `conv -> ADD/SUB(conv_out, residual)` into the conv epilogue when the
 // conv output has no other reader and nobody needs it materialised.  The
 // epilogue reproduces both TFLite ops exactly (conv requant + clamp to the

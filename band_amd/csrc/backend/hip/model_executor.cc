@@ -88,6 +88,7 @@ std::unique_ptr<HipModelExecutor> HipModelExecutor::MakeLane() {
   lane->direct_io_ = true;
   lane->autotune_ = autotune_;
   lane->gpu_detection_ = gpu_detection_;
+  lane->fused_attention_ = fused_attention_;
   return lane;
 }
 
@@ -326,6 +327,7 @@ absl::Status HipModelExecutor::EnsureMeta(const HipModel& model) {
   if (std::strcmp(f, "forcedense") == 0) forced_chain_ = ForcedChain::kDense;  // ... in the dense form
   if (std::strcmp(f, "nostage") == 0) no_stage_chain_ = true;  // A-B: without the stage forms
   if (!env::Autotune()) autotune_ = false;
+  if (fused_attention_ < 0) fused_attention_ = env::FusedAttention() ? 1 : 0;
   return absl::OkStatus();
 }
 
@@ -649,6 +651,7 @@ absl::Status HipModelExecutor::EnqueueLaunch(const Launch& l) {
     case Launch::kBatchMatMulF32: rc = bh_batch_matmul_f32(&l.bmm, stream_); break;
     case Launch::kMeanRows: rc = bh_mean_rows(&l.mrows, stream_); break;
     case Launch::kLayerNorm: rc = bh_layernorm_i8(&l.ln, stream_); break;
+    case Launch::kAttention: rc = bh_attention_i8(&l.attn, stream_); break;
     case Launch::kMean: {
       bh_mean_params q{};
       q.outer = l.mean.outer;

@@ -56,7 +56,8 @@ struct Launch {
     kConvGrouped,     // grouped CONV_2D: `conv` with the total channel counts + conv_groups (never chained / grouped / blocked)
     kBatchMatMul,     // BATCH_MATMUL int8 (BatchMatMulArgs -> `bmm`; never chained / grouped / blocked, no epilogue folds)
     kBatchMatMulF32,  // BATCH_MATMUL float32
-    kLayerNorm        // the ten ops of an int8 LayerNorm as one launch (FuseLayerNorm; kGPU)
+    kLayerNorm,       // the ten ops of an int8 LayerNorm as one launch (FuseLayerNorm; kGPU)
+    kAttention        // BATCH_MATMUL -> SOFTMAX -> BATCH_MATMUL (int8) as one launch (FuseAttention; kGPU, opt-in)
   } kind;
   int op_index = -1;
   int out_tensor = -1;  // tensor this launch materialises (after epilogue fusions)
@@ -94,6 +95,7 @@ struct Launch {
   bh_resize_argminmax_params rzarg{};
   bh_reindex_params reindex{};
   bh_batch_matmul_params bmm{};
+  bh_attention_params attn{};
   const void* table = nullptr;  // kLutU8 / kLutF32: 256-entry device table
   long count = 0;               // kLut* / kQuantF32: elements
   float q_scale = 0.f;          // kQuantF32
@@ -237,6 +239,9 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   // int8 RESIZE_BILINEAR -> ARG_MAX / ARG_MIN over channels as one launch (kGPU)
   void FuseGlue(const HipModel& model, PreparedSubgraph* sg);
   void FuseLayerNorm(const HipModel& model, PreparedSubgraph* sg);
+  // int8 BATCH_MATMUL(adj_y) -> SOFTMAX -> BATCH_MATMUL into one bh_attention_i8
+  // launch that reads and writes through the head TRANSPOSEs around it
+  void FuseAttention(const HipModel& model, PreparedSubgraph* sg);
   // independent small convs (detector / pose heads) deferred past later
   // launches that do not touch them and issued as one conv_group launch
   absl::Status GroupConvs(PreparedSubgraph* sg);
@@ -347,6 +352,10 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   // executor's kGPU set.  Off by default: the reference places the op on
   // the CPU worker, and so does this backend unless asked.
   bool gpu_detection_ = false;
+  // BAND_HIP_FUSED_ATTENTION=1, latched when the executor binds its model
+  // (-1: not yet; lanes and job-batch variants take their parent's): the
+  // attention core as one launch on a kGPU executor.  Off by default.
+  int fused_attention_ = -1;
   std::map<SubgraphKey, std::unique_ptr<PreparedSubgraph>> subgraphs_;
   int ordinal_ = -1;
   bh_stream_t stream_ = nullptr;

@@ -892,6 +892,60 @@ typedef struct {
 } bh_softmax_params;
 int bh_softmax_i8(const bh_softmax_params* p, bh_stream_t s);
 
+/* The int8 attention core as one launch (attention_i8_kernel):
+ *   out[b0, b1] = BATCH_MATMUL(SOFTMAX(BATCH_MATMUL(q[b0, b1], k[b0, b1]^T)), v[b0, b1])
+ * on q [rows, head_dim], k [keys, head_dim], v [keys, out_dim] and out
+ * [rows, out_dim] per batch index.  The stored bytes are those of
+ * bh_batch_matmul_i8 (both operands K-contiguous) -> bh_softmax_i8 (int8) ->
+ * bh_batch_matmul_i8 (rhs K-strided): the scores are requantised and clamped
+ * to int8 before the softmax, the probabilities are int8 before the second
+ * product, and the softmax's row sum is the float32 sum over the keys in
+ * order.  Scores and probabilities live in LDS only.
+ *   Operands by strides in elements (two batch strides, 0 = broadcast, a row
+ * stride and an inner stride that must be 1), so [B, T, H, D] tensors are
+ * read and written as [B, H, T, D] without a TRANSPOSE.
+ *   qk / pv: each product's quantisation as bh_batch_matmul_params carries it
+ * (pv.lhs_zp is the probabilities' zero point); table / sm_out_scale /
+ * sm_out_zp as bh_softmax_params carries them.
+ *   A workgroup holds 64 query rows' scores in an LDS strip of 64 x
+ * (roundup(keys, 64) + 16) bytes, hence keys <= BH_ATTENTION_MAX_KEYS, and
+ * each wave keeps its q fragments in registers, hence head_dim <= 128; out_dim
+ * <= 128 (eight accumulator tiles per wave).
+ * Refused (BH_EINVAL, bh_last_error names the reason): null pointers,
+ * non-positive extents, keys / head_dim / out_dim above their limits, a batch
+ * dim above 65535, negative strides, a non-unit inner stride, 2^31 or more
+ * elements in a tensor, a multiplier / shift out of range.  No scratch, no
+ * atomics. */
+#define BH_ATTENTION_MAX_KEYS 1024
+#define BH_ATTENTION_MAX_DIM 128
+/* kernel_hint bits (parity tests) */
+#define BH_ATTN_BYTES 1 /* 1-byte fragment units whatever the alignment */
+typedef struct bh_attention_quant {
+  int32_t lhs_zp, rhs_zp, out_zp, mult, shift, requant_fast;
+} bh_attention_quant;
+typedef struct bh_attention_params {
+  int32_t batch[2], rows, keys, head_dim, out_dim;
+  int64_t q_bstride[2], k_bstride[2], v_bstride[2], out_bstride[2];
+  int64_t q_row_stride, k_row_stride, v_row_stride, out_row_stride;
+  int64_t q_inner_stride, k_inner_stride, v_inner_stride, out_inner_stride; /* 1 */
+  bh_attention_quant qk, pv;
+  const float* table; /* [256] device: bh_softmax_params.table of the scores' scale */
+  float sm_out_scale;
+  int32_t sm_out_zp;
+  int32_t kernel_hint;
+  const void* q;
+  const void* k;
+  const void* v;
+  void* out;
+} bh_attention_params;
+int bh_attention_i8(const bh_attention_params* p, bh_stream_t s);
+/* "attention_i8_kernel", or "" for parameters bh_attention_i8 refuses; static storage */
+const char* bh_attention_i8_kernel(const bh_attention_params* p);
+/* the launcher's parameter checks alone; pure host, 0 = would run */
+int bh_attention_i8_check(const bh_attention_params* p);
+/* bytes of LDS a launch of these extents takes (0 for refused parameters) */
+size_t bh_attention_i8_lds_bytes(const bh_attention_params* p);
+
 /* TRANSPOSE_CONV support: U[y*sh][x*sw][:] = in[y][x][:], every other
  * position of U (out_h x out_w = (in-1)*stride+1) holds `fill` (the input
  * zero point, so it contributes 0).  A transpose conv is then a stride-1
