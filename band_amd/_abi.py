@@ -181,6 +181,19 @@ class BatchMatMulParams(ctypes.Structure):
         (n, c_void_p) for n in ("lhs", "rhs", "out")]
 
 
+class DynQuantParams(ctypes.Structure):
+    """bh_dynquant_params: the per-row quantisation of a hybrid FULLY_CONNECTED's input"""
+    _fields_ = [("rows", ctypes.c_long), ("depth", c_int), ("asymmetric", c_int)] + [
+        (n, c_void_p) for n in ("input", "q", "scale", "offset")]
+
+
+class FcHybridParams(ctypes.Structure):
+    """bh_fc_hybrid_params: int8 rows x int8 weights, float32 epilogue"""
+    _fields_ = [(n, c_int) for n in ("rows", "depth", "depth_pad", "units")] + [
+        (n, ctypes.c_float) for n in ("w_scale", "act_min", "act_max")] + [
+        (n, c_void_p) for n in ("q", "in_scale", "in_offset", "weights", "w_row_sum", "bias", "output")]
+
+
 class ResizeBilinearU8Params(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("batch", "in_h", "in_w", "channels", "out_h", "out_w")] + [
         (n, c_void_p) for n in ("y_idx", "x_idx", "y_frac", "x_frac", "input", "output")]
@@ -317,6 +330,12 @@ KERNEL_SYMBOLS = {
     "bh_batch_matmul_i8_kernel": (ctypes.c_char_p, [ctypes.POINTER(BatchMatMulParams)]),
     "bh_batch_matmul_f32": (c_int, [ctypes.POINTER(BatchMatMulParams), c_void_p]),
     "bh_batch_matmul_check": (c_int, [ctypes.POINTER(BatchMatMulParams), c_int]),
+    "bh_dynquant_rows": (c_int, [ctypes.POINTER(DynQuantParams), c_void_p]),
+    "bh_dynquant_rows_kernel": (ctypes.c_char_p, [ctypes.POINTER(DynQuantParams)]),
+    "bh_dynquant_rows_check": (c_int, [ctypes.POINTER(DynQuantParams)]),
+    "bh_fc_hybrid": (c_int, [ctypes.POINTER(FcHybridParams), c_void_p]),
+    "bh_fc_hybrid_kernel": (ctypes.c_char_p, [ctypes.POINTER(FcHybridParams)]),
+    "bh_fc_hybrid_check": (c_int, [ctypes.POINTER(FcHybridParams)]),
     "bh_softmax_i8": (c_int, [ctypes.POINTER(SoftmaxParams), c_void_p]),
     "bh_attention_i8": (c_int, [ctypes.POINTER(AttentionParams), c_void_p]),
     "bh_attention_i8_kernel": (ctypes.c_char_p, [ctypes.POINTER(AttentionParams)]),

@@ -496,6 +496,22 @@ int bhx_cpu_mean_rows(const void* mean_rows_params) {
   return 0;
 }
 
+int bhx_cpu_dynquant_rows(const void* dynquant_params) {
+  const auto* p = static_cast<const bh_dynquant_params*>(dynquant_params);
+  if (bh_dynquant_rows_check(p) != 0) return Fail((std::string("CpuDynQuantRows: ") + bh_last_error()).c_str());
+  band::hip::CpuPool pool(1);
+  band::hip::CpuDynQuantRows(*p, pool);
+  return 0;
+}
+
+int bhx_cpu_fc_hybrid(const void* fc_hybrid_params) {
+  const auto* p = static_cast<const bh_fc_hybrid_params*>(fc_hybrid_params);
+  if (bh_fc_hybrid_check(p) != 0) return Fail((std::string("CpuFcHybrid: ") + bh_last_error()).c_str());
+  band::hip::CpuPool pool(1);
+  band::hip::CpuFcHybrid(*p, pool);
+  return 0;
+}
+
 int bhx_cpu_eltwise(const void* eltwise_params) {
   const auto* p = static_cast<const bh_eltwise_params*>(eltwise_params);
   if (!p || !p->a || !p->b || !p->out || p->kind < BH_ELT_ADD || p->kind > BH_ELT_SQDIFF)

@@ -1003,5 +1003,67 @@ void CpuBatchMatMulF32(const bh_batch_matmul_params& p, CpuPool& pool) {
   });
 }
 
+// ---- hybrid FULLY_CONNECTED (band_hip_kernels.h holds the rule) -------------
+// This file is built with -ffp-contract=off: x * inv, off + t, s * ws,
+// dot * sc and bias + prod each round once.
+
+void CpuDynQuantRows(const bh_dynquant_params& p, CpuPool& pool) {
+  pool.ParallelFor(p.rows, [&](long r0, long r1) {
+    for (long r = r0; r < r1; ++r) {
+      const float* x = p.input + r * p.depth;
+      int8_t* q = p.q + r * p.depth;
+      float mn = 0.f, mx = 0.f;
+      for (int k = 0; k < p.depth; ++k) {
+        mn = std::min(mn, x[k]);
+        mx = std::max(mx, x[k]);
+      }
+      float s = 1.f, inv = 0.f;
+      int32_t off = 0;
+      if (!p.asymmetric) {
+        const float rr = std::max(-mn, mx);
+        if (rr != 0.f) {
+          s = rr / 127.f;
+          inv = 127.f / rr;
+        }
+      } else if (mn != mx) {
+        const float range = mx - mn;
+        const double scale = static_cast<double>(range) / 255.0;
+        const double a = static_cast<double>(mn) / scale, b = static_cast<double>(mx) / scale;
+        const double z_min = -128.0 - a, z_max = 127.0 - b;
+        const double e_min = 128.0 + std::fabs(a), e_max = 127.0 + std::fabs(b);
+        const double z = e_min < e_max ? z_min : z_max;
+        off = z <= -128.0 ? -128 : (z >= 127.0 ? 127 : static_cast<int32_t>(static_cast<int8_t>(std::round(z))));
+        s = static_cast<float>(scale);
+        inv = 1.0f / s;
+      }
+      const float foff = static_cast<float>(off);
+      const int32_t lo = p.asymmetric ? -128 : -127;
+      for (int k = 0; k < p.depth; ++k) {
+        const float t = x[k] * inv;
+        q[k] = static_cast<int8_t>(Clamp(static_cast<int32_t>(std::round(foff + t)), lo, 127));
+      }
+      p.scale[r] = s;
+      p.offset[r] = off;
+    }
+  });
+}
+
+void CpuFcHybrid(const bh_fc_hybrid_params& p, CpuPool& pool) {
+  pool.ParallelFor(p.rows, [&](long r0, long r1) {
+    for (long r = r0; r < r1; ++r) {
+      const int8_t* q = p.q + r * p.depth;
+      const float sc = p.in_scale[r] * p.w_scale;
+      const int64_t off = p.in_offset[r];
+      for (int u = 0; u < p.units; ++u) {
+        const int64_t acc = Dot(q, p.weights + static_cast<long>(u) * p.depth_pad, p.depth);
+        const int32_t dot = static_cast<int32_t>(acc - off * p.w_row_sum[u]);
+        const float prod = static_cast<float>(dot) * sc;
+        const float y = (p.bias ? p.bias[u] : 0.f) + prod;
+        p.output[r * p.units + u] = std::min(std::max(y, p.act_min), p.act_max);
+      }
+    }
+  });
+}
+
 }  // namespace hip
 }  // namespace band

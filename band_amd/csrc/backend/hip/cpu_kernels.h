@@ -128,5 +128,12 @@ bool CpuReindex(const bh_reindex_params& p);
 void CpuBatchMatMul(const bh_batch_matmul_params& p, CpuPool& pool);
 void CpuBatchMatMulF32(const bh_batch_matmul_params& p, CpuPool& pool);
 
+// Hybrid FULLY_CONNECTED (float32 input, int8 weights): the host twins of
+// bh_dynquant_rows and bh_fc_hybrid with the rule of band_hip_kernels.h, one
+// float32 operation at a time (float64 where the rule says so), over the pool
+// by rows; validated by the caller
+void CpuDynQuantRows(const bh_dynquant_params& p, CpuPool& pool);
+void CpuFcHybrid(const bh_fc_hybrid_params& p, CpuPool& pool);
+
 }  // namespace hip
 }  // namespace band

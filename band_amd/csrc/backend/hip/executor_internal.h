@@ -135,6 +135,11 @@ inline bool FloatSupports(const TflModel& m, const TflOperator& op, std::string*
   const TflTensor& out = m.tensors[op.outputs[0]];
   if (op.builtin == kTflDequantize)
     return in.is_const() && out.type == DataType::kFloat32 ? true : no("float16 DEQUANTIZE of a constant only");
+  if (IsHybridWeightOp(m, op)) {
+    if (op.builtin != kTflFullyConnected) return no("hybrid CONV_2D / DEPTHWISE_CONV_2D (float32 input, int8 filter)");
+    const char* w = "";
+    return HybridFcArgs(m, op, nullptr, &w) ? true : no(w);
+  }
   if (out.type != DataType::kFloat32) return no("float32 output expected");
   switch (op.builtin) {
     case kTflConv2D:

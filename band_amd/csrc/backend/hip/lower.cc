@@ -605,6 +605,7 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
       return absl::OkStatus();
     }
     case kTflFullyConnected: {
+      if (IsHybridWeightOp(d, op)) return LowerFcHybrid(model, oi, in_ptr, out_ptr, ckey, sg, L);
       FcGeometry g;
       if (!FcArgs(d, op, &g, &why)) return Refused(op, why);
       bh_fc_f32_params& p = L->fcf;
@@ -945,6 +946,79 @@ absl::Status HipModelExecutor::LowerFc(const HipModel& model, int oi, void* in_p
   L->alg_ops = 2.0 * rows * units * depth;
   L->alg_bytes = static_cast<double>(rows) * depth + static_cast<double>(rows) * units +
                  static_cast<double>(units) * depth + 12.0 * units;
+  return absl::OkStatus();
+}
+
+// Hybrid FULLY_CONNECTED (float32 input, int8 filter).  Two launches: the
+// input's rows quantised into a scratch owned by this subgraph (q, then one
+// scale and one offset per row), then the int8 product with the float
+// epilogue.  The constant blob holds the filter packed as the int8 FC packs
+// it (K padded to 16 by zeros), the row sums sum_k w[u][k] and the bias.
+absl::Status HipModelExecutor::LowerFcHybrid(const HipModel& model, int oi, void* in_ptr, void* out_ptr,
+                                             const std::string& ckey, PreparedSubgraph* sg, Launch* L) {
+  const TflModel& d = model.desc();
+  const TflOperator& op = d.ops[oi];
+  HybridFcGeometry h;
+  const char* why = "";
+  if (!HybridFcArgs(d, op, &h, &why)) return Refused(op, why);
+  const FcGeometry& g = h.fc;
+  const TflTensor& w = d.tensors[g.filter];
+  const int units = g.units, depth = g.depth, rows = g.rows;
+  const int depth_pad = (depth + 15) / 16 * 16;
+  const size_t wbytes = static_cast<size_t>(units) * depth_pad;
+  const std::vector<float> bias = g.bias >= 0 ? FloatData(d, g.bias) : std::vector<float>();
+  std::shared_ptr<DeviceBlob> blob;
+  RETURN_STATUS_IF(ConstBlob(ckey + "/hybrid", wbytes + 8ull * units, sg, [&](uint8_t* host) {
+    int8_t* packed = reinterpret_cast<int8_t*>(host);
+    int32_t* sums = reinterpret_cast<int32_t*>(host + wbytes);
+    float* b = reinterpret_cast<float*>(host + wbytes + 4ull * units);
+    for (int u = 0; u < units; ++u) {
+      int32_t s = 0;
+      for (int k = 0; k < depth; ++k) {
+        const int8_t v = static_cast<int8_t>(w.data[static_cast<size_t>(u) * depth + k]);
+        packed[static_cast<size_t>(u) * depth_pad + k] = v;
+        s += v;
+      }
+      sums[u] = s;
+      b[u] = bias.empty() ? 0.f : bias[u];
+    }
+    return absl::OkStatus();
+  }, &blob));
+  // scratch: q [rows][depth] (padded to 16 bytes), scale [rows], offset [rows]
+  const size_t qbytes = (static_cast<size_t>(rows) * depth + 15) / 16 * 16;
+  auto scratch = std::make_shared<DeviceBlob>(ordinal_, qbytes + 8ull * rows);
+  if (!scratch->ok()) return absl::InternalError("HBM scratch allocation failed");
+  sg->consts.push_back(scratch);
+  char* sp = static_cast<char*>(scratch->ptr());
+  const bool cpu = device_flag_ == DeviceFlag::kCPU;
+  Launch Q;
+  Q.kind = Launch::kDynQuantRows;
+  Q.op_index = oi;
+  Q.dq = bh_dynquant_params{};
+  Q.dq.rows = rows; Q.dq.depth = depth; Q.dq.asymmetric = h.asymmetric ? 1 : 0;
+  Q.dq.input = static_cast<const float*>(in_ptr);
+  Q.dq.q = reinterpret_cast<int8_t*>(sp);
+  Q.dq.scale = reinterpret_cast<float*>(sp + qbytes);
+  Q.dq.offset = reinterpret_cast<int32_t*>(sp + qbytes + 4ull * rows);
+  Q.kernel = cpu ? "dynquant_rows_host" : bh_dynquant_rows_kernel(&Q.dq);
+  Q.alg_bytes = 5.0 * rows * depth + 8.0 * rows;
+  sg->launches.push_back(Q);
+  const char* base = static_cast<const char*>(blob->ptr());
+  bh_fc_hybrid_params& p = L->fch;
+  p = bh_fc_hybrid_params{};
+  p.rows = rows; p.depth = depth; p.depth_pad = depth_pad; p.units = units;
+  p.w_scale = h.w_scale;
+  FloatActRange(g.act, &p.act_min, &p.act_max);
+  p.q = Q.dq.q; p.in_scale = Q.dq.scale; p.in_offset = Q.dq.offset;
+  p.weights = reinterpret_cast<const int8_t*>(base);
+  p.w_row_sum = reinterpret_cast<const int32_t*>(base + wbytes);
+  p.bias = g.bias >= 0 ? reinterpret_cast<const float*>(base + wbytes + 4ull * units) : nullptr;
+  p.output = static_cast<float*>(out_ptr);
+  L->kind = Launch::kFcHybrid;
+  L->kernel = cpu ? "fc_hybrid_host" : bh_fc_hybrid_kernel(&p);
+  L->alg_ops = 2.0 * rows * units * depth;
+  L->alg_bytes = static_cast<double>(rows) * depth + 8.0 * rows + 4.0 * rows * units +
+                 static_cast<double>(units) * depth + 8.0 * units;
   return absl::OkStatus();
 }
 

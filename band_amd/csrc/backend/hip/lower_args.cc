@@ -156,6 +156,38 @@ bool FcArgs(const TflModel& m, const TflOperator& op, FcGeometry* g, const char*
   return true;
 }
 
+bool HybridFcArgs(const TflModel& m, const TflOperator& op, HybridFcGeometry* g, const char** why) {
+  auto no = [&](const char* w) {
+    if (why) *why = w;
+    return false;
+  };
+  if (op.builtin != kTflFullyConnected || !IsHybridWeightOp(m, op) || op.outputs.empty() || op.outputs[0] < 0)
+    return no("not a hybrid FULLY_CONNECTED");
+  const TflTensor& w = m.tensors[op.inputs[1]];
+  if (w.type != DataType::kInt8) return no("hybrid FULLY_CONNECTED: uint8 filter (int8 only)");
+  if (!w.is_const()) return no("hybrid FULLY_CONNECTED: filter must be a constant");
+  if (w.scale.size() > 1) return no("hybrid FULLY_CONNECTED: per-channel filter scales");
+  if (w.scale.size() != 1 || !(w.scale[0] > 0.f)) return no("hybrid FULLY_CONNECTED: filter needs one positive scale");
+  if (Zp(w) != 0 || w.zero_point.size() > 1) return no("hybrid FULLY_CONNECTED: non-zero filter zero point");
+  // FullyConnectedOptions: fused activation, weights_format, keep_num_dims, asymmetric_quantize_inputs
+  if (op.options.Int8(1, 0) != 0) return no("hybrid FULLY_CONNECTED: weights_format != 0");
+  if (op.inputs.size() > 2 && op.inputs[2] >= 0 && !ConstFloat(m, op.inputs[2]))
+    return no("hybrid FULLY_CONNECTED: bias must be a float constant");
+  if (m.tensors[op.outputs[0]].type != DataType::kFloat32) return no("hybrid FULLY_CONNECTED: float32 output expected");
+  HybridFcGeometry h{};
+  const char* r = "";
+  if (!FcArgs(m, op, &h.fc, &r)) return no(r);
+  if (h.fc.depth > 65535) return no("hybrid FULLY_CONNECTED: depth > 65,535 (the int32 dot)");
+  if (static_cast<long long>(h.fc.rows) * h.fc.depth > 0x7fffffffLL ||
+      static_cast<long long>(h.fc.rows) * h.fc.units > 0x7fffffffLL ||
+      static_cast<long long>(h.fc.units) * ((h.fc.depth + 15) / 16 * 16) > 0x7fffffffLL)
+    return no("hybrid FULLY_CONNECTED: a tensor of 2^31 or more elements");
+  h.w_scale = w.scale[0];
+  h.asymmetric = op.options.valid() && op.options.Bool(3, false);
+  if (g) *g = h;
+  return true;
+}
+
 bool PoolArgs(const TflModel& m, const TflOperator& op, PoolGeometry* g, const char** why) {
   auto no = [&](const char* w) {
     if (why) *why = w;

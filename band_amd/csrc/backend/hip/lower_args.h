@@ -65,6 +65,28 @@ struct FcGeometry {
 };
 bool FcArgs(const TflModel& m, const TflOperator& op, FcGeometry* g, const char** why = nullptr);
 
+// A float32 op whose filter is 8-bit: the converter's dynamic-range ("hybrid")
+// form.  FULLY_CONNECTED runs (HybridFcArgs); CONV_2D and DEPTHWISE_CONV_2D
+// are refused by name.
+inline bool IsHybridWeightOp(const TflModel& m, const TflOperator& op) {
+  return (op.builtin == kTflFullyConnected || op.builtin == kTflConv2D || op.builtin == kTflDepthwiseConv2D) &&
+         op.inputs.size() >= 2 && op.inputs[0] >= 0 && op.inputs[1] >= 0 &&
+         m.tensors[op.inputs[0]].type == DataType::kFloat32 && IsQ8(m.tensors[op.inputs[1]].type);
+}
+// Hybrid FULLY_CONNECTED: FcArgs' geometry, the filter's one scale and
+// FullyConnectedOptions.asymmetric_quantize_inputs (slot 3).  Refused with a
+// reason that names the op: per-channel filter scales, a non-zero filter zero
+// point, a uint8 or non-constant filter, weights_format != 0, a bias that is
+// not a float constant, a non-float32 output, depth > 65,535 (the int32 dot).
+// Every row is quantised alone, so a job-batch variant (more rows) computes
+// each job's own values.
+struct HybridFcGeometry {
+  FcGeometry fc;
+  float w_scale;
+  bool asymmetric;
+};
+bool HybridFcArgs(const TflModel& m, const TflOperator& op, HybridFcGeometry* g, const char** why = nullptr);
+
 // AVERAGE_POOL_2D / MAX_POOL_2D
 struct PoolGeometry {
   int batch, in_h, in_w, channels, out_h, out_w;

@@ -652,6 +652,8 @@ absl::Status HipModelExecutor::EnqueueLaunch(const Launch& l) {
     case Launch::kMeanRows: rc = bh_mean_rows(&l.mrows, stream_); break;
     case Launch::kLayerNorm: rc = bh_layernorm_i8(&l.ln, stream_); break;
     case Launch::kAttention: rc = bh_attention_i8(&l.attn, stream_); break;
+    case Launch::kDynQuantRows: rc = bh_dynquant_rows(&l.dq, stream_); break;
+    case Launch::kFcHybrid: rc = bh_fc_hybrid(&l.fch, stream_); break;
     case Launch::kMean: {
       bh_mean_params q{};
       q.outer = l.mean.outer;
@@ -857,6 +859,8 @@ absl::Status HipModelExecutor::ExecuteOnHost(PreparedSubgraph* sg) {
       case Launch::kReindex: CpuReindex(l.reindex); break;
       case Launch::kBatchMatMul: CpuBatchMatMul(l.bmm, pool); break;
       case Launch::kBatchMatMulF32: CpuBatchMatMulF32(l.bmm, pool); break;
+      case Launch::kDynQuantRows: CpuDynQuantRows(l.dq, pool); break;
+      case Launch::kFcHybrid: CpuFcHybrid(l.fch, pool); break;
       default: return absl::InternalError(std::string("no host implementation of ") + l.kernel);
     }
   }

@@ -57,7 +57,9 @@ struct Launch {
     kBatchMatMul,     // BATCH_MATMUL int8 (BatchMatMulArgs -> `bmm`; never chained / grouped / blocked, no epilogue folds)
     kBatchMatMulF32,  // BATCH_MATMUL float32
     kLayerNorm,       // the ten ops of an int8 LayerNorm as one launch (FuseLayerNorm; kGPU)
-    kAttention        // BATCH_MATMUL -> SOFTMAX -> BATCH_MATMUL (int8) as one launch (FuseAttention; kGPU, opt-in)
+    kAttention,       // BATCH_MATMUL -> SOFTMAX -> BATCH_MATMUL (int8) as one launch (FuseAttention; kGPU, opt-in)
+    kDynQuantRows,    // hybrid FULLY_CONNECTED, first launch: the input's rows quantised into the subgraph's scratch (`dq`)
+    kFcHybrid         // hybrid FULLY_CONNECTED, second launch: int8 product, float epilogue (`fch`)
   } kind;
   int op_index = -1;
   int out_tensor = -1;  // tensor this launch materialises (after epilogue fusions)
@@ -96,6 +98,8 @@ struct Launch {
   bh_reindex_params reindex{};
   bh_batch_matmul_params bmm{};
   bh_attention_params attn{};
+  bh_dynquant_params dq{};
+  bh_fc_hybrid_params fch{};
   const void* table = nullptr;  // kLutU8 / kLutF32: 256-entry device table
   long count = 0;               // kLut* / kQuantF32: elements
   float q_scale = 0.f;          // kQuantF32
@@ -269,6 +273,10 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
                               const std::string& ckey, PreparedSubgraph* sg, Launch* l);
   absl::Status LowerFc(const HipModel& model, int op_index, void* in_ptr, void* out_ptr, const std::string& ckey,
                        PreparedSubgraph* sg, Launch* l);
+  // hybrid FULLY_CONNECTED (HybridFcArgs): a kDynQuantRows launch into a
+  // scratch owned by sg, then *l as the kFcHybrid launch
+  absl::Status LowerFcHybrid(const HipModel& model, int op_index, void* in_ptr, void* out_ptr, const std::string& ckey,
+                             PreparedSubgraph* sg, Launch* l);
   absl::Status LowerEltwise(const HipModel& model, int op_index, void* in_ptr, void* out_ptr, PreparedSubgraph* sg,
                             Launch* l);
   absl::Status LowerPool(const HipModel& model, int op_index, void* in_ptr, void* out_ptr, Launch* l);

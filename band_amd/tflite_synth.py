@@ -855,9 +855,15 @@ class FGraph(_ReindexOps):
     """Float graph builder with QGraph's method names: a TFLite fp16 model
     (post-training float16 quantization) - float32 activations, every
     constant stored as float16 behind a DEQUANTIZE op, float32 compute.
-    Weights are He-initialised so activations stay O(1) through ReLU6."""
+    Weights are He-initialised so activations stay O(1) through ReLU6.
 
-    def __init__(self, seed=0, name="model"):
+    hybrid = "symmetric" | "asymmetric" builds the converter's dynamic-range
+    form instead: every constant a plain float32 tensor (no DEQUANTIZE), every
+    FULLY_CONNECTED with int8 weights (fully_connected's `hybrid`)."""
+
+    def __init__(self, seed=0, name="model", hybrid=None):
+        assert hybrid in (None, "symmetric", "asymmetric"), hybrid
+        self.hybrid = hybrid
         self.dtype = np.dtype(np.float16)
         self.rng = np.random.default_rng(seed)
         self.mb = ModelBuilder(name)
@@ -874,8 +880,10 @@ class FGraph(_ReindexOps):
         return t
 
     def _const(self, values, kind):
-        """float16 constant + DEQUANTIZE -> float32 tensor"""
+        """float16 constant + DEQUANTIZE -> float32 tensor (a dynamic-range graph: a float32 constant)"""
         v = np.asarray(values, np.float32)
+        if self.hybrid:
+            return self.mb.tensor(self._name(kind), list(v.shape), np.float32, data=v)
         c = self.mb.tensor(self._name(kind + "_fp16"), list(v.shape), np.float16, data=v.astype(np.float16))
         y = self.mb.tensor(self._name(kind), list(v.shape), np.float32)
         self.mb.op("DEQUANTIZE", [c], [y], OPT["DequantizeOptions"], Table())
@@ -945,17 +953,32 @@ class FGraph(_ReindexOps):
         self.mb.op("RESHAPE", [x, st], [y], OPT["ReshapeOptions"], Table().set(0, "o", Vec("i", list(shape))))
         return y
 
-    def fully_connected(self, x, units, act="NONE", keep_num_dims=False, gain=1.0):
-        """`gain` scales the weights' standard deviation (an attention block's 1 / sqrt(D) folded into Q)"""
+    def fully_connected(self, x, units, act="NONE", keep_num_dims=False, gain=1.0, hybrid=None):
+        """`gain` scales the weights' standard deviation (an attention block's 1 / sqrt(D) folded into Q).
+        hybrid = "symmetric" | "asymmetric" (default: the graph's): int8 weights with ws = max|w| / 127
+        and zero point 0, a plain float32 bias constant, asymmetric_quantize_inputs (slot 3) when asymmetric"""
+        hybrid = hybrid or self.hybrid
+        assert hybrid in (None, "symmetric", "asymmetric"), hybrid
         shp = self.meta[x][0]
         depth = shp[-1]
         rows = int(np.prod(shp)) // depth
-        wt = self._const(self.rng.normal(0, gain * np.sqrt(1.0 / depth), (units, depth)), "fc_weights")
-        bt = self._const(self.rng.normal(0, 0.05, units), "fc_bias")
+        w = self.rng.normal(0, gain * np.sqrt(1.0 / depth), (units, depth))
+        b = self.rng.normal(0, 0.05, units)
+        if hybrid:
+            w = w.astype(np.float32)
+            ws = float(np.float32(np.abs(w).max()) / np.float32(127.0)) or 1.0
+            wq = np.clip(np.round(w / np.float32(ws)), -127, 127).astype(np.int8)
+            wt = self.mb.tensor(self._name("fc_weights"), [units, depth], np.int8, scale=[ws], zero_point=[0], data=wq)
+            bt = self.mb.tensor(self._name("fc_bias"), [units], np.float32, data=b.astype(np.float32))
+        else:
+            wt = self._const(w, "fc_weights")
+            bt = self._const(b, "fc_bias")
         y = self._act(list(shp[:-1]) + [units] if keep_num_dims else [rows, units])
         opt = act_options(act)
         if keep_num_dims:
             opt.set(2, "b", 1)
+        if hybrid == "asymmetric":
+            opt.set(3, "b", 1)
         self.mb.op("FULLY_CONNECTED", [x, wt, bt], [y], OPT["FullyConnectedOptions"], opt)
         return y
 
@@ -1177,14 +1200,16 @@ def _attention(g, x, heads, residual=None):
     return g.add(y, x if residual is None else residual)
 
 
-def attention_block(dtype=np.int8, seed=6, tokens=196, dim=192, heads=3, batch=1):
+def attention_block(dtype=np.int8, seed=6, tokens=196, dim=192, heads=3, batch=1, hybrid=None):
     """One self-attention block on [batch, tokens, dim]: three FULLY_CONNECTED
     (keep_num_dims), RESHAPE / TRANSPOSE to [batch, heads, tokens, dim / heads],
     BATCH_MATMUL(adj_y) -> SOFTMAX -> BATCH_MATMUL, TRANSPOSE / RESHAPE back,
     FULLY_CONNECTED, ADD with the input.  dtype float32 (or float16) builds the
-    fp16-constant float model.  No LayerNorm: encoder_block has it."""
+    fp16-constant float model, or with `hybrid` ("symmetric" | "asymmetric") the
+    dynamic-range one (FGraph).  No LayerNorm: encoder_block has it."""
+    assert hybrid is None or np.dtype(dtype) == np.dtype(np.float32), "hybrid is a form of the float32 model"
     if np.dtype(dtype) in (np.dtype(np.float32), np.dtype(np.float16)):
-        g = FGraph(seed, "attention_block_f32")
+        g = FGraph(seed, "attention_block_f32" + ("_hybrid" if hybrid else ""), hybrid=hybrid)
     else:
         g = QGraph(dtype, seed, "attention_block_%s" % np.dtype(dtype).name)
     x = g.input([batch, tokens, dim], scale=0.05)
@@ -1201,14 +1226,16 @@ def _encoder(g, x, heads, hidden, layer_norm=True, mlp=True):
     return y
 
 
-def encoder_block(dtype=np.int8, seed=8, tokens=196, dim=192, heads=3, hidden=768, batch=1):
+def encoder_block(dtype=np.int8, seed=8, tokens=196, dim=192, heads=3, hidden=768, batch=1, hybrid=None):
     """One pre-norm transformer encoder block on [batch, tokens, dim]:
     LayerNorm (the converter's ten ops, see QGraph.layer_norm) -> attention
     (attention_block's) -> LayerNorm -> MLP (FULLY_CONNECTED to `hidden`, GELU,
     FULLY_CONNECTED back), with the residual ADDs.  dtype float32 (or float16)
-    builds the fp16-constant float model."""
+    builds the fp16-constant float model, or with `hybrid` ("symmetric" |
+    "asymmetric") the dynamic-range one (FGraph)."""
+    assert hybrid is None or np.dtype(dtype) == np.dtype(np.float32), "hybrid is a form of the float32 model"
     if np.dtype(dtype) in (np.dtype(np.float32), np.dtype(np.float16)):
-        g = FGraph(seed, "encoder_block_f32")
+        g = FGraph(seed, "encoder_block_f32" + ("_hybrid" if hybrid else ""), hybrid=hybrid)
     else:
         g = QGraph(dtype, seed, "encoder_block_%s" % np.dtype(dtype).name)
     x = g.input([batch, tokens, dim], scale=0.05)
@@ -1216,12 +1243,19 @@ def encoder_block(dtype=np.int8, seed=8, tokens=196, dim=192, heads=3, hidden=76
     return g.build()
 
 
-def vit_tiny(dtype=np.int8, seed=7, size=224, dim=192, heads=3, blocks=2, batch=1, layer_norm=False, mlp=False):
+def vit_tiny(dtype=np.int8, seed=7, size=224, dim=192, heads=3, blocks=2, batch=1, layer_norm=False, mlp=False,
+             hybrid=None):
     """ViT-Tiny's front: a 16 x 16 stride-16 patch CONV_2D, RESHAPE to tokens
     [batch, (size / 16)^2, dim] and `blocks` attention blocks; with layer_norm
     / mlp, pre-norm encoder blocks (encoder_block's, hidden = 4 dim).  No
-    class token and no position embedding."""
-    g = QGraph(dtype, seed, "vit_tiny_%s" % np.dtype(dtype).name)
+    class token and no position embedding.  dtype float32 with `hybrid`
+    ("symmetric" | "asymmetric") builds the dynamic-range float model: a float32
+    patch conv, hybrid FULLY_CONNECTEDs."""
+    if hybrid:
+        assert np.dtype(dtype) == np.dtype(np.float32), "hybrid is a form of the float32 model"
+        g = FGraph(seed, "vit_tiny_f32_hybrid", hybrid=hybrid)
+    else:
+        g = QGraph(dtype, seed, "vit_tiny_%s" % np.dtype(dtype).name)
     x = g.input([batch, size, size, 3], scale=0.05)
     y = g.conv(x, dim, k=16, stride=16, act="NONE", padding="VALID")
     n = (size // 16) ** 2

@@ -202,6 +202,12 @@ int bhx_cpu_batch_matmul(const void* batch_matmul_params, int is_float32);
 int bhx_cpu_mean_rows(const void* mean_rows_params);
 int bhx_cpu_eltwise(const void* eltwise_params);
 int bhx_cpu_unary_f32(int kind, const float* in, float* out, long n);
+/* CpuDynQuantRows / CpuFcHybrid, the host twins of bh_dynquant_rows and
+ * bh_fc_hybrid (hybrid FULLY_CONNECTED) over host pointers: a
+ * bh_dynquant_params / bh_fc_hybrid_params.  Refuse what the launchers'
+ * checks refuse. */
+int bhx_cpu_dynquant_rows(const void* dynquant_params);
+int bhx_cpu_fc_hybrid(const void* fc_hybrid_params);
 /* The 256-entry tables the 8-bit RSQRT (int8) and GELU lower to, indexed by
  * the input byte, and squared_difference.cc's multipliers as {m1, s1, m2, s2,
  * mo, so, left_shift}; non-zero (bhx_last_error names the reason) for scales

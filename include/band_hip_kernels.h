@@ -41,6 +41,8 @@
  *                        DEPTH_TO_SPACE (one launch per output; numpy's indexing semantics)
  *   bh_batch_matmul_i8 / bh_batch_matmul_f32 <- BATCH_MATMUL int8 / float32 (the arithmetic of
  *                        reference_integer_ops::FullyConnected without a bias, per batch slice)
+ *   bh_dynquant_rows + bh_fc_hybrid <- FULLY_CONNECTED float32 with int8 weights (fully_connected.cc
+ *                        EvalHybrid: each input row quantised at run time, int8 product, float epilogue)
  *   bh_detection_postprocess <- TFLite_Detection_PostProcess (custom; detection_postprocess.cc,
  *                        fast NMS, one class per detection)
  *   (HARD_SWISH 8-bit runs as a bh_lut_u8 table of reference_ops::HardSwish)
@@ -945,6 +947,69 @@ const char* bh_attention_i8_kernel(const bh_attention_params* p);
 int bh_attention_i8_check(const bh_attention_params* p);
 /* bytes of LDS a launch of these extents takes (0 for refused parameters) */
 size_t bh_attention_i8_lds_bytes(const bh_attention_params* p);
+
+/* Dynamic-range ("hybrid") FULLY_CONNECTED: float32 input, constant int8
+ * weights [units][depth] with one scale and zero point 0, float32 output.
+ * Restated from memory of TFLite's fully_connected.cc EvalHybrid and
+ * tensor_utils::{Symmetric,Asymmetric}QuantizeFloats (DESIGN 4 holds the rule
+ * and what is pinned).  Every float operation is one IEEE float32 operation
+ * (float64 where marked), no contraction; round is half away from zero.
+ *
+ * bh_dynquant_rows (dynquant_rows_kernel, one wave per row) quantises each
+ * row x of input [rows][depth] on its own:
+ *   symmetric   r = max |x|; r == 0: q = 0, s = 1; else s = r / 127,
+ *               inv = 127 / r, q = clamp(round(x inv), -127, 127); off = 0.
+ *   asymmetric  rmin = min(0, min x), rmax = max(0, max x); equal: q = 0,
+ *               s = 1, off = 0; else in float64 scale = (rmax - rmin) / 255
+ *               (the difference in float32), off = the zero point nudged from
+ *               the end with the smaller error, clamped to [-128, 127];
+ *               s = (float)scale, inv = 1 / s,
+ *               q = clamp(round((float)off + x inv), -128, 127).
+ * into q [rows][depth], scale [rows], offset [rows].  Any depth.
+ *
+ * bh_fc_hybrid (fc_hybrid_kernel, v_mfma_i32_16x16x64_i8):
+ *   dot = sum_k w[u][k] q[k] - off * w_row_sum[u]           (int32, exact)
+ *   y = bias[u] + (float)dot * (s * w_scale), clamped to [act_min, act_max]
+ * (a missing bias adds 0).  weights are packed [units][depth_pad] with
+ * depth_pad a multiple of 16 and the padding zero, 16-byte aligned;
+ * w_row_sum [units] = sum_k w[u][k], built once by the caller.  Rows <= 16
+ * (the classifier head) spread a workgroup's 4 waves over unit tiles or over
+ * K slices whose partial sums are added as integers.
+ * Refused (BH_EINVAL, bh_last_error names the launcher and the reason): null
+ * pointers, non-positive extents, depth > 65,535 (bh_fc_hybrid: the int32
+ * dot), 2^31 or more elements in a tensor, a bad depth_pad, misaligned
+ * operands.  No scratch, no atomics. */
+typedef struct bh_dynquant_params {
+  long rows;
+  int depth;
+  int asymmetric;
+  const float* input;   /* [rows][depth] */
+  int8_t* q;            /* [rows][depth] */
+  float* scale;         /* [rows] */
+  int32_t* offset;      /* [rows] */
+} bh_dynquant_params;
+int bh_dynquant_rows(const bh_dynquant_params* p, bh_stream_t s);
+/* "dynquant_rows_kernel", or "" for parameters bh_dynquant_rows refuses; static storage */
+const char* bh_dynquant_rows_kernel(const bh_dynquant_params* p);
+/* the launcher's parameter check alone; pure host */
+int bh_dynquant_rows_check(const bh_dynquant_params* p);
+
+typedef struct bh_fc_hybrid_params {
+  int rows, depth, depth_pad, units;
+  float w_scale, act_min, act_max;
+  const int8_t* q;            /* [rows][depth] */
+  const float* in_scale;      /* [rows] */
+  const int32_t* in_offset;   /* [rows] */
+  const int8_t* weights;      /* [units][depth_pad] */
+  const int32_t* w_row_sum;   /* [units] */
+  const float* bias;          /* [units] or NULL */
+  float* output;              /* [rows][units] */
+} bh_fc_hybrid_params;
+int bh_fc_hybrid(const bh_fc_hybrid_params* p, bh_stream_t s);
+/* "fc_hybrid_kernel", or "" for parameters bh_fc_hybrid refuses; static storage */
+const char* bh_fc_hybrid_kernel(const bh_fc_hybrid_params* p);
+/* the launcher's parameter check alone; pure host */
+int bh_fc_hybrid_check(const bh_fc_hybrid_params* p);
 
 /* TRANSPOSE_CONV support: U[y*sh][x*sw][:] = in[y][x][:], every other
  * position of U (out_h x out_w = (in-1)*stride+1) holds `fill` (the input
