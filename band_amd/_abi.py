@@ -194,6 +194,25 @@ class FcHybridParams(ctypes.Structure):
         (n, c_void_p) for n in ("q", "in_scale", "in_offset", "weights", "w_row_sum", "bias", "output")]
 
 
+class DynQuantItemsParams(ctypes.Structure):
+    """bh_dynquant_items_params: the per-item quantisation of a hybrid CONV_2D / DEPTHWISE_CONV_2D's input"""
+    _fields_ = [(n, c_int) for n in ("items", "item_size", "asymmetric", "form")] + [
+        (n, c_void_p) for n in ("input", "q", "scale", "offset", "pairs")]
+
+
+DYNQUANT_CHUNK = 4096            # BH_DYNQUANT_CHUNK
+DYNQUANT_ONE_LAUNCH_MAX = 16384  # BH_DYNQUANT_ONE_LAUNCH_MAX
+
+
+class ConvHybridParams(ctypes.Structure):
+    """bh_conv_hybrid_params: int8 items x int8 filter, float32 epilogue (conv and depthwise)"""
+    _fields_ = [(n, c_int) for n in ("batch", "in_h", "in_w", "in_c", "out_h", "out_w", "out_c", "k_h", "k_w", "stride_h",
+                                     "stride_w", "dil_h", "dil_w", "pad_h", "pad_w", "k_pad", "depth_multiplier",
+                                     "per_channel")] + [
+        (n, ctypes.c_float) for n in ("act_min", "act_max")] + [
+        (n, c_void_p) for n in ("q", "in_scale", "in_offset", "weights", "w_row_sum", "w_scale", "bias", "output")]
+
+
 class ResizeBilinearU8Params(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("batch", "in_h", "in_w", "channels", "out_h", "out_w")] + [
         (n, c_void_p) for n in ("y_idx", "x_idx", "y_frac", "x_frac", "input", "output")]
@@ -336,6 +355,15 @@ KERNEL_SYMBOLS = {
     "bh_fc_hybrid": (c_int, [ctypes.POINTER(FcHybridParams), c_void_p]),
     "bh_fc_hybrid_kernel": (ctypes.c_char_p, [ctypes.POINTER(FcHybridParams)]),
     "bh_fc_hybrid_check": (c_int, [ctypes.POINTER(FcHybridParams)]),
+    "bh_dynquant_items": (c_int, [ctypes.POINTER(DynQuantItemsParams), c_void_p]),
+    "bh_dynquant_items_kernel": (ctypes.c_char_p, [ctypes.POINTER(DynQuantItemsParams)]),
+    "bh_dynquant_items_check": (c_int, [ctypes.POINTER(DynQuantItemsParams)]),
+    "bh_conv2d_hybrid": (c_int, [ctypes.POINTER(ConvHybridParams), c_void_p]),
+    "bh_conv2d_hybrid_kernel": (ctypes.c_char_p, [ctypes.POINTER(ConvHybridParams)]),
+    "bh_conv2d_hybrid_check": (c_int, [ctypes.POINTER(ConvHybridParams)]),
+    "bh_dwconv2d_hybrid": (c_int, [ctypes.POINTER(ConvHybridParams), c_void_p]),
+    "bh_dwconv2d_hybrid_kernel": (ctypes.c_char_p, [ctypes.POINTER(ConvHybridParams)]),
+    "bh_dwconv2d_hybrid_check": (c_int, [ctypes.POINTER(ConvHybridParams)]),
     "bh_softmax_i8": (c_int, [ctypes.POINTER(SoftmaxParams), c_void_p]),
     "bh_attention_i8": (c_int, [ctypes.POINTER(AttentionParams), c_void_p]),
     "bh_attention_i8_kernel": (ctypes.c_char_p, [ctypes.POINTER(AttentionParams)]),

@@ -87,6 +87,9 @@ _abi.BACKEND_SYMBOLS.update({
     "bhx_cpu_mean_rows": (c_int, [ctypes.POINTER(_abi.MeanRowsParams)]),
     "bhx_cpu_dynquant_rows": (c_int, [ctypes.POINTER(_abi.DynQuantParams)]),
     "bhx_cpu_fc_hybrid": (c_int, [ctypes.POINTER(_abi.FcHybridParams)]),
+    "bhx_cpu_dynquant_items": (c_int, [ctypes.POINTER(_abi.DynQuantItemsParams)]),
+    "bhx_cpu_conv_hybrid": (c_int, [ctypes.POINTER(_abi.ConvHybridParams)]),
+    "bhx_cpu_dwconv_hybrid": (c_int, [ctypes.POINTER(_abi.ConvHybridParams)]),
     "bhx_cpu_eltwise": (c_int, [ctypes.POINTER(_abi.EltwiseParams)]),
     "bhx_cpu_unary_f32": (c_int, [c_int, c_void_p, c_void_p, ctypes.c_long]),
     "bhx_rsqrt_table": (c_int, [ctypes.c_float, c_int, ctypes.c_float, c_int, c_void_p]),

@@ -512,6 +512,30 @@ int bhx_cpu_fc_hybrid(const void* fc_hybrid_params) {
   return 0;
 }
 
+int bhx_cpu_dynquant_items(const void* dynquant_items_params) {
+  const auto* p = static_cast<const bh_dynquant_items_params*>(dynquant_items_params);
+  if (bh_dynquant_items_check(p) != 0) return Fail((std::string("CpuDynQuantItems: ") + bh_last_error()).c_str());
+  band::hip::CpuPool pool(1);
+  band::hip::CpuDynQuantItems(*p, pool);
+  return 0;
+}
+
+int bhx_cpu_conv_hybrid(const void* conv_hybrid_params) {
+  const auto* p = static_cast<const bh_conv_hybrid_params*>(conv_hybrid_params);
+  if (bh_conv2d_hybrid_check(p) != 0) return Fail((std::string("CpuConvHybrid: ") + bh_last_error()).c_str());
+  band::hip::CpuPool pool(1);
+  band::hip::CpuConvHybrid(*p, pool);
+  return 0;
+}
+
+int bhx_cpu_dwconv_hybrid(const void* conv_hybrid_params) {
+  const auto* p = static_cast<const bh_conv_hybrid_params*>(conv_hybrid_params);
+  if (bh_dwconv2d_hybrid_check(p) != 0) return Fail((std::string("CpuDwConvHybrid: ") + bh_last_error()).c_str());
+  band::hip::CpuPool pool(1);
+  band::hip::CpuDwConvHybrid(*p, pool);
+  return 0;
+}
+
 int bhx_cpu_eltwise(const void* eltwise_params) {
   const auto* p = static_cast<const bh_eltwise_params*>(eltwise_params);
   if (!p || !p->a || !p->b || !p->out || p->kind < BH_ELT_ADD || p->kind > BH_ELT_SQDIFF)

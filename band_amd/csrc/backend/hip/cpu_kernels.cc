@@ -1065,5 +1065,88 @@ void CpuFcHybrid(const bh_fc_hybrid_params& p, CpuPool& pool) {
   });
 }
 
+// ---- hybrid CONV_2D / DEPTHWISE_CONV_2D (band_hip_kernels.h holds the rule) --
+// The float steps go through volatile so that each rounds once whatever the
+// compiler would like to do with them.
+
+void CpuDynQuantItems(const bh_dynquant_items_params& p, CpuPool& pool) {
+  bh_dynquant_params r{};
+  r.rows = p.items;
+  r.depth = p.item_size;
+  r.asymmetric = p.asymmetric;
+  r.input = p.input;
+  r.q = p.q;
+  r.scale = p.scale;
+  r.offset = p.offset;
+  CpuDynQuantRows(r, pool);
+}
+
+namespace {
+
+// the three epilogues, one float32 operation at a time
+inline float HybridEpilogue(int form, int32_t acc, float ws, float s, float bias, float lo, float hi) {
+  volatile float y;
+  if (form == 0) {  // CONV_2D, one filter scale
+    volatile float sc = s * ws;
+    volatile float prod = static_cast<float>(acc) * sc;
+    y = bias + prod;
+  } else if (form == 1) {  // CONV_2D, out_c scales
+    volatile float t1 = static_cast<float>(acc) * ws;
+    volatile float t2 = t1 * s;
+    y = t2 + bias;
+  } else {  // DEPTHWISE_CONV_2D
+    volatile float sc = ws * s;
+    volatile float prod = static_cast<float>(acc) * sc;
+    y = prod + bias;
+  }
+  const float v = y;
+  return std::min(std::max(v, lo), hi);
+}
+
+void HybridConvRows(const bh_conv_hybrid_params& p, bool dw, long r0, long r1) {
+  const long per_item = static_cast<long>(p.out_h) * p.out_w;
+  for (long m = r0; m < r1; ++m) {
+    const int b = static_cast<int>(m / per_item);
+    const int oy = static_cast<int>((m % per_item) / p.out_w), ox = static_cast<int>(m % p.out_w);
+    const int8_t* img = p.q + static_cast<long>(b) * p.in_h * p.in_w * p.in_c;
+    const int32_t off = p.in_offset[b];
+    const float s = p.in_scale[b];
+    for (int c = 0; c < p.out_c; ++c) {
+      int64_t acc = 0;
+      for (int ky = 0; ky < p.k_h; ++ky) {
+        const int iy = oy * p.stride_h - p.pad_h + ky * p.dil_h;
+        if (iy < 0 || iy >= p.in_h) continue;
+        for (int kx = 0; kx < p.k_w; ++kx) {
+          const int ix = ox * p.stride_w - p.pad_w + kx * p.dil_w;
+          if (ix < 0 || ix >= p.in_w) continue;
+          const int8_t* px = img + (static_cast<long>(iy) * p.in_w + ix) * p.in_c;
+          if (dw) {
+            const int32_t w = p.weights[static_cast<long>(ky * p.k_w + kx) * p.out_c + c];
+            acc += static_cast<int64_t>(w) * (px[c / p.depth_multiplier] - off);
+          } else {
+            const int8_t* wp = p.weights + static_cast<long>(c) * p.k_pad + static_cast<long>(ky * p.k_w + kx) * p.in_c;
+            for (int ci = 0; ci < p.in_c; ++ci) acc += static_cast<int64_t>(wp[ci]) * (px[ci] - off);
+          }
+        }
+      }
+      const int form = dw ? 2 : (p.per_channel ? 1 : 0);
+      p.output[m * p.out_c + c] = HybridEpilogue(form, static_cast<int32_t>(acc), p.w_scale[c], s,
+                                                 p.bias ? p.bias[c] : 0.f, p.act_min, p.act_max);
+    }
+  }
+}
+
+}  // namespace
+
+void CpuConvHybrid(const bh_conv_hybrid_params& p, CpuPool& pool) {
+  pool.ParallelFor(static_cast<long>(p.batch) * p.out_h * p.out_w,
+                   [&](long r0, long r1) { HybridConvRows(p, false, r0, r1); });
+}
+
+void CpuDwConvHybrid(const bh_conv_hybrid_params& p, CpuPool& pool) {
+  pool.ParallelFor(static_cast<long>(p.batch) * p.out_h * p.out_w,
+                   [&](long r0, long r1) { HybridConvRows(p, true, r0, r1); });
+}
+
 }  // namespace hip
 }  // namespace band

@@ -135,5 +135,14 @@ void CpuBatchMatMulF32(const bh_batch_matmul_params& p, CpuPool& pool);
 void CpuDynQuantRows(const bh_dynquant_params& p, CpuPool& pool);
 void CpuFcHybrid(const bh_fc_hybrid_params& p, CpuPool& pool);
 
+// Hybrid CONV_2D / DEPTHWISE_CONV_2D: the host twins of bh_dynquant_items,
+// bh_conv2d_hybrid and bh_dwconv2d_hybrid with the rule of band_hip_kernels.h.
+// CpuDynQuantItems is CpuDynQuantRows with the item as the row (`pairs` and
+// `form` are not read); the products sum w (q - off) over the in-bounds taps
+// and read neither k_pad's padding nor w_row_sum.  Validated by the caller.
+void CpuDynQuantItems(const bh_dynquant_items_params& p, CpuPool& pool);
+void CpuConvHybrid(const bh_conv_hybrid_params& p, CpuPool& pool);
+void CpuDwConvHybrid(const bh_conv_hybrid_params& p, CpuPool& pool);
+
 }  // namespace hip
 }  // namespace band

@@ -48,6 +48,8 @@ inline const char* CoalesceIo() { return Str("BAND_HIP_COALESCE_IO"); }
 inline bool CoalesceFailBuild() { return Int("BAND_HIP_COALESCE_FAIL_BUILD", 0, INT_MIN) != 0; }
 // 1: TFLite_Detection_PostProcess on the device
 inline bool GpuDetection() { return Flag("BAND_HIP_GPU_DETECTION", false); }
+// 1: hybrid CONV_2D / DEPTHWISE_CONV_2D (float32 input, int8 filter) run, on both workers
+inline bool HybridConv() { return Flag("BAND_HIP_HYBRID_CONV", false); }
 // 0: job-batch variants capture their graphs lazily
 inline bool Precapture() { return Flag("BAND_HIP_PRECAPTURE", true); }
 // 1: BATCH_MATMUL -> SOFTMAX -> BATCH_MATMUL (int8) as one attention_i8_kernel launch on kGPU executors

@@ -126,7 +126,8 @@ inline bool IsFloatOp(const TflModel& m, const TflOperator& op) {
   }
 }
 // the float32 op set (fp16-weight models)
-inline bool FloatSupports(const TflModel& m, const TflOperator& op, std::string* why) {
+// hybrid_conv: the executor was built with BAND_HIP_HYBRID_CONV=1
+inline bool FloatSupports(const TflModel& m, const TflOperator& op, std::string* why, bool hybrid_conv = false) {
   auto no = [&](const char* w) {
     if (why) *why = w;
     return false;
@@ -136,8 +137,11 @@ inline bool FloatSupports(const TflModel& m, const TflOperator& op, std::string*
   if (op.builtin == kTflDequantize)
     return in.is_const() && out.type == DataType::kFloat32 ? true : no("float16 DEQUANTIZE of a constant only");
   if (IsHybridWeightOp(m, op)) {
-    if (op.builtin != kTflFullyConnected) return no("hybrid CONV_2D / DEPTHWISE_CONV_2D (float32 input, int8 filter)");
     const char* w = "";
+    if (op.builtin != kTflFullyConnected) {
+      if (!hybrid_conv) return no("hybrid CONV_2D / DEPTHWISE_CONV_2D (float32 input, int8 filter)");
+      return HybridConvArgs(m, op, nullptr, &w) ? true : no(w);
+    }
     return HybridFcArgs(m, op, nullptr, &w) ? true : no(w);
   }
   if (out.type != DataType::kFloat32) return no("float32 output expected");

@@ -60,6 +60,7 @@ absl::Status HipModelExecutor::PrepareJobBatches(interface::IModel* model, const
     v.exec->block_sync_ = block_sync_;
     v.exec->sync_mode_ = sync_mode_;
     v.exec->gpu_detection_ = gpu_detection_;
+    v.exec->hybrid_conv_ = hybrid_conv_;
     v.exec->fused_attention_ = fused_attention_;
     if (device_flag_ == DeviceFlag::kCPU) {  // one host pool per worker
       if (!cpu_pool_)

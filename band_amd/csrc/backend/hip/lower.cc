@@ -575,6 +575,7 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
     }
     case kTflConv2D:
     case kTflDepthwiseConv2D: {
+      if (hybrid_conv_ && IsHybridConvOp(d, op)) return LowerConvHybrid(model, oi, in_ptr, out_ptr, ckey, sg, L);
       const bool dw = op.builtin == kTflDepthwiseConv2D;
       ConvGeometry g;
       if (!ConvArgs(d, op, &g, &why)) return Refused(op, why);
@@ -1022,6 +1023,102 @@ absl::Status HipModelExecutor::LowerFcHybrid(const HipModel& model, int oi, void
   return absl::OkStatus();
 }
 
+// Hybrid CONV_2D / DEPTHWISE_CONV_2D (float32 input, int8 filter; executors
+// built with BAND_HIP_HYBRID_CONV=1).  The input's batch items are quantised
+// into a scratch owned by this subgraph (q, the chunk pairs of the two-launch
+// form, then one scale and one offset per item; a job-batch variant has more
+// items and so a larger scratch), then the int8 product with the float
+// epilogue.  One constant blob per op, shared across executors: the filter
+// (CONV_2D: packed [out_c][k_pad], K padded to 16 by zeros; depthwise: as the
+// flatbuffer holds it), the row sums over all taps, the scales expanded to
+// [out_c] and the bias.
+absl::Status HipModelExecutor::LowerConvHybrid(const HipModel& model, int oi, void* in_ptr, void* out_ptr,
+                                               const std::string& ckey, PreparedSubgraph* sg, Launch* L) {
+  const TflModel& d = model.desc();
+  const TflOperator& op = d.ops[oi];
+  HybridConvGeometry h;
+  const char* why = "";
+  if (!HybridConvArgs(d, op, &h, &why)) return Refused(op, why);
+  const ConvGeometry& g = h.conv;
+  const TflTensor& w = d.tensors[g.filter];
+  const bool dw = h.depthwise;
+  const int oc = g.out_c;
+  const int K = g.k_h * g.k_w * (dw ? 1 : g.in_c);
+  const int k_pad = (K + 15) / 16 * 16;
+  const size_t wbytes = dw ? (static_cast<size_t>(K) * oc + 15) / 16 * 16 : static_cast<size_t>(oc) * k_pad;
+  const std::vector<float> bias = g.bias >= 0 ? FloatData(d, g.bias) : std::vector<float>();
+  std::shared_ptr<DeviceBlob> blob;
+  RETURN_STATUS_IF(ConstBlob(ckey + "/hybrid", wbytes + 12ull * oc, sg, [&](uint8_t* host) {
+    int8_t* packed = reinterpret_cast<int8_t*>(host);
+    int32_t* sums = reinterpret_cast<int32_t*>(host + wbytes);
+    float* scales = reinterpret_cast<float*>(host + wbytes + 4ull * oc);
+    float* b = reinterpret_cast<float*>(host + wbytes + 8ull * oc);
+    std::memset(host, 0, wbytes);
+    for (int c = 0; c < oc; ++c) {
+      int32_t s = 0;
+      for (int k = 0; k < K; ++k) {
+        // OHWI: [c][k]; depthwise [1][kh][kw][oc]: [k][c]
+        const size_t at = dw ? static_cast<size_t>(k) * oc + c : static_cast<size_t>(c) * K + k;
+        const int8_t v = static_cast<int8_t>(w.data[at]);
+        packed[dw ? at : static_cast<size_t>(c) * k_pad + k] = v;
+        s += v;
+      }
+      sums[c] = s;
+      scales[c] = h.w_scale[c];
+      b[c] = bias.empty() ? 0.f : bias[c];
+    }
+    return absl::OkStatus();
+  }, &blob));
+  // scratch: q (padded to 16 bytes), pairs [items][chunks][2], scale [items], offset [items]
+  const int items = g.batch;
+  const int item_size = g.in_h * g.in_w * g.in_c;
+  const size_t chunks = (static_cast<size_t>(item_size) + BH_DYNQUANT_CHUNK - 1) / BH_DYNQUANT_CHUNK;
+  const size_t qbytes = (static_cast<size_t>(items) * item_size + 15) / 16 * 16;
+  const size_t pbytes = 8ull * items * chunks;
+  auto scratch = std::make_shared<DeviceBlob>(ordinal_, qbytes + pbytes + 8ull * items);
+  if (!scratch->ok()) return absl::InternalError("HBM scratch allocation failed");
+  sg->consts.push_back(scratch);
+  char* sp = static_cast<char*>(scratch->ptr());
+  const bool cpu = device_flag_ == DeviceFlag::kCPU;
+  Launch Q;
+  Q.kind = Launch::kDynQuantItems;
+  Q.op_index = oi;
+  Q.dqi = bh_dynquant_items_params{};
+  Q.dqi.items = items; Q.dqi.item_size = item_size; Q.dqi.asymmetric = h.per_channel ? 1 : 0;
+  Q.dqi.input = static_cast<const float*>(in_ptr);
+  Q.dqi.q = reinterpret_cast<int8_t*>(sp);
+  Q.dqi.pairs = reinterpret_cast<float*>(sp + qbytes);
+  Q.dqi.scale = reinterpret_cast<float*>(sp + qbytes + pbytes);
+  Q.dqi.offset = reinterpret_cast<int32_t*>(sp + qbytes + pbytes + 4ull * items);
+  Q.kernel = cpu ? "dynquant_items_host" : bh_dynquant_items_kernel(&Q.dqi);
+  Q.alg_bytes = 5.0 * items * item_size + 8.0 * items;
+  sg->launches.push_back(Q);
+  const char* base = static_cast<const char*>(blob->ptr());
+  bh_conv_hybrid_params& p = L->convh;
+  p = bh_conv_hybrid_params{};
+  p.batch = g.batch; p.in_h = g.in_h; p.in_w = g.in_w; p.in_c = g.in_c;
+  p.out_h = g.out_h; p.out_w = g.out_w; p.out_c = oc;
+  p.k_h = g.k_h; p.k_w = g.k_w; p.stride_h = g.stride_h; p.stride_w = g.stride_w;
+  p.dil_h = g.dil_h; p.dil_w = g.dil_w; p.pad_h = g.pad_h; p.pad_w = g.pad_w;
+  p.k_pad = k_pad;
+  p.depth_multiplier = g.depth_multiplier;
+  p.per_channel = h.per_channel ? 1 : 0;
+  FloatActRange(g.act, &p.act_min, &p.act_max);
+  p.q = Q.dqi.q; p.in_scale = Q.dqi.scale; p.in_offset = Q.dqi.offset;
+  p.weights = reinterpret_cast<const int8_t*>(base);
+  p.w_row_sum = reinterpret_cast<const int32_t*>(base + wbytes);
+  p.w_scale = reinterpret_cast<const float*>(base + wbytes + 4ull * oc);
+  p.bias = g.bias >= 0 ? reinterpret_cast<const float*>(base + wbytes + 8ull * oc) : nullptr;
+  p.output = static_cast<float*>(out_ptr);
+  L->kind = dw ? Launch::kDwConvHybrid : Launch::kConvHybrid;
+  L->kernel = cpu ? (dw ? "dwconv_hybrid_host" : "conv_hybrid_host")
+                  : (dw ? bh_dwconv2d_hybrid_kernel(&p) : bh_conv2d_hybrid_kernel(&p));
+  const double outs = static_cast<double>(g.batch) * g.out_h * g.out_w * oc;
+  L->alg_ops = 2.0 * outs * K;
+  L->alg_bytes = static_cast<double>(items) * item_size + 8.0 * items + 4.0 * outs + static_cast<double>(wbytes) + 12.0 * oc;
+  return absl::OkStatus();
+}
+
 // ADD / SUB / MUL int8 / uint8, SQUARED_DIFFERENCE int8
 absl::Status HipModelExecutor::LowerEltwise(const HipModel& model, int oi, void* in_ptr, void* out_ptr,
                                             PreparedSubgraph* sg, Launch* L) {
@@ -1191,7 +1288,7 @@ absl::Status HipModelExecutor::Lower(const HipModel& model, int oi, PreparedSubg
   const TflOperator& op = d.ops[oi];
   std::string why;
   const bool cpu = device_flag_ == DeviceFlag::kCPU;
-  if (!(cpu ? CpuSupports(d, op, &why) : GpuSupportsHere(d, op, &why)))
+  if (!(cpu ? CpuSupportsHere(d, op, &why) : GpuSupportsHere(d, op, &why)))
     return absl::InternalError("HIP backend cannot run op " + std::to_string(oi) + " (" +
                                TflBuiltinName(op.builtin) + ") on " + ToString(device_flag_) + ": " + why);
   if (DequantFoldsIntoDetection(d, *sg, oi)) {

@@ -188,6 +188,52 @@ bool HybridFcArgs(const TflModel& m, const TflOperator& op, HybridFcGeometry* g,
   return true;
 }
 
+bool HybridConvArgs(const TflModel& m, const TflOperator& op, HybridConvGeometry* g, const char** why) {
+  auto no = [&](const char* w) {
+    if (why) *why = w;
+    return false;
+  };
+  if (!IsHybridConvOp(m, op) || op.outputs.empty() || op.outputs[0] < 0) return no("not a hybrid CONV_2D / DEPTHWISE_CONV_2D");
+  const bool dw = op.builtin == kTflDepthwiseConv2D;
+  // one literal per op and reason: `why` outlives the call
+#define BH_HY(reason) (dw ? "hybrid DEPTHWISE_CONV_2D: " reason : "hybrid CONV_2D: " reason)
+  const TflTensor& in = m.tensors[op.inputs[0]];
+  const TflTensor& w = m.tensors[op.inputs[1]];
+  if (w.type != DataType::kInt8) return no(BH_HY("uint8 filter (int8 only)"));
+  if (!w.is_const()) return no(BH_HY("filter must be a constant"));
+  if (op.inputs.size() > 2 && op.inputs[2] >= 0) {
+    const TflTensor& b = m.tensors[op.inputs[2]];
+    if (!b.is_const() || b.type != DataType::kFloat32) return no(BH_HY("bias must be a float32 constant"));
+  }
+  if (m.tensors[op.outputs[0]].type != DataType::kFloat32) return no(BH_HY("float32 output expected"));
+  for (int64_t z : w.zero_point)
+    if (z != 0) return no(BH_HY("non-zero filter zero point"));
+  if (!dw && in.shape.size() == 4 && w.shape.size() == 4 && w.shape[3] != in.shape[3])
+    return no(BH_HY("grouped filter (in_c / G input channels)"));
+  HybridConvGeometry h{};
+  const char* r = "";
+  if (!ConvArgs(m, op, &h.conv, &r)) return no(r);
+  const ConvGeometry& c = h.conv;
+  const size_t ns = w.scale.size();
+  if (ns != 1 && ns != static_cast<size_t>(c.out_c)) return no(BH_HY("filter scale count is neither 1 nor the output channels"));
+  for (float s : w.scale)
+    if (!(s > 0.f)) return no(BH_HY("filter scales must be positive"));
+  h.depthwise = dw;
+  h.per_channel = dw || ns > 1;
+  if (dw && ns == 1 && c.out_c != 1) return no(BH_HY("one filter scale (per-channel only)"));
+  const long long K = static_cast<long long>(c.k_h) * c.k_w * (dw ? 1 : c.in_c);
+  if (K > 65535) return no(BH_HY("k_h * k_w * in_c > 65,535 (the int32 sum)"));
+  if (static_cast<long long>(c.batch) * c.in_h * c.in_w * c.in_c > 0x7fffffffLL ||
+      static_cast<long long>(c.batch) * c.out_h * c.out_w * c.out_c > 0x7fffffffLL ||
+      static_cast<long long>(c.out_c) * ((K + 15) / 16 * 16) > 0x7fffffffLL)
+    return no(BH_HY("a tensor of 2^31 or more elements"));
+#undef BH_HY
+  h.w_scale.assign(c.out_c, w.scale[0]);
+  if (ns > 1) h.w_scale = w.scale;
+  if (g) *g = std::move(h);
+  return true;
+}
+
 bool PoolArgs(const TflModel& m, const TflOperator& op, PoolGeometry* g, const char** why) {
   auto no = [&](const char* w) {
     if (why) *why = w;

@@ -67,7 +67,8 @@ bool FcArgs(const TflModel& m, const TflOperator& op, FcGeometry* g, const char*
 
 // A float32 op whose filter is 8-bit: the converter's dynamic-range ("hybrid")
 // form.  FULLY_CONNECTED runs (HybridFcArgs); CONV_2D and DEPTHWISE_CONV_2D
-// are refused by name.
+// run on executors built with BAND_HIP_HYBRID_CONV=1 (HybridConvArgs) and are
+// refused by name on every other.
 inline bool IsHybridWeightOp(const TflModel& m, const TflOperator& op) {
   return (op.builtin == kTflFullyConnected || op.builtin == kTflConv2D || op.builtin == kTflDepthwiseConv2D) &&
          op.inputs.size() >= 2 && op.inputs[0] >= 0 && op.inputs[1] >= 0 &&
@@ -86,6 +87,30 @@ struct HybridFcGeometry {
   bool asymmetric;
 };
 bool HybridFcArgs(const TflModel& m, const TflOperator& op, HybridFcGeometry* g, const char** why = nullptr);
+
+inline bool IsHybridConvOp(const TflModel& m, const TflOperator& op) {
+  return op.builtin != kTflFullyConnected && IsHybridWeightOp(m, op);
+}
+// Hybrid CONV_2D / DEPTHWISE_CONV_2D: ConvArgs' geometry, the filter scales
+// expanded to [out_c] and the form.  The scale count selects the form, nothing
+// in the flatbuffer does: one scale (CONV_2D only) quantises the input
+// symmetrically and ends in bias + acc * (s * ws); out_c scales (quantised
+// dimension 0, 3 for depthwise) quantise it asymmetrically and end in
+// (acc * ws[c]) * s + bias (conv) or acc * (ws[c] * s) + bias (depthwise).
+// Refused with a reason that names the op: a uint8 or non-constant filter, a
+// bias that is not a float32 constant, a non-float32 output, a non-zero
+// filter zero point, a scale count that is neither 1 nor out_c, one scale on a
+// depthwise filter, a non-positive scale, a grouped filter, k_h k_w in_c >
+// 65,535 (the int32 sum), a tensor of 2^31 or more elements, and whatever
+// ConvArgs refuses.  Every batch item is quantised alone, so a job-batch
+// variant (more items) computes each job's own values.
+struct HybridConvGeometry {
+  ConvGeometry conv;
+  bool depthwise;
+  bool per_channel;  // out_c scales: the asymmetric input quantisation
+  std::vector<float> w_scale;  // [out_c]
+};
+bool HybridConvArgs(const TflModel& m, const TflOperator& op, HybridConvGeometry* g, const char** why = nullptr);
 
 // AVERAGE_POOL_2D / MAX_POOL_2D
 struct PoolGeometry {

@@ -55,6 +55,7 @@ HipModelExecutor::HipModelExecutor(ModelId model_id, WorkerId worker_id, DeviceF
   coalesce_max_ = env::Coalesce();
   coalesce_lanes_ = env::CoalesceLanes();
   gpu_detection_ = env::GpuDetection();
+  hybrid_conv_ = env::HybridConv();
 }
 
 HipModelExecutor::~HipModelExecutor() {
@@ -88,6 +89,7 @@ std::unique_ptr<HipModelExecutor> HipModelExecutor::MakeLane() {
   lane->direct_io_ = true;
   lane->autotune_ = autotune_;
   lane->gpu_detection_ = gpu_detection_;
+  lane->hybrid_conv_ = hybrid_conv_;
   lane->fused_attention_ = fused_attention_;
   return lane;
 }
@@ -285,7 +287,13 @@ bool HipModelExecutor::CpuSupports(const TflModel& m, const TflOperator& op, std
 bool HipModelExecutor::GpuSupportsHere(const TflModel& m, const TflOperator& op, std::string* why) const {
   int batch = 1;
   if (gpu_detection_ && DetectionSupported(m, op, nullptr, &batch)) return true;
+  if (hybrid_conv_ && IsHybridConvOp(m, op)) return FloatSupports(m, op, why, true);
   return GpuSupports(m, op, why);
+}
+
+bool HipModelExecutor::CpuSupportsHere(const TflModel& m, const TflOperator& op, std::string* why) const {
+  if (hybrid_conv_ && IsHybridConvOp(m, op)) return FloatSupports(m, op, why, true);
+  return CpuSupports(m, op, why);
 }
 
 absl::Status HipModelExecutor::EnsureMeta(const HipModel& model) {
@@ -387,11 +395,11 @@ absl::StatusOr<ModelSpec> HipModelExecutor::InvestigateModelSpec(interface::IMod
       if (u.empty()) continue;
       bool cpu_only = true;
       for (int c : u) cpu_only &= unsupported[flag].count(c) > 0;
-      if (cpu_only && CpuSupports(d, op, nullptr)) unsupported[flag].insert(i);
+      if (cpu_only && CpuSupportsHere(d, op, nullptr)) unsupported[flag].insert(i);
     }
   }
   for (int i = 0; i < num_ops; ++i)
-    if (!CpuSupports(d, d.ops[i], nullptr)) unsupported[DeviceFlag::kCPU].insert(i);
+    if (!CpuSupportsHere(d, d.ops[i], nullptr)) unsupported[DeviceFlag::kCPU].insert(i);
   ModelSpec spec(num_ops, static_cast<int>(d.tensors.size()), tensor_types,
                  std::set<int>(d.inputs.begin(), d.inputs.end()),
                  std::set<int>(d.outputs.begin(), d.outputs.end()), op_in, op_out, unsupported, unavailable);
@@ -654,6 +662,9 @@ absl::Status HipModelExecutor::EnqueueLaunch(const Launch& l) {
     case Launch::kAttention: rc = bh_attention_i8(&l.attn, stream_); break;
     case Launch::kDynQuantRows: rc = bh_dynquant_rows(&l.dq, stream_); break;
     case Launch::kFcHybrid: rc = bh_fc_hybrid(&l.fch, stream_); break;
+    case Launch::kDynQuantItems: rc = bh_dynquant_items(&l.dqi, stream_); break;
+    case Launch::kConvHybrid: rc = bh_conv2d_hybrid(&l.convh, stream_); break;
+    case Launch::kDwConvHybrid: rc = bh_dwconv2d_hybrid(&l.convh, stream_); break;
     case Launch::kMean: {
       bh_mean_params q{};
       q.outer = l.mean.outer;
@@ -861,6 +872,9 @@ absl::Status HipModelExecutor::ExecuteOnHost(PreparedSubgraph* sg) {
       case Launch::kBatchMatMulF32: CpuBatchMatMulF32(l.bmm, pool); break;
       case Launch::kDynQuantRows: CpuDynQuantRows(l.dq, pool); break;
       case Launch::kFcHybrid: CpuFcHybrid(l.fch, pool); break;
+      case Launch::kDynQuantItems: CpuDynQuantItems(l.dqi, pool); break;
+      case Launch::kConvHybrid: CpuConvHybrid(l.convh, pool); break;
+      case Launch::kDwConvHybrid: CpuDwConvHybrid(l.convh, pool); break;
       default: return absl::InternalError(std::string("no host implementation of ") + l.kernel);
     }
   }

@@ -59,7 +59,10 @@ struct Launch {
     kLayerNorm,       // the ten ops of an int8 LayerNorm as one launch (FuseLayerNorm; kGPU)
     kAttention,       // BATCH_MATMUL -> SOFTMAX -> BATCH_MATMUL (int8) as one launch (FuseAttention; kGPU, opt-in)
     kDynQuantRows,    // hybrid FULLY_CONNECTED, first launch: the input's rows quantised into the subgraph's scratch (`dq`)
-    kFcHybrid         // hybrid FULLY_CONNECTED, second launch: int8 product, float epilogue (`fch`)
+    kFcHybrid,        // hybrid FULLY_CONNECTED, second launch: int8 product, float epilogue (`fch`)
+    kDynQuantItems,   // hybrid CONV_2D / DEPTHWISE_CONV_2D, first launch(es): each batch item quantised into the subgraph's scratch (`dqi`)
+    kConvHybrid,      // hybrid CONV_2D: int8 implicit GEMM, float epilogue (`convh`)
+    kDwConvHybrid     // hybrid DEPTHWISE_CONV_2D (`convh`)
   } kind;
   int op_index = -1;
   int out_tensor = -1;  // tensor this launch materialises (after epilogue fusions)
@@ -100,6 +103,8 @@ struct Launch {
   bh_attention_params attn{};
   bh_dynquant_params dq{};
   bh_fc_hybrid_params fch{};
+  bh_dynquant_items_params dqi{};
+  bh_conv_hybrid_params convh{};
   const void* table = nullptr;  // kLutU8 / kLutF32: 256-entry device table
   long count = 0;               // kLut* / kQuantF32: elements
   float q_scale = 0.f;          // kQuantF32
@@ -219,6 +224,9 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   // (DetectionSupported) when the executor was built with
   // BAND_HIP_GPU_DETECTION=1.
   bool GpuSupportsHere(const TflModel& model, const TflOperator& op, std::string* why) const;
+  // This executor's kCPU set: CpuSupports, plus hybrid CONV_2D /
+  // DEPTHWISE_CONV_2D when the executor was built with BAND_HIP_HYBRID_CONV=1
+  bool CpuSupportsHere(const TflModel& model, const TflOperator& op, std::string* why) const;
 
  private:
   friend class JobCoalescer;
@@ -277,6 +285,10 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   // scratch owned by sg, then *l as the kFcHybrid launch
   absl::Status LowerFcHybrid(const HipModel& model, int op_index, void* in_ptr, void* out_ptr, const std::string& ckey,
                              PreparedSubgraph* sg, Launch* l);
+  // hybrid CONV_2D / DEPTHWISE_CONV_2D (HybridConvArgs; hybrid_conv_): a
+  // kDynQuantItems launch into a scratch owned by sg, then *l as the product
+  absl::Status LowerConvHybrid(const HipModel& model, int op_index, void* in_ptr, void* out_ptr, const std::string& ckey,
+                               PreparedSubgraph* sg, Launch* l);
   absl::Status LowerEltwise(const HipModel& model, int op_index, void* in_ptr, void* out_ptr, PreparedSubgraph* sg,
                             Launch* l);
   absl::Status LowerPool(const HipModel& model, int op_index, void* in_ptr, void* out_ptr, Launch* l);
@@ -360,6 +372,9 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   // executor's kGPU set.  Off by default: the reference places the op on
   // the CPU worker, and so does this backend unless asked.
   bool gpu_detection_ = false;
+  // BAND_HIP_HYBRID_CONV latched at construction: hybrid CONV_2D /
+  // DEPTHWISE_CONV_2D run (both workers: the rule changes what the op computes)
+  bool hybrid_conv_ = false;
   // BAND_HIP_FUSED_ATTENTION=1, latched when the executor binds its model
   // (-1: not yet; lanes and job-batch variants take their parent's): the
   // attention core as one launch on a kGPU executor.  Off by default.

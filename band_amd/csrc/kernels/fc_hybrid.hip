@@ -35,29 +35,12 @@
 
 #include "bmm_frag.hpp"
 #include "common.hpp"
+#include "dynquant.hpp"
 
 namespace bh {
 
 constexpr int kDqRowsPerBlock = 4;
 constexpr int kDqRegs = 4;  // float4 per lane kept between the passes: rows of up to 1024 floats
-
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-
-// one value by the row's (inv, offset): round half away from zero, then the clamp
-__device__ __forceinline__ int32_t dq_one(float x, float inv, float off, int32_t lo) {
-  const float t = x * inv;
-  const int32_t v = (int32_t)roundf(off + t);
-  return v < lo ? lo : (v > 127 ? 127 : v);
-}
 
 template <bool VEC4>
 __global__ __launch_bounds__(kDqRowsPerBlock * kWave) void dynquant_rows_kernel(bh_dynquant_params p) {
@@ -94,25 +77,7 @@ __global__ __launch_bounds__(kDqRowsPerBlock * kWave) void dynquant_rows_kernel(
 
   float s = 1.f, inv = 0.f;  // inv 0: every q is the offset, 0
   int32_t off = 0;
-  if (lane == 0) {
-    if (!p.asymmetric) {
-      const float r = fmaxf(-mn, mx);
-      if (r != 0.f) {
-        s = r / 127.f;
-        inv = 127.f / r;
-      }
-    } else if (mn != mx) {
-      const float range = mx - mn;
-      const double scale = (double)range / 255.0;
-      const double a = (double)mn / scale, b = (double)mx / scale;
-      const double z_min = -128.0 - a, z_max = 127.0 - b;
-      const double e_min = 128.0 + fabs(a), e_max = 127.0 + fabs(b);
-      const double z = e_min < e_max ? z_min : z_max;
-      off = z <= -128.0 ? -128 : (z >= 127.0 ? 127 : (int32_t)(int8_t)round(z));
-      s = (float)scale;
-      inv = 1.0f / s;
-    }
-  }
+  if (lane == 0) dq_derive(mn, mx, p.asymmetric != 0, s, inv, off);  // dynquant.hpp
   s = __shfl(s, 0);
   inv = __shfl(inv, 0);
   off = __shfl(off, 0);

@@ -859,11 +859,24 @@ class FGraph(_ReindexOps):
 
     hybrid = "symmetric" | "asymmetric" builds the converter's dynamic-range
     form instead: every constant a plain float32 tensor (no DEQUANTIZE), every
-    FULLY_CONNECTED with int8 weights (fully_connected's `hybrid`)."""
+    FULLY_CONNECTED with int8 weights (fully_connected's `hybrid`).
 
-    def __init__(self, seed=0, name="model", hybrid=None):
+    hybrid_conv = "per_channel" | "per_tensor" makes the graph dynamic-range
+    too (float32 constants, no DEQUANTIZE) and gives CONV_2D and
+    DEPTHWISE_CONV_2D int8 filters (conv's / dwconv's `hybrid`): ws = max|w| /
+    127 over each output channel (quantized_dimension 0, 3 for depthwise) or
+    over the whole filter, zero points 0, a plain float32 bias.  A depthwise
+    filter is per-channel under either graph setting.  Filters of fewer than
+    hybrid_min_elements elements stay float32, as the converter leaves small
+    weights alone (1024, restated from memory of the converter; 0 quantises
+    every filter)."""
+
+    def __init__(self, seed=0, name="model", hybrid=None, hybrid_conv=None, hybrid_min_elements=1024):
         assert hybrid in (None, "symmetric", "asymmetric"), hybrid
+        assert hybrid_conv in (None, "per_channel", "per_tensor"), hybrid_conv
         self.hybrid = hybrid
+        self.hybrid_conv = hybrid_conv
+        self.hybrid_min_elements = hybrid_min_elements
         self.dtype = np.dtype(np.float16)
         self.rng = np.random.default_rng(seed)
         self.mb = ModelBuilder(name)
@@ -882,7 +895,7 @@ class FGraph(_ReindexOps):
     def _const(self, values, kind):
         """float16 constant + DEQUANTIZE -> float32 tensor (a dynamic-range graph: a float32 constant)"""
         v = np.asarray(values, np.float32)
-        if self.hybrid:
+        if self.hybrid or self.hybrid_conv:
             return self.mb.tensor(self._name(kind), list(v.shape), np.float32, data=v)
         c = self.mb.tensor(self._name(kind + "_fp16"), list(v.shape), np.float16, data=v.astype(np.float16))
         y = self.mb.tensor(self._name(kind), list(v.shape), np.float32)
@@ -897,12 +910,46 @@ class FGraph(_ReindexOps):
     def output(self, t):
         self.mb.outputs.append(t)
 
+    def _hybrid_filter(self, wv, bv, mode, axis, kind):
+        """int8 filter tensor (scales over `axis`, the output channels, or one for the whole filter) and float32 bias"""
+        wv = np.asarray(wv, np.float32)
+        if mode == "per_channel":
+            red = tuple(a for a in range(wv.ndim) if a != axis)
+            ws = (np.abs(wv).max(axis=red, keepdims=True).astype(np.float32) / np.float32(127.0)).astype(np.float32)
+            ws[ws == 0] = 1.0
+            scale = [float(v) for v in ws.reshape(-1)]
+        else:
+            ws = np.float32(np.float32(np.abs(wv).max()) / np.float32(127.0)) or np.float32(1.0)
+            scale = [float(ws)]
+        wq = np.clip(np.round(wv / ws), -127, 127).astype(np.int8)
+        wt = self.mb.tensor(self._name(kind), list(wv.shape), np.int8, scale=scale, zero_point=[0] * len(scale),
+                            qdim=axis if mode == "per_channel" else 0, data=wq)
+        bt = self.mb.tensor(self._name(kind.replace("weights", "bias")), [wv.shape[axis]], np.float32,
+                            data=np.asarray(bv, np.float32))
+        return wt, bt
+
+    def _conv_mode(self, hybrid, elements, depthwise):
+        assert hybrid in (None, "per_channel", "per_tensor"), hybrid
+        if hybrid:
+            return hybrid  # the call's own choice, whatever the size
+        if not self.hybrid_conv or elements < self.hybrid_min_elements:
+            return None
+        return "per_channel" if depthwise else self.hybrid_conv
+
     def conv(self, x, out_c, k=1, stride=1, act="RELU6", padding="SAME", dilation=1, out_scale=None,
-             bias_offset_lsb=0):
+             bias_offset_lsb=0, hybrid=None):
+        """hybrid = "per_channel" | "per_tensor" (default: the graph's hybrid_conv above
+        hybrid_min_elements): an int8 filter, see the class"""
         b, h, w, c = self.meta[x][0]
         K = k * k * c
-        wt = self._const(self.rng.normal(0, np.sqrt(2.0 / K), (out_c, k, k, c)), "weights")
-        bt = self._const(self.rng.normal(0, 0.05, out_c) + (bias_offset_lsb * 0.05 if bias_offset_lsb else 0), "bias")
+        mode = self._conv_mode(hybrid, out_c * K, False)
+        wv = self.rng.normal(0, np.sqrt(2.0 / K), (out_c, k, k, c))
+        bv = self.rng.normal(0, 0.05, out_c) + (bias_offset_lsb * 0.05 if bias_offset_lsb else 0)
+        if mode:
+            wt, bt = self._hybrid_filter(wv, bv, mode, 0, "weights")
+        else:
+            wt = self._const(wv, "weights")
+            bt = self._const(bv, "bias")
         eff = (k - 1) * dilation + 1
         oh = (h + stride - 1) // stride if padding == "SAME" else (h + stride - eff) // stride
         ow = (w + stride - 1) // stride if padding == "SAME" else (w + stride - eff) // stride
@@ -910,11 +957,18 @@ class FGraph(_ReindexOps):
         self.mb.op("CONV_2D", [x, wt, bt], [y], OPT["Conv2DOptions"], conv_options(padding, stride, act, dilation))
         return y
 
-    def dwconv(self, x, k=3, stride=1, act="RELU6", padding="SAME", dm=1, dilation=1):
+    def dwconv(self, x, k=3, stride=1, act="RELU6", padding="SAME", dm=1, dilation=1, hybrid=None):
+        """hybrid: as conv's; scales over dimension 3"""
         b, h, w, c = self.meta[x][0]
         out_c = c * dm
-        wt = self._const(self.rng.normal(0, np.sqrt(2.0 / (k * k)), (1, k, k, out_c)), "dw_weights")
-        bt = self._const(self.rng.normal(0, 0.05, out_c), "dw_bias")
+        mode = self._conv_mode(hybrid, k * k * out_c, True)
+        wv = self.rng.normal(0, np.sqrt(2.0 / (k * k)), (1, k, k, out_c))
+        bv = self.rng.normal(0, 0.05, out_c)
+        if mode:
+            wt, bt = self._hybrid_filter(wv, bv, mode, 3, "dw_weights")
+        else:
+            wt = self._const(wv, "dw_weights")
+            bt = self._const(bv, "dw_bias")
         eff = (k - 1) * dilation + 1
         oh = (h + stride - 1) // stride if padding == "SAME" else (h + stride - eff) // stride
         ow = (w + stride - 1) // stride if padding == "SAME" else (w + stride - eff) // stride
@@ -1068,8 +1122,12 @@ class FGraph(_ReindexOps):
         return self.mb.build()
 
 
-def _graph(dtype, seed, name):
-    """QGraph for 8-bit models, FGraph for fp16-weight float models"""
+def _graph(dtype, seed, name, hybrid_conv=None, hybrid_min_elements=1024):
+    """QGraph for 8-bit models, FGraph for fp16-weight float models and, with
+    hybrid_conv, for the dynamic-range float32 CNN"""
+    if hybrid_conv:
+        assert np.dtype(dtype) == np.dtype(np.float32), "hybrid_conv is a form of the float32 model"
+        return FGraph(seed, name + "_hybrid", hybrid_conv=hybrid_conv, hybrid_min_elements=hybrid_min_elements)
     if np.dtype(dtype) == np.float16:
         return FGraph(seed, name)
     return QGraph(dtype, seed, name)
@@ -1082,10 +1140,13 @@ MNV2_BLOCKS = [(1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 9
                (6, 160, 3, 2), (6, 320, 1, 1)]
 
 
-def mobilenet_v2(dtype=np.int8, seed=0, size=224, batch=1, classes=1001, width=1.0):
+def mobilenet_v2(dtype=np.int8, seed=0, size=224, batch=1, classes=1001, width=1.0, hybrid_conv=None,
+                 hybrid_min_elements=1024):
     """MobileNetV2-1.0 with the topology of mobilenet_v2_1.0_224_quant.tflite
-    (65 ops: 36 CONV_2D, 17 DEPTHWISE_CONV_2D, 10 ADD, AVERAGE_POOL_2D, RESHAPE)."""
-    g = _graph(dtype, seed, "mobilenet_v2_%s" % np.dtype(dtype).name)
+    (65 ops: 36 CONV_2D, 17 DEPTHWISE_CONV_2D, 10 ADD, AVERAGE_POOL_2D, RESHAPE).
+    dtype float32 with hybrid_conv ("per_channel" | "per_tensor") builds the
+    dynamic-range CNN (FGraph): float32 constants, int8 filters."""
+    g = _graph(dtype, seed, "mobilenet_v2_%s" % np.dtype(dtype).name, hybrid_conv, hybrid_min_elements)
     ch = lambda c: max(8, int(c * width + 4) // 8 * 8)
     x = g.input([batch, size, size, 3])
     x = g.conv(x, ch(32), k=3, stride=2)
@@ -1112,9 +1173,10 @@ def mobilenet_v2(dtype=np.int8, seed=0, size=224, batch=1, classes=1001, width=1
     return g.build()
 
 
-def mobilenet_v1(dtype=np.int8, seed=0, size=224, batch=1, classes=1001):
-    """MobileNetV1-1.0 (config C1): conv + 13 depthwise-separable blocks."""
-    g = _graph(dtype, seed, "mobilenet_v1_%s" % np.dtype(dtype).name)
+def mobilenet_v1(dtype=np.int8, seed=0, size=224, batch=1, classes=1001, hybrid_conv=None, hybrid_min_elements=1024):
+    """MobileNetV1-1.0 (config C1): conv + 13 depthwise-separable blocks.
+    hybrid_conv: the dynamic-range CNN, as mobilenet_v2's."""
+    g = _graph(dtype, seed, "mobilenet_v1_%s" % np.dtype(dtype).name, hybrid_conv, hybrid_min_elements)
     x = g.input([batch, size, size, 3])
     x = g.conv(x, 32, k=3, stride=2)
     for c, s in [(64, 1), (128, 2), (128, 1), (256, 2), (256, 1), (512, 2), (512, 1), (512, 1),
@@ -1244,16 +1306,19 @@ def encoder_block(dtype=np.int8, seed=8, tokens=196, dim=192, heads=3, hidden=76
 
 
 def vit_tiny(dtype=np.int8, seed=7, size=224, dim=192, heads=3, blocks=2, batch=1, layer_norm=False, mlp=False,
-             hybrid=None):
+             hybrid=None, hybrid_conv=None, hybrid_min_elements=1024):
     """ViT-Tiny's front: a 16 x 16 stride-16 patch CONV_2D, RESHAPE to tokens
     [batch, (size / 16)^2, dim] and `blocks` attention blocks; with layer_norm
     / mlp, pre-norm encoder blocks (encoder_block's, hidden = 4 dim).  No
     class token and no position embedding.  dtype float32 with `hybrid`
     ("symmetric" | "asymmetric") builds the dynamic-range float model: a float32
-    patch conv, hybrid FULLY_CONNECTEDs."""
+    patch conv, hybrid FULLY_CONNECTEDs; with hybrid_conv ("per_channel" |
+    "per_tensor") beside it the patch conv is hybrid too."""
+    assert not hybrid_conv or hybrid, "hybrid_conv goes with hybrid"
     if hybrid:
         assert np.dtype(dtype) == np.dtype(np.float32), "hybrid is a form of the float32 model"
-        g = FGraph(seed, "vit_tiny_f32_hybrid", hybrid=hybrid)
+        g = FGraph(seed, "vit_tiny_f32_hybrid", hybrid=hybrid, hybrid_conv=hybrid_conv,
+                   hybrid_min_elements=hybrid_min_elements)
     else:
         g = QGraph(dtype, seed, "vit_tiny_%s" % np.dtype(dtype).name)
     x = g.input([batch, size, size, 3], scale=0.05)

@@ -208,6 +208,13 @@ int bhx_cpu_unary_f32(int kind, const float* in, float* out, long n);
  * checks refuse. */
 int bhx_cpu_dynquant_rows(const void* dynquant_params);
 int bhx_cpu_fc_hybrid(const void* fc_hybrid_params);
+/* CpuDynQuantItems / CpuConvHybrid / CpuDwConvHybrid, the host twins of
+ * bh_dynquant_items, bh_conv2d_hybrid and bh_dwconv2d_hybrid (hybrid CONV_2D /
+ * DEPTHWISE_CONV_2D) over host pointers: a bh_dynquant_items_params / a
+ * bh_conv_hybrid_params.  Refuse what the launchers' checks refuse. */
+int bhx_cpu_dynquant_items(const void* dynquant_items_params);
+int bhx_cpu_conv_hybrid(const void* conv_hybrid_params);
+int bhx_cpu_dwconv_hybrid(const void* conv_hybrid_params);
 /* The 256-entry tables the 8-bit RSQRT (int8) and GELU lower to, indexed by
  * the input byte, and squared_difference.cc's multipliers as {m1, s1, m2, s2,
  * mo, so, left_shift}; non-zero (bhx_last_error names the reason) for scales

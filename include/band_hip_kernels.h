@@ -43,6 +43,9 @@
  *                        reference_integer_ops::FullyConnected without a bias, per batch slice)
  *   bh_dynquant_rows + bh_fc_hybrid <- FULLY_CONNECTED float32 with int8 weights (fully_connected.cc
  *                        EvalHybrid: each input row quantised at run time, int8 product, float epilogue)
+ *   bh_dynquant_items + bh_conv2d_hybrid / bh_dwconv2d_hybrid <- CONV_2D / DEPTHWISE_CONV_2D float32
+ *                        with an int8 filter (conv.cc / depthwise_conv.cc EvalHybrid[PerChannel]: each
+ *                        batch item quantised at run time; executors built with BAND_HIP_HYBRID_CONV=1)
  *   bh_detection_postprocess <- TFLite_Detection_PostProcess (custom; detection_postprocess.cc,
  *                        fast NMS, one class per detection)
  *   (HARD_SWISH 8-bit runs as a bh_lut_u8 table of reference_ops::HardSwish)
@@ -1010,6 +1013,89 @@ int bh_fc_hybrid(const bh_fc_hybrid_params* p, bh_stream_t s);
 const char* bh_fc_hybrid_kernel(const bh_fc_hybrid_params* p);
 /* the launcher's parameter check alone; pure host */
 int bh_fc_hybrid_check(const bh_fc_hybrid_params* p);
+
+/* Dynamic-range ("hybrid") CONV_2D / DEPTHWISE_CONV_2D: float32 input,
+ * constant int8 filter (OHWI; [1][kh][kw][out_c] depthwise) with zero points
+ * 0, float32 output.  Restated from memory of TFLite's conv.cc EvalHybrid /
+ * EvalHybridPerChannel, depthwise_conv.cc EvalHybridPerChannel and the
+ * reference hybrid kernels - their source was not at hand (DESIGN 4 holds the
+ * rule and says what is pinned).  Every float operation is one IEEE float32
+ * operation (float64 where the row rule above marks it), no contraction.
+ *
+ * bh_dynquant_items quantises each batch item - the item_size = H W C floats
+ * of one image - on its own by exactly the row rule of bh_dynquant_rows with
+ * the item as the row, into q [items][item_size], scale [items], offset
+ * [items].  Two forms.  One launch (dynquant_item_kernel): a workgroup per
+ * item takes the item's min and max, derives (s, inv, off) and quantises.
+ * Two launches: dynquant_minmax_kernel writes one (min, max) pair per
+ * BH_DYNQUANT_CHUNK floats into `pairs` [items][chunks][2]; in
+ * dynquant_items_kernel every workgroup reduces its item's pairs (min and max
+ * are exact in any order), derives the same three values and quantises its
+ * chunk, and the item's first workgroup stores s and off.  No atomics, no
+ * waiting across workgroups.  form 0 picks by item_size (one launch up to
+ * BH_DYNQUANT_ONE_LAUNCH_MAX floats), 1 / 2 force a form.  `pairs` may be
+ * null where the one-launch form is taken.
+ *
+ * bh_conv2d_hybrid (conv_hybrid_kernel, v_mfma_i32_16x16x64_i8, the implicit
+ * im2col GEMM M = batch out_h out_w, N = out_c, K = k_h k_w in_c):
+ *   acc = sum over the in-bounds taps of w (q - off[b])       (int32, exact)
+ *   one filter scale (per_channel 0; the input quantised symmetrically, off 0):
+ *     y = bias[c] + (float)acc * (s[b] * ws)
+ *   out_c filter scales (per_channel 1; the input quantised asymmetrically):
+ *     y = ((float)acc * ws[c]) * s[b] + bias[c]
+ * the kernel fills a padded tap with the byte off[b] and subtracts
+ * off[b] * w_row_sum[c] (the sum over all taps), the same integer.
+ * bh_dwconv2d_hybrid (dwconv_hybrid_kernel, VALU, a lane per 4 output
+ * channels of a pixel; out_c scales):
+ *   y = (float)acc * (ws[c] * s[b]) + bias[c]
+ * All clamp to [act_min, act_max]; a missing bias adds 0.  weights: conv
+ * [out_c][k_pad], k_pad = K rounded up to 16, zero padding, 16-byte aligned;
+ * depthwise [k_h k_w][out_c] as the flatbuffer holds them.  w_scale is
+ * [out_c] in every form (one scale: repeated).  w_row_sum [out_c] is read by
+ * bh_conv2d_hybrid only.
+ * Refused (BH_EINVAL, bh_last_error names the launcher and the reason): null
+ * pointers, non-positive extents, K > 65,535 (the int32 sum), 2^31 or more
+ * elements in a tensor, a bad k_pad or depth multiplier, an output shape that
+ * reads outside the padded input, misaligned operands. */
+#define BH_DYNQUANT_CHUNK 4096
+#define BH_DYNQUANT_ONE_LAUNCH_MAX 16384
+typedef struct bh_dynquant_items_params {
+  int items, item_size;
+  int asymmetric;
+  int form;             /* 0: by item_size; 1: one launch; 2: two launches */
+  const float* input;   /* [items][item_size] */
+  int8_t* q;            /* [items][item_size] */
+  float* scale;         /* [items] */
+  int32_t* offset;      /* [items] */
+  float* pairs;         /* [items][ceil(item_size / BH_DYNQUANT_CHUNK)][2]; two-launch form */
+} bh_dynquant_items_params;
+int bh_dynquant_items(const bh_dynquant_items_params* p, bh_stream_t s);
+/* "dynquant_item_kernel" or "dynquant_minmax_kernel+dynquant_items_kernel", or "" when refused; static storage */
+const char* bh_dynquant_items_kernel(const bh_dynquant_items_params* p);
+int bh_dynquant_items_check(const bh_dynquant_items_params* p);
+
+typedef struct bh_conv_hybrid_params {
+  int batch, in_h, in_w, in_c, out_h, out_w, out_c;
+  int k_h, k_w, stride_h, stride_w, dil_h, dil_w, pad_h, pad_w;
+  int k_pad;             /* bh_conv2d_hybrid: K padded to 16 */
+  int depth_multiplier;  /* bh_dwconv2d_hybrid: out_c / in_c */
+  int per_channel;       /* bh_conv2d_hybrid: which epilogue */
+  float act_min, act_max;
+  const int8_t* q;            /* [batch][in_h][in_w][in_c] */
+  const float* in_scale;      /* [batch] */
+  const int32_t* in_offset;   /* [batch] */
+  const int8_t* weights;
+  const int32_t* w_row_sum;   /* [out_c]; conv only */
+  const float* w_scale;       /* [out_c] */
+  const float* bias;          /* [out_c] or NULL */
+  float* output;              /* [batch][out_h][out_w][out_c] */
+} bh_conv_hybrid_params;
+int bh_conv2d_hybrid(const bh_conv_hybrid_params* p, bh_stream_t s);
+const char* bh_conv2d_hybrid_kernel(const bh_conv_hybrid_params* p);  /* "conv_hybrid_kernel" or "" */
+int bh_conv2d_hybrid_check(const bh_conv_hybrid_params* p);
+int bh_dwconv2d_hybrid(const bh_conv_hybrid_params* p, bh_stream_t s);
+const char* bh_dwconv2d_hybrid_kernel(const bh_conv_hybrid_params* p);  /* "dwconv_hybrid_kernel" or "" */
+int bh_dwconv2d_hybrid_check(const bh_conv_hybrid_params* p);
 
 /* TRANSPOSE_CONV support: U[y*sh][x*sw][:] = in[y][x][:], every other
  * position of U (out_h x out_w = (in-1)*stride+1) holds `fill` (the input
