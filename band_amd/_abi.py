@@ -103,6 +103,15 @@ class LayerNormParams(ctypes.Structure):
         ("eps_q", c_int32)] + [(n, c_void_p) for n in ("rsqrt_table", "input", "gamma", "beta", "output")]
 
 
+LAYERNORM_F32_MAX_DEPTH = 1024  # BH_LAYERNORM_F32_MAX_DEPTH
+
+
+class LayerNormF32Params(ctypes.Structure):
+    """bh_layernorm_f32_params: a float32 LayerNorm as one launch; output may be null, q / scale / offset all or none"""
+    _fields_ = [("rows", ctypes.c_long), ("depth", c_int), ("eps", ctypes.c_float)] + [
+        (n, c_void_p) for n in ("input", "gamma", "beta", "output", "q", "scale", "offset")] + [("asymmetric", c_int)]
+
+
 class DetectionParams(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("batch", "num_boxes", "num_classes", "num_classes_with_background",
                                      "max_detections")] + [
@@ -391,6 +400,9 @@ KERNEL_SYMBOLS = {
     "bh_layernorm_i8": (c_int, [ctypes.POINTER(LayerNormParams), c_void_p]),
     "bh_layernorm_i8_kernel": (ctypes.c_char_p, [ctypes.POINTER(LayerNormParams)]),
     "bh_layernorm_i8_check": (c_int, [ctypes.POINTER(LayerNormParams)]),
+    "bh_layernorm_f32": (c_int, [ctypes.POINTER(LayerNormF32Params), c_void_p]),
+    "bh_layernorm_f32_kernel": (ctypes.c_char_p, [ctypes.POINTER(LayerNormF32Params)]),
+    "bh_layernorm_f32_check": (c_int, [ctypes.POINTER(LayerNormF32Params)]),
     "bh_detection_scratch_bytes": (c_size_t, [c_int, c_int]),
     "bh_detection_postprocess": (c_int, [ctypes.POINTER(DetectionParams), c_void_p]),
     "bh_chain_lds_bytes": (c_size_t, [ctypes.POINTER(ChainParams)]),

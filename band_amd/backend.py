@@ -82,6 +82,8 @@ _abi.BACKEND_SYMBOLS.update({
     "bhx_time_subgraph": (c_int, _KEY + [c_int, ctypes.POINTER(ctypes.c_double)]),
     "bhx_cpu_reindex": (c_int, [ctypes.POINTER(_abi.ReindexParams)]),
     "bhx_launch_kernels": (c_int, _KEY + [ctypes.POINTER(ctypes.c_char_p), c_int, ctypes.POINTER(c_int)]),
+    "bhx_job_batch_launch_kernels": (c_int, _KEY + [c_int, ctypes.POINTER(ctypes.c_char_p), c_int,
+                                                    ctypes.POINTER(c_int)]),
     "bhx_cpu_conv_grouped": (c_int, [ctypes.POINTER(_abi.ConvGroupedParams)]),
     "bhx_cpu_batch_matmul": (c_int, [ctypes.POINTER(_abi.BatchMatMulParams), c_int]),
     "bhx_cpu_mean_rows": (c_int, [ctypes.POINTER(_abi.MeanRowsParams)]),
@@ -502,6 +504,15 @@ class HipModelExecutor:
         cap = 4096
         arr = (ctypes.c_char_p * cap)()
         _abi.check(self.lib.bhx_launch_kernels(self.handle, *key._args(), arr, cap, ctypes.byref(n)), "LaunchKernels")
+        return [arr[i].decode() for i in range(min(n.value, cap))]
+
+    def JobBatchLaunchKernels(self, key, jobs):
+        """LaunchKernels of the job-batch variant that runs `jobs` jobs (PrepareJobBatches)"""
+        n = c_int(0)
+        cap = 4096
+        arr = (ctypes.c_char_p * cap)()
+        _abi.check(self.lib.bhx_job_batch_launch_kernels(self.handle, *key._args(), int(jobs), arr, cap,
+                                                         ctypes.byref(n)), "JobBatchLaunchKernels")
         return [arr[i].decode() for i in range(min(n.value, cap))]
 
     def TimeSubgraph(self, key, iters=100):

@@ -465,6 +465,18 @@ int bhx_launch_kernels(bhx_executor* e, int mid, int wid, uint64_t mask, const c
   return 0;
 }
 
+int bhx_job_batch_launch_kernels(bhx_executor* e, int mid, int wid, uint64_t mask, int jobs, const char** out, int cap,
+                                 int* n) {
+  auto* h = e ? dynamic_cast<band::hip::HipModelExecutor*>(e->exec.get()) : nullptr;
+  if (!h) return Fail("not a HIP executor");
+  std::vector<const char*> k;
+  auto s = h->JobBatchLaunchKernels(Key(mid, wid, mask), jobs, &k);
+  if (!s.ok()) return Fail(s);
+  if (n) *n = static_cast<int>(k.size());
+  for (int i = 0; out && i < cap && i < static_cast<int>(k.size()); ++i) out[i] = k[i];
+  return 0;
+}
+
 int bhx_cpu_conv_grouped(const void* grouped_params) {
   if (!grouped_params) return Fail("null argument");
   const bh_conv_grouped_params& gp = *static_cast<const bh_conv_grouped_params*>(grouped_params);

@@ -54,6 +54,9 @@ inline bool HybridConv() { return Flag("BAND_HIP_HYBRID_CONV", false); }
 inline bool Precapture() { return Flag("BAND_HIP_PRECAPTURE", true); }
 // 1: BATCH_MATMUL -> SOFTMAX -> BATCH_MATMUL (int8) as one attention_i8_kernel launch on kGPU executors
 inline bool FusedAttention() { return Flag("BAND_HIP_FUSED_ATTENTION", false); }
+// 1: the ten float32 ops of a LayerNorm as one layernorm_f32_kernel launch on kGPU executors, which also
+// quantises its rows for the hybrid FULLY_CONNECTEDs that read them
+inline bool FusedLayerNormF32() { return Flag("BAND_HIP_FUSED_LAYERNORM_F32", false); }
 // 1: kernels without the host copies (tools/concurrency_probe.py --no-io)
 inline bool ProbeNoIo() { return Flag("BAND_HIP_PROBE_NO_IO", false); }
 // file the chain tuner's decisions persist in (unset or empty: none)

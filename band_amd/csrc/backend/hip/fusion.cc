@@ -897,6 +897,180 @@ void HipModelExecutor::FuseLayerNorm(const HipModel& model, PreparedSubgraph* sg
   sg->launches.swap(out);
 }
 
+// The same ten ops in float32 (FGraph.layer_norm; BAND_HIP_FUSED_LAYERNORM_F32=1,
+// kGPU): kMean, kEltwiseF32 (SQDIFF), kMean, kEltwiseF32 (ADD), kUnaryF32
+// (RSQRT), kEltwiseF32 x 5 (MUL, MUL, MUL, SUB, ADD) with FuseLayerNorm's
+// operand wiring become one layernorm_f32_kernel launch.  They qualify when
+// every tensor is float32, the MEANs run over the last axis with keep_dims,
+// every fused activation is NONE, gamma and beta are float32 constants [C],
+// eps is a float32 constant of one element (its value is taken here), every
+// intermediate is private to the pattern, no output and not viewed, and the
+// launcher's check takes the row (C <= BH_LAYERNORM_F32_MAX_DEPTH).  The
+// kernel's two row sums have an order of their own (band_hip_kernels.h), so
+// its result lies within the ops' error bound but is not their bits.
+//   A model whose constants are fp16 behind DEQUANTIZE ops lowers a
+// DEQUANTIZE launch between the MEAN and the ADD of eps (and its gamma / beta
+// are no constants): it never presents the ten consecutive launches and keeps
+// them.
+void HipModelExecutor::FuseLayerNormF32(const HipModel& model, PreparedSubgraph* sg) {
+  const TflModel& d = model.desc();
+  static const int kPattern[10] = {kTflMean, kTflSquaredDifference, kTflMean, kTflAdd, kTflRsqrt,
+                                   kTflMul,  kTflMul,               kTflMul,  kTflSub, kTflAdd};
+  static const Launch::Kind kKinds[10] = {Launch::kMean,       Launch::kEltwiseF32, Launch::kMean,       Launch::kEltwiseF32,
+                                          Launch::kUnaryF32,   Launch::kEltwiseF32, Launch::kEltwiseF32, Launch::kEltwiseF32,
+                                          Launch::kEltwiseF32, Launch::kEltwiseF32};
+  static const int kElt[10] = {-1, BH_ELTF_SQDIFF, -1, BH_ELTF_ADD, -1, BH_ELTF_MUL, BH_ELTF_MUL, BH_ELTF_MUL, BH_ELTF_SUB,
+                               BH_ELTF_ADD};
+  auto in_outputs = [&](int t) {
+    return std::find(sg->outputs.begin(), sg->outputs.end(), t) != sg->outputs.end() ||
+           std::find(d.outputs.begin(), d.outputs.end(), t) != d.outputs.end();
+  };
+  const float inf = std::numeric_limits<float>::infinity();
+  std::vector<Launch> out;
+  for (size_t i = 0; i < sg->launches.size(); ++i) {
+    const std::vector<Launch>& ls = sg->launches;
+    bool ok = i + 10 <= ls.size();
+    const TflOperator* o[10] = {};
+    for (int k = 0; ok && k < 10; ++k) {
+      const Launch& l = ls[i + k];
+      ok = l.kind == kKinds[k] && l.op_index >= 0 && d.ops[l.op_index].builtin == kPattern[k] &&
+           d.ops[l.op_index].outputs.size() == 1 && l.out_tensor == d.ops[l.op_index].outputs[0] &&
+           d.ops[l.op_index].inputs.size() >= (k == 4 ? 1u : 2u);
+      if (ok && kElt[k] >= 0) ok = l.eltf.kind == kElt[k] && l.eltf.act_min == -inf && l.eltf.act_max == inf;
+      if (ok && k == 4) ok = l.unary_kind == BH_UNARY_RSQRT;
+      if (ok) o[k] = &d.ops[l.op_index];
+    }
+    if (!ok) {
+      out.push_back(ls[i]);
+      continue;
+    }
+    auto in = [&](int k, int j) { return o[k]->inputs[j]; };
+    auto res = [&](int k) { return o[k]->outputs[0]; };
+    const int x = in(0, 0), m = res(0), dd = res(1), v = res(2), e = res(3), r = res(4), g = res(5), a = res(6),
+              b = res(7), c = res(8), y = res(9);
+    const int eps = in(3, 1), gamma = in(5, 1), beta = in(8, 0);
+    ok = x >= 0 && in(1, 0) == x && in(1, 1) == m && in(2, 0) == dd && in(3, 0) == v && in(4, 0) == e &&
+         in(5, 0) == r && in(6, 0) == x && in(6, 1) == g && in(7, 0) == m && in(7, 1) == g && in(8, 1) == b &&
+         in(9, 0) == a && in(9, 1) == c && eps >= 0 && gamma >= 0 && beta >= 0;
+    if (!ok) {
+      out.push_back(ls[i]);
+      continue;
+    }
+    const TflTensor& tx = d.tensors[x];
+    const long depth = !tx.shape.empty() ? tx.shape.back() : 0;
+    ok = depth >= 1 && d.tensors[y].shape == tx.shape && d.tensors[eps].is_const() &&
+         d.tensors[eps].num_elements() == 1 && d.tensors[eps].data_size >= 4 && d.tensors[gamma].is_const() &&
+         d.tensors[gamma].shape == std::vector<int>{static_cast<int>(depth)} && d.tensors[beta].is_const() &&
+         d.tensors[beta].shape == std::vector<int>{static_cast<int>(depth)};
+    for (int t : {x, m, dd, v, e, r, g, a, b, c, y, eps, gamma, beta}) ok = ok && d.tensors[t].type == DataType::kFloat32;
+    // the row statistics keep the input's rank with a last axis of 1 (keep_dims), the per-element tensors its shape
+    std::vector<int> stat = tx.shape;
+    if (!stat.empty()) stat.back() = 1;
+    for (int t : {m, v, e, r}) ok = ok && d.tensors[t].shape == stat;
+    for (int t : {dd, g, a, b, c}) ok = ok && d.tensors[t].shape == tx.shape;
+    // MEAN over the last axis alone: rows x depth x 1
+    for (int k : {0, 2}) {
+      const CpuMeanParams& q = ls[i + k].mean;
+      ok = ok && q.type == 0 && q.inner == 1 && q.reduce == depth &&
+           q.outer * depth == static_cast<long>(tx.num_elements());
+    }
+    std::set<int> inside;
+    for (int k = 0; k < 10; ++k) inside.insert(ls[i + k].op_index);
+    for (int t : {m, dd, v, e, r, g, a, b, c}) {
+      ok = ok && !in_outputs(t) && !sg->no_fuse.count(t) && !sg->extra_d2h.count(t);
+      for (int consumer : consumers_[t]) ok = ok && inside.count(consumer) > 0;
+    }
+    Launch F;
+    if (ok) {
+      F.kind = Launch::kLayerNormF32;
+      F.op_index = ls[i].op_index;
+      F.out_tensor = y;
+      bh_layernorm_f32_params& p = F.lnf;
+      p = bh_layernorm_f32_params{};
+      p.rows = ls[i].mean.outer;
+      p.depth = static_cast<int>(depth);
+      std::memcpy(&p.eps, d.tensors[eps].data, sizeof(float));
+      p.input = static_cast<const float*>(ls[i].mean.input);
+      p.gamma = ls[i + 5].eltf.b;
+      p.beta = ls[i + 8].eltf.a;
+      p.output = ls[i + 9].eltf.out;
+      ok = ls[i + 6].eltf.a == p.input && bh_layernorm_f32_check(&p) == 0;
+    }
+    if (!ok) {
+      out.push_back(ls[i]);
+      continue;
+    }
+    F.kernel = bh_layernorm_f32_kernel(&F.lnf);
+    F.alg_bytes = 8.0 * static_cast<double>(tx.num_elements()) + 8.0 * depth;
+    for (int k = 1; k < 10; ++k) sg->fused_ops.insert(ls[i + k].op_index);
+    for (int t : {m, dd, v, e, r, g, a, b, c}) sg->fused_tensors.insert(t);
+    out.push_back(F);
+    i += 9;
+  }
+  sg->launches.swap(out);
+}
+
+// The row quantisation of the hybrid FULLY_CONNECTEDs that read a fused
+// float32 LayerNorm's result y, folded into that launch: the finished row is
+// quantised once, in registers, for all of them.  Per fused launch: the
+// kDynQuantRows launches whose op reads tensor y itself, over its rows x
+// depth, in one form (the first reader's; a reader of the other form keeps its
+// launch) are dropped, the fused launch writes q / scale / offset into the
+// first one's scratch, and every such op's kFcHybrid block reads that scratch.
+// y itself is then stored only when something still reads it: an op whose
+// launch was not folded, an output, a view (no_fuse / extra_d2h).  Otherwise
+// it joins fused_tensors, so a later view re-lowers with y materialised.
+void HipModelExecutor::FoldLayerNormQuant(const HipModel& model, PreparedSubgraph* sg) {
+  const TflModel& d = model.desc();
+  std::vector<Launch>& ls = sg->launches;
+  std::vector<bool> dead(ls.size(), false);
+  for (size_t i = 0; i < ls.size(); ++i) {
+    if (ls[i].kind != Launch::kLayerNormF32 || ls[i].lnf.q) continue;
+    bh_layernorm_f32_params& p = ls[i].lnf;
+    const int y = ls[i].out_tensor;
+    std::set<int> folded;  // ops whose quantisation this launch takes over
+    const bh_dynquant_params* first = nullptr;
+    for (size_t j = i + 1; j < ls.size(); ++j) {
+      const Launch& q = ls[j];
+      if (q.kind != Launch::kDynQuantRows || dead[j] || q.op_index < 0) continue;
+      const TflOperator& op = d.ops[q.op_index];
+      if (op.inputs.empty() || op.inputs[0] != y || q.dq.input != p.output || q.dq.rows != p.rows ||
+          q.dq.depth != p.depth)
+        continue;
+      if (first && (q.dq.asymmetric != 0) != (first->asymmetric != 0)) continue;
+      if (!first) first = &q.dq;
+      folded.insert(q.op_index);
+      dead[j] = true;
+    }
+    if (!first) continue;
+    p.q = first->q;
+    p.scale = first->scale;
+    p.offset = first->offset;
+    p.asymmetric = first->asymmetric;
+    for (Launch& l : ls)
+      if (l.kind == Launch::kFcHybrid && folded.count(l.op_index)) {
+        l.fch.q = p.q;
+        l.fch.in_scale = p.scale;
+        l.fch.in_offset = p.offset;
+      }
+    bool needed = sg->no_fuse.count(y) || sg->extra_d2h.count(y) ||
+                  std::find(sg->outputs.begin(), sg->outputs.end(), y) != sg->outputs.end() ||
+                  std::find(d.outputs.begin(), d.outputs.end(), y) != d.outputs.end();
+    for (int consumer : consumers_[y]) needed = needed || !folded.count(consumer);
+    ls[i].alg_bytes += 1.0 * static_cast<double>(p.rows) * p.depth + 8.0 * p.rows;
+    if (!needed) {
+      ls[i].alg_bytes -= 4.0 * static_cast<double>(p.rows) * p.depth;
+      p.output = nullptr;
+      sg->fused_tensors.insert(y);
+    }
+    if (bh_layernorm_f32_check(&p) == 0) ls[i].kernel = bh_layernorm_f32_kernel(&p);
+  }
+  std::vector<Launch> out;
+  for (size_t i = 0; i < ls.size(); ++i)
+    if (!dead[i]) out.push_back(ls[i]);
+  sg->launches.swap(out);
+}
+
 // The attention core of a converted int8 block, three consecutive launches
 //   scores = BATCH_MATMUL(q, k, adj_y)   p = SOFTMAX(scores)   ctx = BATCH_MATMUL(p, v)
 // becomes one attention_i8_kernel launch (BAND_HIP_FUSED_ATTENTION=1, kGPU)

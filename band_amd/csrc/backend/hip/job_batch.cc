@@ -62,6 +62,7 @@ absl::Status HipModelExecutor::PrepareJobBatches(interface::IModel* model, const
     v.exec->gpu_detection_ = gpu_detection_;
     v.exec->hybrid_conv_ = hybrid_conv_;
     v.exec->fused_attention_ = fused_attention_;
+    v.exec->fused_layernorm_f32_ = fused_layernorm_f32_;
     if (device_flag_ == DeviceFlag::kCPU) {  // one host pool per worker
       if (!cpu_pool_)
         cpu_pool_ = std::make_shared<CpuPool>(num_threads_ > 0 ? num_threads_ : 1,
@@ -127,6 +128,14 @@ std::shared_ptr<interface::ITensorView> HipModelExecutor::GetJobSlotView(const S
   if (!vs || h == vs->host.end()) return nullptr;  // slot views exist for boundary tensors only
   TensorMeta* m = meta_[index].get();
   return std::make_shared<HipTensorView>(m, h->second->data() + static_cast<size_t>(slot) * m->bytes);
+}
+
+absl::Status HipModelExecutor::JobBatchLaunchKernels(const SubgraphKey& key, int n,
+                                                     std::vector<const char*>* out) const {
+  if (n == 1) return LaunchKernels(key, out);
+  const JobBatchVariant* v = VariantFor(key, n);
+  if (!v || n < 1) return absl::InternalError("no job batch variant for " + std::to_string(n) + " jobs");
+  return v->exec->LaunchKernels(key, out);
 }
 
 absl::Status HipModelExecutor::ExecuteJobBatch(const SubgraphKey& key, int n) {

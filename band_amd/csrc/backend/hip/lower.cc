@@ -470,6 +470,10 @@ absl::Status HipModelExecutor::BuildLaunches(const HipModel& model, PreparedSubg
   if (allow_fusion_ && allow_chain_ && device_flag_ == DeviceFlag::kGPU) FuseChains(model, sg);
   if (allow_fusion_ && allow_irb_ && device_flag_ == DeviceFlag::kGPU) FuseBlocks(model, sg);
   if (allow_fusion_ && allow_layernorm_ && device_flag_ == DeviceFlag::kGPU) FuseLayerNorm(model, sg);
+  if (allow_fusion_ && allow_layernorm_ && fused_layernorm_f32_ == 1 && device_flag_ == DeviceFlag::kGPU) {
+    FuseLayerNormF32(model, sg);
+    FoldLayerNormQuant(model, sg);
+  }
   if (allow_fusion_ && fused_attention_ == 1 && device_flag_ == DeviceFlag::kGPU) FuseAttention(model, sg);
   if (allow_fusion_) FuseGlue(model, sg);
   if (allow_fusion_ && allow_group_ && device_flag_ == DeviceFlag::kGPU) RETURN_STATUS_IF(GroupConvs(sg));

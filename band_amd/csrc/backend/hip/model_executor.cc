@@ -91,6 +91,7 @@ std::unique_ptr<HipModelExecutor> HipModelExecutor::MakeLane() {
   lane->gpu_detection_ = gpu_detection_;
   lane->hybrid_conv_ = hybrid_conv_;
   lane->fused_attention_ = fused_attention_;
+  lane->fused_layernorm_f32_ = fused_layernorm_f32_;
   return lane;
 }
 
@@ -336,6 +337,7 @@ absl::Status HipModelExecutor::EnsureMeta(const HipModel& model) {
   if (std::strcmp(f, "nostage") == 0) no_stage_chain_ = true;  // A-B: without the stage forms
   if (!env::Autotune()) autotune_ = false;
   if (fused_attention_ < 0) fused_attention_ = env::FusedAttention() ? 1 : 0;
+  if (fused_layernorm_f32_ < 0) fused_layernorm_f32_ = env::FusedLayerNormF32() ? 1 : 0;
   return absl::OkStatus();
 }
 
@@ -659,6 +661,7 @@ absl::Status HipModelExecutor::EnqueueLaunch(const Launch& l) {
     case Launch::kBatchMatMulF32: rc = bh_batch_matmul_f32(&l.bmm, stream_); break;
     case Launch::kMeanRows: rc = bh_mean_rows(&l.mrows, stream_); break;
     case Launch::kLayerNorm: rc = bh_layernorm_i8(&l.ln, stream_); break;
+    case Launch::kLayerNormF32: rc = bh_layernorm_f32(&l.lnf, stream_); break;
     case Launch::kAttention: rc = bh_attention_i8(&l.attn, stream_); break;
     case Launch::kDynQuantRows: rc = bh_dynquant_rows(&l.dq, stream_); break;
     case Launch::kFcHybrid: rc = bh_fc_hybrid(&l.fch, stream_); break;

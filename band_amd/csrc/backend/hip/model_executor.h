@@ -62,7 +62,9 @@ struct Launch {
     kFcHybrid,        // hybrid FULLY_CONNECTED, second launch: int8 product, float epilogue (`fch`)
     kDynQuantItems,   // hybrid CONV_2D / DEPTHWISE_CONV_2D, first launch(es): each batch item quantised into the subgraph's scratch (`dqi`)
     kConvHybrid,      // hybrid CONV_2D: int8 implicit GEMM, float epilogue (`convh`)
-    kDwConvHybrid     // hybrid DEPTHWISE_CONV_2D (`convh`)
+    kDwConvHybrid,    // hybrid DEPTHWISE_CONV_2D (`convh`)
+    kLayerNormF32     // the ten ops of a float32 LayerNorm as one launch, with the row quantisation of the hybrid
+                      // FULLY_CONNECTEDs that read it (`lnf`; FuseLayerNormF32 / FoldLayerNormQuant; kGPU, opt-in)
   } kind;
   int op_index = -1;
   int out_tensor = -1;  // tensor this launch materialises (after epilogue fusions)
@@ -96,6 +98,7 @@ struct Launch {
   CpuMeanParams mean{};
   bh_mean_rows_params mrows{};
   bh_layernorm_params ln{};
+  bh_layernorm_f32_params lnf{};
   bh_argminmax_params argmm{};
   bh_resize_argminmax_params rzarg{};
   bh_reindex_params reindex{};
@@ -208,6 +211,8 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   // Kernel symbol of every launch of a prepared subgraph in program order
   // (host twins on a kCPU executor); needs no device
   absl::Status LaunchKernels(const SubgraphKey& key, std::vector<const char*>* out) const;
+  // the same for the job-batch variant that runs n jobs (n = 1: the subgraph itself)
+  absl::Status JobBatchLaunchKernels(const SubgraphKey& key, int n, std::vector<const char*>* out) const;
   // Device time of one subgraph pass (us) with `iters` passes issued back to
   // back (replayed hipGraph when captured, else the launch sequence): no host
   // gaps, H2D/D2H included.  The latency floor of ExecuteSubgraph's device side.
@@ -251,6 +256,11 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   // int8 RESIZE_BILINEAR -> ARG_MAX / ARG_MIN over channels as one launch (kGPU)
   void FuseGlue(const HipModel& model, PreparedSubgraph* sg);
   void FuseLayerNorm(const HipModel& model, PreparedSubgraph* sg);
+  // the ten float32 launches of a LayerNorm into one bh_layernorm_f32 launch
+  // (fused_layernorm_f32_), then the kDynQuantRows launches that read its
+  // result folded into that launch's epilogue
+  void FuseLayerNormF32(const HipModel& model, PreparedSubgraph* sg);
+  void FoldLayerNormQuant(const HipModel& model, PreparedSubgraph* sg);
   // int8 BATCH_MATMUL(adj_y) -> SOFTMAX -> BATCH_MATMUL into one bh_attention_i8
   // launch that reads and writes through the head TRANSPOSEs around it
   void FuseAttention(const HipModel& model, PreparedSubgraph* sg);
@@ -379,6 +389,11 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   // (-1: not yet; lanes and job-batch variants take their parent's): the
   // attention core as one launch on a kGPU executor.  Off by default.
   int fused_attention_ = -1;
+  // BAND_HIP_FUSED_LAYERNORM_F32=1, latched and inherited as fused_attention_
+  // is: a float32 LayerNorm as one launch on a kGPU executor, quantising its
+  // rows for the hybrid FULLY_CONNECTEDs that read it.  Off by default;
+  // BAND_HIP_FUSION=0 / nolayernorm turn it off.
+  int fused_layernorm_f32_ = -1;
   std::map<SubgraphKey, std::unique_ptr<PreparedSubgraph>> subgraphs_;
   int ordinal_ = -1;
   bh_stream_t stream_ = nullptr;

@@ -186,6 +186,9 @@ int bhx_cpu_reindex(const void* reindex_params);
  * order, up to cap; *n = the count.  Works on kCPU executors too. */
 int bhx_launch_kernels(bhx_executor* e, int model_id, int worker_id, uint64_t unit_mask, const char** out, int cap,
                        int* n);
+/* the same for the job-batch variant that runs `jobs` jobs (bhx_prepare_job_batches; jobs = 1: the subgraph itself) */
+int bhx_job_batch_launch_kernels(bhx_executor* e, int model_id, int worker_id, uint64_t unit_mask, int jobs,
+                                 const char** out, int cap, int* n);
 /* CpuConvGrouped, the kCPU worker's host twin of bh_conv2d_grouped_i8, over
  * host pointers: `grouped_params` is a bh_conv_grouped_params.  Refuses a
  * group count that does not divide both channel counts. */

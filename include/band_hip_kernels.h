@@ -565,6 +565,62 @@ int bh_layernorm_i8(const bh_layernorm_params* p, bh_stream_t s);
 const char* bh_layernorm_i8_kernel(const bh_layernorm_params* p);
 int bh_layernorm_i8_check(const bh_layernorm_params* p);
 
+/* The ten float32 ops a converter makes of a LayerNormalization over the last
+ * axis of x [rows][depth], as one launch (layernorm_f32_kernel), optionally
+ * followed in the same launch by the row quantisation of a hybrid
+ * FULLY_CONNECTED (bh_dynquant_rows below).  The rule is the ten ops in their
+ * order and operand order, each one IEEE float32 operation on a row x[0..C),
+ * no contraction, the divisions and the square root correctly rounded:
+ *   m = S(x) / C                      d_i = (x_i - m)^2  (two roundings)
+ *   v = S(d) / C      e = v + eps     r = 1 / sqrt(e)    (sqrt, then divide, as unary_f32_kernel's RSQRT)
+ *   g_i = r * gamma_i   a_i = x_i * g_i   b_i = m * g_i   c_i = beta_i - b_i   y_i = a_i + c_i
+ * The two-pass form is the rule; E[x^2] - m^2 is not.  Only the two sums S are
+ * reassociated, and their order is part of the rule - there is ONE order,
+ * whatever the number of rows, the row's place in its workgroup or the
+ * alignment of any pointer:
+ *   lane l of 64 owns elements 256 j + 4 l + k, j = 0 .. 3, k = 0 .. 3 (those
+ *   below C).  It starts from +0 and adds its own elements in ascending index
+ *   order (j outer, k inner).  The 64 lane sums then meet in an xor butterfly
+ *   over offsets 32, 16, 8, 4, 2, 1: at each offset o lane l replaces its value
+ *   by value[l] + value[l ^ o].  Float addition commutes, so every lane ends
+ *   with the same bits.
+ * (MEAN op by op sums a row in index order in one lane, so the fused result
+ * is not bit for bit the ten launches'; both lie within the same error bound
+ * of the real LayerNorm, tests/layernorm_f32_models.py derives it.)
+ * A wave owns a row and keeps it in registers from load to store: 16 values
+ * per lane, so depth <= BH_LAYERNORM_F32_MAX_DEPTH = 1024.  A 16-byte aligned
+ * row of a depth that is a multiple of 4 is read as float4; any other row is
+ * read element by element into the same lanes.
+ *   input [rows][depth], gamma [depth], beta [depth], eps the value of the ADD's constant;
+ *   output [rows][depth] float32, or NULL: y is not stored;
+ *   q [rows][depth], scale [rows], offset [rows], all set or all NULL: the
+ *   hybrid row rule (symmetric, or asymmetric when `asymmetric`) applied to
+ *   the float32 values y, through the device functions bh_dynquant_rows uses -
+ *   the bytes bh_dynquant_rows writes when run on the stored y.
+ * Refused (BH_EINVAL, bh_last_error names the reason): a null input, gamma or
+ * beta; neither output nor q set; q, scale, offset only partly set; rows or
+ * depth < 1; depth above the limit; rows >= 2^31; a float / int32 operand off
+ * its 4-byte boundary.  No LDS, no scratch, no atomics. */
+#define BH_LAYERNORM_F32_MAX_DEPTH 1024
+typedef struct bh_layernorm_f32_params {
+  long rows;
+  int depth;
+  float eps;
+  const float* input;
+  const float* gamma;
+  const float* beta;
+  float* output;    /* [rows][depth] or NULL */
+  int8_t* q;        /* [rows][depth] or NULL (then scale and offset are NULL too) */
+  float* scale;     /* [rows] */
+  int32_t* offset;  /* [rows] */
+  int asymmetric;
+} bh_layernorm_f32_params;
+int bh_layernorm_f32(const bh_layernorm_f32_params* p, bh_stream_t s);
+/* "layernorm_f32_kernel", or "" for parameters bh_layernorm_f32 refuses; static storage */
+const char* bh_layernorm_f32_kernel(const bh_layernorm_f32_params* p);
+/* the launcher's parameter check alone; pure host */
+int bh_layernorm_f32_check(const bh_layernorm_f32_params* p);
+
 /* ---- host-side operand packing (pure CPU, no device calls) -------------- */
 
 /* Pack OHWI conv weights ([out_c][k_h*k_w*in_c] bytes, signed or unsigned)
