@@ -1,5 +1,5 @@
 // Helpers shared by the HipModelExecutor translation units (model_executor.cc,
-// lower.cc, fusion.cc, job_batch.cc): small accessors and the float32 op set.
+// lower.cc, fusion.cc, fusion_transformer.cc, job_batch.cc): small accessors and the float32 op set.
 // The per-family Args functions are in lower_args.h.
 #pragma once
 
@@ -28,6 +28,9 @@ namespace ex {
 // set while PrepareJobBatches constructs a variant executor: a kCPU variant
 // then makes no host pool of its own (job_batch.cc)
 extern thread_local bool t_variant_ctor;
+
+// *ls without the launches a fusion pass marked dead (fusion.cc)
+void DropDead(std::vector<Launch>* ls, const std::vector<bool>& dead);
 
 constexpr size_t kAlign = 256;
 

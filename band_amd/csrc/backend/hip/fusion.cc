@@ -1,7 +1,9 @@
-// HipModelExecutor: fusion passes over the lowered launch program - grouped
-// independent convs, the inverted-residual block, the fused chains (every
-// form timed on the real buffers, decisions cached per geometry / device and
-// in BAND_HIP_TUNE_FILE), glue-op epilogue folds.  Split from model_executor.cc.
+// HipModelExecutor: what every fusion pass over the lowered launch program
+// shares - the privacy rule (KeptOutside / PrivateTensor / PrivateTo),
+// DropDead, TimeLaunches and the tune cache (BAND_HIP_TUNE_FILE) - and the
+// passes for convolutional models: GroupConvs, FuseBlocks, FuseChains (with
+// PackChainTile) and FuseGlue.  The transformer passes are in
+// fusion_transformer.cc; the residual ADD folds in lower.cc (TryFuseResidualAdd).
 #include "backend/hip/chain_form.h"
 #include "backend/hip/env.h"
 #include "backend/hip/executor_internal.h"
@@ -350,7 +352,6 @@ double HipModelExecutor::TimeLaunches(const std::vector<const Launch*>& ls, int 
 // bh_irb_i8 launch when the intermediates are private to the run.
 void HipModelExecutor::FuseBlocks(const HipModel& model, PreparedSubgraph* sg) {
   const TflModel& d = model.desc();
-  auto private_tensor = [&](int t, int only_consumer) { return PrivateTensor(d, *sg, t, only_consumer); };
   std::vector<Launch> out;
   const auto& L = sg->launches;
   for (size_t i = 0; i < L.size(); ++i) {
@@ -372,11 +373,11 @@ void HipModelExecutor::FuseBlocks(const HipModel& model, PreparedSubgraph* sg) {
     bool ok = dw.in_xor == 0 && dw.w_zp == 0 && dw.depth_multiplier == 1 && dw.k_h == 3 && dw.k_w == 3 &&
               dw.dil_h == 1 && dw.dil_w == 1 && dw.stride_h == dw.stride_w && pc.in_xor == 0 && pc.w_zp == 0 &&
               Is1x1S1(pc) && pc.input == dw.output &&
-              private_tensor(d.ops[D.op_index].outputs[0], P.op_index);
+              PrivateTensor(d, *sg, d.ops[D.op_index].outputs[0], P.op_index);
     if (ok && E) {
       const bh_conv_params& ec = E->conv;
       ok = ec.in_xor == 0 && ec.w_zp == 0 && Is1x1S1(ec) && !ec.residual && ec.output == dw.input &&
-           private_tensor(d.ops[E->op_index].outputs[0], D.op_index);
+           PrivateTensor(d, *sg, d.ops[E->op_index].outputs[0], D.op_index);
     }
     if (ok && pc.residual) {
       const void* x = E ? E->conv.input : dw.input;
@@ -420,14 +421,14 @@ void HipModelExecutor::FuseBlocks(const HipModel& model, PreparedSubgraph* sg) {
       bh_irb_params kq = q;
       if (tune_batch_ > 0) kq.batch = tune_batch_;  // a job-batch variant reuses its anchor's choice
       const std::string key = IrbKey(ordinal_, kq);
-      const std::optional<int> cached = autotune_ ? TuneLookup(key) : std::nullopt;
+      const std::optional<int> cached = opt_.autotune ? TuneLookup(key) : std::nullopt;
       int tile = cached.value_or(0);
       if (!cached) {
         double best_model = 1e300;
         int model_tile = 0;
         std::vector<const Launch*> unfused = {&D, &P};
         if (E) unfused.insert(unfused.begin(), E);
-        Fastest best(autotune_ ? TimeLaunches(unfused, 10) : -1.0);
+        Fastest best(opt_.autotune ? TimeLaunches(unfused, 10) : -1.0);
         const bool measured = best.us > 0;
         for (int t = 8; t >= 1; --t) {
           q.tile_h = q.tile_w = t;
@@ -499,23 +500,38 @@ bool HipModelExecutor::PackChainTile(bh_chain_params* q, std::shared_ptr<DeviceB
   return true;
 }
 
-// t is read by op `only_consumer` alone and needed by nobody outside the run
+// The one rule for "may this tensor disappear": somebody outside the launches
+// needs t stored - a view (no_fuse / extra_d2h), a later subgraph or the caller
+bool HipModelExecutor::KeptOutside(const TflModel& d, const PreparedSubgraph& sg, int t) const {
+  return sg.no_fuse.count(t) || sg.extra_d2h.count(t) ||
+         std::find(sg.outputs.begin(), sg.outputs.end(), t) != sg.outputs.end() ||
+         std::find(d.outputs.begin(), d.outputs.end(), t) != d.outputs.end();
+}
+
 bool HipModelExecutor::PrivateTensor(const TflModel& d, const PreparedSubgraph& sg, int t, int only_consumer) const {
-  if (t < 0 || consumers_[t].size() != 1 || consumers_[t][0] != only_consumer) return false;
-  if (sg.no_fuse.count(t) || sg.extra_d2h.count(t)) return false;
-  if (std::find(sg.outputs.begin(), sg.outputs.end(), t) != sg.outputs.end()) return false;
-  return std::find(d.outputs.begin(), d.outputs.end(), t) == d.outputs.end();
+  return t >= 0 && consumers_[t].size() == 1 && consumers_[t][0] == only_consumer && !KeptOutside(d, sg, t);
+}
+
+bool HipModelExecutor::PrivateTo(const TflModel& d, const PreparedSubgraph& sg, int t, const std::set<int>& ops) const {
+  if (t < 0 || KeptOutside(d, sg, t)) return false;
+  return std::all_of(consumers_[t].begin(), consumers_[t].end(), [&](int op) { return ops.count(op) > 0; });
+}
+
+void ex::DropDead(std::vector<Launch>* ls, const std::vector<bool>& dead) {
+  std::vector<Launch> out;
+  for (size_t i = 0; i < ls->size(); ++i)
+    if (!dead[i]) out.push_back((*ls)[i]);
+  ls->swap(out);
 }
 
 void HipModelExecutor::FuseChains(const HipModel& model, PreparedSubgraph* sg) {
   const TflModel& d = model.desc();
-  auto private_tensor = [&](int t, int only_consumer) { return PrivateTensor(d, *sg, t, only_consumer); };
   std::vector<Launch> out;
   const auto& L = sg->launches;
   for (size_t i = 0; i < L.size(); ++i) {
     const bool head = L[i].kind == Launch::kDwConv && i + 1 < L.size() && L[i + 1].kind == Launch::kConv &&
                       L[i + 1].conv.input == L[i].dw.output && !L[i].dw.out_table &&
-                      private_tensor(L[i].out_tensor, L[i + 1].op_index);
+                      PrivateTensor(d, *sg, L[i].out_tensor, L[i + 1].op_index);
     if (!head) {
       out.push_back(L[i]);
       continue;
@@ -536,7 +552,7 @@ void HipModelExecutor::FuseChains(const HipModel& model, PreparedSubgraph* sg) {
     if (P2) {
       c3.has_pw2 = 1;
       c3.pw2 = P2->conv;
-      if (private_tensor(P1.out_tensor, P2->op_index)) c3.pw1.output = nullptr;
+      if (PrivateTensor(d, *sg, P1.out_tensor, P2->op_index)) c3.pw1.output = nullptr;
       ok3 = bh_chain_lds_bytes(&c3) > 0;
     }
     const bool ok2 = bh_chain_lds_bytes(&c2) > 0;
@@ -558,26 +574,26 @@ void HipModelExecutor::FuseChains(const HipModel& model, PreparedSubgraph* sg) {
     std::snprintf(key, sizeof(key), "ch%d:%d:%d:%dx%dx%d:s%dd%d:%d:%d:%d:%d:f%d%d%d%d", kChainTuneVersion, ordinal_,
                   tune_batch_ > 0 ? tune_batch_ : D.dw.batch, D.dw.in_h, D.dw.in_w, D.dw.in_c, D.dw.stride_h, D.dw.dil_h,
                   P1.conv.out_c, P1.conv.residual ? 1 : 0, ok3 ? c3.pw2.out_c : 0, ok3 && c3.pw1.output ? 1 : 0,
-                  no_tile_chain_, no_deep_chain_, no_split_chain_, no_stage_chain_);
-    const bool forced = forced_chain_ != ForcedChain::kNone;
-    const std::optional<int> cached = autotune_ && !forced ? TuneLookup(key) : std::nullopt;
+                  opt_.no_tile_chain, opt_.no_deep_chain, opt_.no_split_chain, opt_.no_stage_chain);
+    const bool forced = opt_.forced_chain != ForcedChain::kNone;
+    const std::optional<int> cached = opt_.autotune && !forced ? TuneLookup(key) : std::nullopt;
     ChainForm form = kUnfused;
     if (forced) {
-      form = ForcedForm(forced_chain_, ok3 ? c3 : c2);
+      form = ForcedForm(opt_.forced_chain, ok3 ? c3 : c2);
     } else if (cached) {
       Decode(*cached, &form);  // an integer no form encodes to (another kernel tree's tune file): unfused
     } else {
       std::vector<const Launch*> base = {&D, &P1};
       if (ok3) base.push_back(P2);
       double u = -1.0, u_p2 = 0.0;
-      if (autotune_) {
+      if (opt_.autotune) {
         u = TimeLaunches(base, 10);
         if (ok3) u_p2 = TimeLaunches({P2}, 10);
       }
       const bool measured = u > 0 && u_p2 >= 0;
       Fastest best(u);
       ForEachChainForm([&](ChainForm f) {
-        if (!measured || FilteredOut(f, no_tile_chain_, no_deep_chain_, no_split_chain_, no_stage_chain_)) return;
+        if (!measured || FilteredOut(f, opt_.no_tile_chain, opt_.no_deep_chain, opt_.no_split_chain, opt_.no_stage_chain)) return;
         for (f.launches = 3; f.launches >= 2; --f.launches) {
           Launch F;
           F.kind = Launch::kChain;
@@ -652,15 +668,11 @@ const void** TableSlot(Launch& l) {
 
 void HipModelExecutor::FuseGlue(const HipModel& model, PreparedSubgraph* sg) {
   const TflModel& d = model.desc();
-  auto in_outputs = [&](int t) {
-    return std::find(sg->outputs.begin(), sg->outputs.end(), t) != sg->outputs.end() ||
-           std::find(d.outputs.begin(), d.outputs.end(), t) != d.outputs.end();
-  };
   // t reaches op `to` through RESHAPE / SQUEEZE aliases only, every tensor on
   // the way read by nothing else and needed by nobody outside; collects them
   auto private_chain = [&](int t, int to, std::vector<int>* chain) {
     while (t >= 0) {
-      if (consumers_[t].size() != 1 || in_outputs(t) || sg->no_fuse.count(t) || sg->extra_d2h.count(t)) return false;
+      if (consumers_[t].size() != 1 || KeptOutside(d, *sg, t)) return false;
       chain->push_back(t);
       const int c = consumers_[t][0];
       if (c == to) return true;
@@ -756,7 +768,7 @@ void HipModelExecutor::FuseGlue(const HipModel& model, PreparedSubgraph* sg) {
   // one resize_bilinear_argminmax_kernel launch, the resized tensor never
   // stored (kGPU; the kCPU worker runs the two host kernels).  The launcher
   // refuses geometries whose blended rows do not fit LDS: those keep both.
-  for (size_t i = 0; allow_argmax_ && device_flag_ == DeviceFlag::kGPU && i < sg->launches.size(); ++i) {
+  for (size_t i = 0; opt_.allow_argmax && device_flag_ == DeviceFlag::kGPU && i < sg->launches.size(); ++i) {
     Launch& A = sg->launches[i];
     if (A.kind != Launch::kArgMinMax || A.argmm.in_type != BH_ARG_I8 || A.argmm.inner != 1) continue;
     int j = -1;
@@ -769,494 +781,25 @@ void HipModelExecutor::FuseGlue(const HipModel& model, PreparedSubgraph* sg) {
     if (A.argmm.axis_len != R.rbil.channels ||
         A.argmm.outer != static_cast<long>(R.rbil.batch) * R.rbil.out_h * R.rbil.out_w)
       continue;
-    if (t < 0 || consumers_[t].size() != 1 || consumers_[t][0] != A.op_index || in_outputs(t) ||
-        sg->no_fuse.count(t) || sg->extra_d2h.count(t))
-      continue;
+    if (!PrivateTensor(d, *sg, t, A.op_index)) continue;
     bh_resize_argminmax_params q{};
     q.rz = R.rbil;
     q.rz.output = A.argmm.output;
     q.is_min = A.argmm.is_min;
     q.out_bytes = A.argmm.out_bytes;
     if (bh_resize_bilinear_argminmax_i8_ok(&q) != 0) continue;
+    // reads the small map, writes the indices; the resized tensor is gone
+    A.alg_bytes = static_cast<double>(R.rbil.batch) * R.rbil.in_h * R.rbil.in_w * R.rbil.channels +
+                  static_cast<double>(A.argmm.outer) * q.out_bytes;
     A.kind = Launch::kResizeArgMinMax;
     A.rzarg = q;
     A.kernel = "resize_bilinear_argminmax_kernel";
-    // reads the small map, writes the indices; the resized tensor is gone
-    A.alg_bytes = static_cast<double>(R.rbil.batch) * R.rbil.in_h * R.rbil.in_w * R.rbil.channels +
-                  static_cast<double>(A.argmm.outer) * A.argmm.out_bytes;
     sg->fused_tensors.insert(t);
     sg->fused_ops.insert(R.op_index);
     dead[j] = true;
   }
-  std::vector<Launch> out;
-  for (size_t i = 0; i < sg->launches.size(); ++i)
-    if (!dead[i]) out.push_back(sg->launches[i]);
-  sg->launches.swap(out);
+  DropDead(&sg->launches, dead);
 }
-
-// The ten ops a converter makes of an int8 LayerNormalization over the last
-// axis, in the order and with the operand order the synthesiser emits:
-//   m = MEAN(x)  d = SQUARED_DIFFERENCE(x, m)  v = MEAN(d)  e = ADD(v, eps)
-//   r = RSQRT(e)  g = MUL(r, gamma)  a = MUL(x, g)  b = MUL(m, g)
-//   c = SUB(beta, b)  y = ADD(a, c)
-// on x [..., C], row statistics [..., 1] and constants gamma / beta [C], eps
-// [1].  Op by op that is ten launches at the dispatch floor; matched, they
-// become one layernorm_i8_kernel launch that carries the ten parameter blocks
-// as they were lowered, so it stores the same bytes.  Ten consecutive launches
-// qualify when every intermediate is read only inside the pattern, is no
-// subgraph or model output, is not viewed (no_fuse / extra_d2h), and the
-// launcher's check takes the row (C <= BH_LAYERNORM_MAX_DEPTH).
-void HipModelExecutor::FuseLayerNorm(const HipModel& model, PreparedSubgraph* sg) {
-  const TflModel& d = model.desc();
-  static const int kPattern[10] = {kTflMean, kTflSquaredDifference, kTflMean, kTflAdd, kTflRsqrt,
-                                   kTflMul,  kTflMul,               kTflMul,  kTflSub, kTflAdd};
-  static const Launch::Kind kKinds[10] = {Launch::kMeanRows, Launch::kEltwise, Launch::kMeanRows, Launch::kEltwise,
-                                          Launch::kLutU8,    Launch::kEltwise, Launch::kEltwise,  Launch::kEltwise,
-                                          Launch::kEltwise,  Launch::kEltwise};
-  auto in_outputs = [&](int t) {
-    return std::find(sg->outputs.begin(), sg->outputs.end(), t) != sg->outputs.end() ||
-           std::find(d.outputs.begin(), d.outputs.end(), t) != d.outputs.end();
-  };
-  std::vector<Launch> out;
-  for (size_t i = 0; i < sg->launches.size(); ++i) {
-    const std::vector<Launch>& ls = sg->launches;
-    bool ok = i + 10 <= ls.size();
-    const TflOperator* o[10] = {};
-    for (int k = 0; ok && k < 10; ++k) {
-      const Launch& l = ls[i + k];
-      ok = l.kind == kKinds[k] && l.op_index >= 0 && d.ops[l.op_index].builtin == kPattern[k] &&
-           d.ops[l.op_index].outputs.size() == 1 && l.out_tensor == d.ops[l.op_index].outputs[0];
-      if (ok) o[k] = &d.ops[l.op_index];
-    }
-    if (!ok) {
-      out.push_back(ls[i]);
-      continue;
-    }
-    auto in = [&](int k, int j) { return o[k]->inputs[j]; };
-    auto res = [&](int k) { return o[k]->outputs[0]; };
-    const int x = in(0, 0), m = res(0), dd = res(1), v = res(2), e = res(3), r = res(4), g = res(5), a = res(6),
-              b = res(7), c = res(8);
-    const int eps = in(3, 1), gamma = in(5, 1), beta = in(8, 0);
-    ok = in(1, 0) == x && in(1, 1) == m && in(2, 0) == dd && in(3, 0) == v && in(4, 0) == e && in(5, 0) == r &&
-         in(6, 0) == x && in(6, 1) == g && in(7, 0) == m && in(7, 1) == g && in(8, 1) == b && in(9, 0) == a &&
-         in(9, 1) == c && eps >= 0 && gamma >= 0 && beta >= 0;
-    const TflTensor& tx = d.tensors[x];
-    const long depth = ok && !tx.shape.empty() ? tx.shape.back() : 0;
-    ok = ok && depth >= 1 && tx.type == DataType::kInt8 && d.tensors[res(9)].shape == tx.shape &&
-         d.tensors[eps].is_const() && d.tensors[eps].num_elements() == 1 && d.tensors[eps].data_size >= 1 &&
-         d.tensors[gamma].is_const() && d.tensors[gamma].shape == std::vector<int>{static_cast<int>(depth)} &&
-         d.tensors[beta].is_const() && d.tensors[beta].shape == std::vector<int>{static_cast<int>(depth)};
-    // the row statistics hold one value per row, the per-element tensors the input's shape
-    for (int t : {m, v, e, r})
-      ok = ok && d.tensors[t].num_elements() * static_cast<size_t>(depth) == tx.num_elements();
-    for (int t : {dd, g, a, b, c}) ok = ok && d.tensors[t].shape == tx.shape;
-    const std::set<int> inside = {ls[i].op_index,     ls[i + 1].op_index, ls[i + 2].op_index, ls[i + 3].op_index,
-                                  ls[i + 4].op_index, ls[i + 5].op_index, ls[i + 6].op_index, ls[i + 7].op_index,
-                                  ls[i + 8].op_index, ls[i + 9].op_index};
-    for (int t : {m, dd, v, e, r, g, a, b, c}) {
-      ok = ok && !in_outputs(t) && !sg->no_fuse.count(t) && !sg->extra_d2h.count(t);
-      for (int consumer : consumers_[t]) ok = ok && inside.count(consumer) > 0;
-    }
-    Launch F;
-    if (ok) {
-      F.kind = Launch::kLayerNorm;
-      F.op_index = ls[i].op_index;
-      F.out_tensor = res(9);
-      bh_layernorm_params& p = F.ln;
-      p = bh_layernorm_params{};
-      p.rows = ls[i].mrows.rows;
-      p.depth = static_cast<int>(depth);
-      p.mean_x = ls[i].mrows;
-      p.sqdiff = ls[i + 1].elt;
-      p.mean_d = ls[i + 2].mrows;
-      p.add_eps = ls[i + 3].elt;
-      p.rsqrt_table = ls[i + 4].table;
-      p.mul_gamma = ls[i + 5].elt;
-      p.mul_x = ls[i + 6].elt;
-      p.mul_m = ls[i + 7].elt;
-      p.sub_beta = ls[i + 8].elt;
-      p.add_out = ls[i + 9].elt;
-      p.eps_q = static_cast<int8_t>(d.tensors[eps].data[0]);
-      p.input = ls[i].mrows.input;
-      p.gamma = ls[i + 5].elt.b;
-      p.beta = ls[i + 8].elt.a;
-      p.output = ls[i + 9].elt.out;
-      ok = p.mean_d.rows == p.rows && bh_layernorm_i8_check(&p) == 0;
-    }
-    if (!ok) {
-      out.push_back(ls[i]);
-      continue;
-    }
-    F.kernel = bh_layernorm_i8_kernel(&F.ln);
-    F.alg_bytes = 2.0 * static_cast<double>(tx.num_elements()) + 2.0 * depth + 256.0;
-    for (int k = 1; k < 10; ++k) sg->fused_ops.insert(ls[i + k].op_index);
-    for (int t : {m, dd, v, e, r, g, a, b, c}) sg->fused_tensors.insert(t);
-    out.push_back(F);
-    i += 9;
-  }
-  sg->launches.swap(out);
-}
-
-// The same ten ops in float32 (FGraph.layer_norm; BAND_HIP_FUSED_LAYERNORM_F32=1,
-// kGPU): kMean, kEltwiseF32 (SQDIFF), kMean, kEltwiseF32 (ADD), kUnaryF32
-// (RSQRT), kEltwiseF32 x 5 (MUL, MUL, MUL, SUB, ADD) with FuseLayerNorm's
-// operand wiring become one layernorm_f32_kernel launch.  They qualify when
-// every tensor is float32, the MEANs run over the last axis with keep_dims,
-// every fused activation is NONE, gamma and beta are float32 constants [C],
-// eps is a float32 constant of one element (its value is taken here), every
-// intermediate is private to the pattern, no output and not viewed, and the
-// launcher's check takes the row (C <= BH_LAYERNORM_F32_MAX_DEPTH).  The
-// kernel's two row sums have an order of their own (band_hip_kernels.h), so
-// its result lies within the ops' error bound but is not their bits.
-//   A model whose constants are fp16 behind DEQUANTIZE ops lowers a
-// DEQUANTIZE launch between the MEAN and the ADD of eps (and its gamma / beta
-// are no constants): it never presents the ten consecutive launches and keeps
-// them.
-void HipModelExecutor::FuseLayerNormF32(const HipModel& model, PreparedSubgraph* sg) {
-  const TflModel& d = model.desc();
-  static const int kPattern[10] = {kTflMean, kTflSquaredDifference, kTflMean, kTflAdd, kTflRsqrt,
-                                   kTflMul,  kTflMul,               kTflMul,  kTflSub, kTflAdd};
-  static const Launch::Kind kKinds[10] = {Launch::kMean,       Launch::kEltwiseF32, Launch::kMean,       Launch::kEltwiseF32,
-                                          Launch::kUnaryF32,   Launch::kEltwiseF32, Launch::kEltwiseF32, Launch::kEltwiseF32,
-                                          Launch::kEltwiseF32, Launch::kEltwiseF32};
-  static const int kElt[10] = {-1, BH_ELTF_SQDIFF, -1, BH_ELTF_ADD, -1, BH_ELTF_MUL, BH_ELTF_MUL, BH_ELTF_MUL, BH_ELTF_SUB,
-                               BH_ELTF_ADD};
-  auto in_outputs = [&](int t) {
-    return std::find(sg->outputs.begin(), sg->outputs.end(), t) != sg->outputs.end() ||
-           std::find(d.outputs.begin(), d.outputs.end(), t) != d.outputs.end();
-  };
-  const float inf = std::numeric_limits<float>::infinity();
-  std::vector<Launch> out;
-  for (size_t i = 0; i < sg->launches.size(); ++i) {
-    const std::vector<Launch>& ls = sg->launches;
-    bool ok = i + 10 <= ls.size();
-    const TflOperator* o[10] = {};
-    for (int k = 0; ok && k < 10; ++k) {
-      const Launch& l = ls[i + k];
-      ok = l.kind == kKinds[k] && l.op_index >= 0 && d.ops[l.op_index].builtin == kPattern[k] &&
-           d.ops[l.op_index].outputs.size() == 1 && l.out_tensor == d.ops[l.op_index].outputs[0] &&
-           d.ops[l.op_index].inputs.size() >= (k == 4 ? 1u : 2u);
-      if (ok && kElt[k] >= 0) ok = l.eltf.kind == kElt[k] && l.eltf.act_min == -inf && l.eltf.act_max == inf;
-      if (ok && k == 4) ok = l.unary_kind == BH_UNARY_RSQRT;
-      if (ok) o[k] = &d.ops[l.op_index];
-    }
-    if (!ok) {
-      out.push_back(ls[i]);
-      continue;
-    }
-    auto in = [&](int k, int j) { return o[k]->inputs[j]; };
-    auto res = [&](int k) { return o[k]->outputs[0]; };
-    const int x = in(0, 0), m = res(0), dd = res(1), v = res(2), e = res(3), r = res(4), g = res(5), a = res(6),
-              b = res(7), c = res(8), y = res(9);
-    const int eps = in(3, 1), gamma = in(5, 1), beta = in(8, 0);
-    ok = x >= 0 && in(1, 0) == x && in(1, 1) == m && in(2, 0) == dd && in(3, 0) == v && in(4, 0) == e &&
-         in(5, 0) == r && in(6, 0) == x && in(6, 1) == g && in(7, 0) == m && in(7, 1) == g && in(8, 1) == b &&
-         in(9, 0) == a && in(9, 1) == c && eps >= 0 && gamma >= 0 && beta >= 0;
-    if (!ok) {
-      out.push_back(ls[i]);
-      continue;
-    }
-    const TflTensor& tx = d.tensors[x];
-    const long depth = !tx.shape.empty() ? tx.shape.back() : 0;
-    ok = depth >= 1 && d.tensors[y].shape == tx.shape && d.tensors[eps].is_const() &&
-         d.tensors[eps].num_elements() == 1 && d.tensors[eps].data_size >= 4 && d.tensors[gamma].is_const() &&
-         d.tensors[gamma].shape == std::vector<int>{static_cast<int>(depth)} && d.tensors[beta].is_const() &&
-         d.tensors[beta].shape == std::vector<int>{static_cast<int>(depth)};
-    for (int t : {x, m, dd, v, e, r, g, a, b, c, y, eps, gamma, beta}) ok = ok && d.tensors[t].type == DataType::kFloat32;
-    // the row statistics keep the input's rank with a last axis of 1 (keep_dims), the per-element tensors its shape
-    std::vector<int> stat = tx.shape;
-    if (!stat.empty()) stat.back() = 1;
-    for (int t : {m, v, e, r}) ok = ok && d.tensors[t].shape == stat;
-    for (int t : {dd, g, a, b, c}) ok = ok && d.tensors[t].shape == tx.shape;
-    // MEAN over the last axis alone: rows x depth x 1
-    for (int k : {0, 2}) {
-      const CpuMeanParams& q = ls[i + k].mean;
-      ok = ok && q.type == 0 && q.inner == 1 && q.reduce == depth &&
-           q.outer * depth == static_cast<long>(tx.num_elements());
-    }
-    std::set<int> inside;
-    for (int k = 0; k < 10; ++k) inside.insert(ls[i + k].op_index);
-    for (int t : {m, dd, v, e, r, g, a, b, c}) {
-      ok = ok && !in_outputs(t) && !sg->no_fuse.count(t) && !sg->extra_d2h.count(t);
-      for (int consumer : consumers_[t]) ok = ok && inside.count(consumer) > 0;
-    }
-    Launch F;
-    if (ok) {
-      F.kind = Launch::kLayerNormF32;
-      F.op_index = ls[i].op_index;
-      F.out_tensor = y;
-      bh_layernorm_f32_params& p = F.lnf;
-      p = bh_layernorm_f32_params{};
-      p.rows = ls[i].mean.outer;
-      p.depth = static_cast<int>(depth);
-      std::memcpy(&p.eps, d.tensors[eps].data, sizeof(float));
-      p.input = static_cast<const float*>(ls[i].mean.input);
-      p.gamma = ls[i + 5].eltf.b;
-      p.beta = ls[i + 8].eltf.a;
-      p.output = ls[i + 9].eltf.out;
-      ok = ls[i + 6].eltf.a == p.input && bh_layernorm_f32_check(&p) == 0;
-    }
-    if (!ok) {
-      out.push_back(ls[i]);
-      continue;
-    }
-    F.kernel = bh_layernorm_f32_kernel(&F.lnf);
-    F.alg_bytes = 8.0 * static_cast<double>(tx.num_elements()) + 8.0 * depth;
-    for (int k = 1; k < 10; ++k) sg->fused_ops.insert(ls[i + k].op_index);
-    for (int t : {m, dd, v, e, r, g, a, b, c}) sg->fused_tensors.insert(t);
-    out.push_back(F);
-    i += 9;
-  }
-  sg->launches.swap(out);
-}
-
-// The row quantisation of the hybrid FULLY_CONNECTEDs that read a fused
-// float32 LayerNorm's result y, folded into that launch: the finished row is
-// quantised once, in registers, for all of them.  Per fused launch: the
-// kDynQuantRows launches whose op reads tensor y itself, over its rows x
-// depth, in one form (the first reader's; a reader of the other form keeps its
-// launch) are dropped, the fused launch writes q / scale / offset into the
-// first one's scratch, and every such op's kFcHybrid block reads that scratch.
-// y itself is then stored only when something still reads it: an op whose
-// launch was not folded, an output, a view (no_fuse / extra_d2h).  Otherwise
-// it joins fused_tensors, so a later view re-lowers with y materialised.
-void HipModelExecutor::FoldLayerNormQuant(const HipModel& model, PreparedSubgraph* sg) {
-  const TflModel& d = model.desc();
-  std::vector<Launch>& ls = sg->launches;
-  std::vector<bool> dead(ls.size(), false);
-  for (size_t i = 0; i < ls.size(); ++i) {
-    if (ls[i].kind != Launch::kLayerNormF32 || ls[i].lnf.q) continue;
-    bh_layernorm_f32_params& p = ls[i].lnf;
-    const int y = ls[i].out_tensor;
-    std::set<int> folded;  // ops whose quantisation this launch takes over
-    const bh_dynquant_params* first = nullptr;
-    for (size_t j = i + 1; j < ls.size(); ++j) {
-      const Launch& q = ls[j];
-      if (q.kind != Launch::kDynQuantRows || dead[j] || q.op_index < 0) continue;
-      const TflOperator& op = d.ops[q.op_index];
-      if (op.inputs.empty() || op.inputs[0] != y || q.dq.input != p.output || q.dq.rows != p.rows ||
-          q.dq.depth != p.depth)
-        continue;
-      if (first && (q.dq.asymmetric != 0) != (first->asymmetric != 0)) continue;
-      if (!first) first = &q.dq;
-      folded.insert(q.op_index);
-      dead[j] = true;
-    }
-    if (!first) continue;
-    p.q = first->q;
-    p.scale = first->scale;
-    p.offset = first->offset;
-    p.asymmetric = first->asymmetric;
-    for (Launch& l : ls)
-      if (l.kind == Launch::kFcHybrid && folded.count(l.op_index)) {
-        l.fch.q = p.q;
-        l.fch.in_scale = p.scale;
-        l.fch.in_offset = p.offset;
-      }
-    bool needed = sg->no_fuse.count(y) || sg->extra_d2h.count(y) ||
-                  std::find(sg->outputs.begin(), sg->outputs.end(), y) != sg->outputs.end() ||
-                  std::find(d.outputs.begin(), d.outputs.end(), y) != d.outputs.end();
-    for (int consumer : consumers_[y]) needed = needed || !folded.count(consumer);
-    ls[i].alg_bytes += 1.0 * static_cast<double>(p.rows) * p.depth + 8.0 * p.rows;
-    if (!needed) {
-      ls[i].alg_bytes -= 4.0 * static_cast<double>(p.rows) * p.depth;
-      p.output = nullptr;
-      sg->fused_tensors.insert(y);
-    }
-    if (bh_layernorm_f32_check(&p) == 0) ls[i].kernel = bh_layernorm_f32_kernel(&p);
-  }
-  std::vector<Launch> out;
-  for (size_t i = 0; i < ls.size(); ++i)
-    if (!dead[i]) out.push_back(ls[i]);
-  sg->launches.swap(out);
-}
-
-// The attention core of a converted int8 block, three consecutive launches
-//   scores = BATCH_MATMUL(q, k, adj_y)   p = SOFTMAX(scores)   ctx = BATCH_MATMUL(p, v)
-// becomes one attention_i8_kernel launch (BAND_HIP_FUSED_ATTENTION=1, kGPU)
-// that carries the three parameter blocks as they were lowered, so it stores
-// the same bytes.  They qualify when scores and p are int8, are read only
-// inside the pattern (scores by the SOFTMAX, p by the second product as its
-// lhs), are no subgraph or model output and are not viewed (no_fuse /
-// extra_d2h), the softmax runs over the scores' last axis, the first product
-// has a K-contiguous rhs and no adj_x, the second no adjoint, and the
-// launcher's check takes the result (keys <= 1024, head_dim, out_dim <= 128).
-//   Head TRANSPOSEs.  q, k or v produced by a kReindex launch that is a
-// TRANSPOSE leaving the last axis in place, whose output nothing else reads
-// and nobody needs materialised, is read through strides from the TRANSPOSE's
-// input and that launch is dropped; a TRANSPOSE of the same kind that is
-// ctx's only reader is absorbed into the output strides, and the fused launch
-// then writes the TRANSPOSE's output tensor.  An operand that cannot be
-// absorbed stays the dense tensor it was.
-void HipModelExecutor::FuseAttention(const HipModel& model, PreparedSubgraph* sg) {
-  const TflModel& d = model.desc();
-  std::vector<Launch>& ls = sg->launches;
-  std::vector<bool> dead(ls.size(), false);
-  // op is a TRANSPOSE of rank 2 .. 4 that leaves the last axis in place
-  auto head_perm = [&](const TflOperator& op, std::vector<int64_t>* perm) {
-    if (op.builtin != kTflTranspose || op.inputs.size() < 2 || op.inputs[0] < 0 || op.inputs[1] < 0 ||
-        op.outputs.size() != 1)
-      return false;
-    const size_t r = d.tensors[op.inputs[0]].shape.size();
-    if (r < 2 || r > 4 || !ConstInts(d.tensors[op.inputs[1]], perm) || perm->size() != r) return false;
-    std::vector<bool> seen(r, false);
-    for (int64_t p : *perm) {
-      if (p < 0 || p >= static_cast<int64_t>(r) || seen[p]) return false;
-      seen[p] = true;
-    }
-    return perm->back() == static_cast<int64_t>(r) - 1;
-  };
-  auto dense_strides = [](const std::vector<int>& shape) {
-    std::vector<int64_t> s(shape.size(), 1);
-    for (int k = static_cast<int>(shape.size()) - 2; k >= 0; --k) s[k] = s[k + 1] * shape[k + 1];
-    return s;
-  };
-  // a matrix operand of dims `dm` walked at strides `st`: its batch strides (0 for a dim of 1) and row stride
-  auto operand = [](const std::vector<int64_t>& dm, const std::vector<int64_t>& st, int64_t* bstride, int64_t* row) {
-    const int r = static_cast<int>(dm.size());
-    bstride[0] = bstride[1] = 0;
-    for (int k = 0; k < r - 2; ++k) bstride[2 - (r - 2) + k] = dm[k] == 1 ? 0 : st[k];
-    *row = st[r - 2];
-  };
-  // operand tensor t of op `reader`, at `ptr`: when a head TRANSPOSE launch made it for that op alone, the launch
-  // (its index) and the strides that read the TRANSPOSE's input instead
-  auto absorb_in = [&](size_t before, int t, int reader, const void* ptr, int64_t* bstride, int64_t* row,
-                       const void** src) -> int {
-    for (size_t j = before; j-- > 0;) {
-      const Launch& r = ls[j];
-      if (dead[j] || r.kind != Launch::kReindex || r.reindex.output != ptr || r.out_tensor != t) continue;
-      const TflOperator& op = d.ops[r.op_index];
-      std::vector<int64_t> perm;
-      if (!head_perm(op, &perm) || op.outputs[0] != t || !PrivateTensor(d, *sg, t, reader)) return -1;
-      const TflTensor& x = d.tensors[op.inputs[0]];
-      const std::vector<int64_t> xs = dense_strides(x.shape);
-      std::vector<int64_t> dm, st;
-      for (int64_t p : perm) {
-        dm.push_back(x.shape[p]);
-        st.push_back(xs[p]);
-      }
-      operand(dm, st, bstride, row);
-      *src = r.reindex.input;
-      return static_cast<int>(j);
-    }
-    return -1;
-  };
-  for (size_t i = 0; i + 2 < ls.size(); ++i) {
-    const Launch &A = ls[i], &S = ls[i + 1], &B = ls[i + 2];
-    if (A.kind != Launch::kBatchMatMul || S.kind != Launch::kSoftmax || B.kind != Launch::kBatchMatMul) continue;
-    if (A.op_index < 0 || S.op_index < 0 || B.op_index < 0) continue;
-    const TflOperator &oa = d.ops[A.op_index], &os = d.ops[S.op_index], &ob = d.ops[B.op_index];
-    if (oa.builtin != kTflBatchMatMul || os.builtin != kTflSoftmax || ob.builtin != kTflBatchMatMul) continue;
-    auto adj = [](const TflOperator& op, int k) { return op.options.valid() && op.options.Int8(k, 0) != 0; };
-    if (adj(oa, 0) || !adj(oa, 1) || adj(ob, 0) || adj(ob, 1)) continue;
-    const int sc = oa.outputs[0], pr = os.outputs[0], ctx = ob.outputs[0];
-    if (os.inputs[0] != sc || ob.inputs[0] != pr || ob.inputs[1] == pr || A.out_tensor != sc || S.out_tensor != pr ||
-        B.out_tensor != ctx)
-      continue;
-    if (d.tensors[sc].type != DataType::kInt8 || d.tensors[pr].type != DataType::kInt8) continue;
-    if (!PrivateTensor(d, *sg, sc, S.op_index) || !PrivateTensor(d, *sg, pr, B.op_index)) continue;
-    const bh_batch_matmul_params &a = A.bmm, &b = B.bmm;
-    const bh_softmax_params& s = S.softmax;
-    if (s.input != a.out || s.output != b.lhs || !s.is_signed || s.depth != a.n ||
-        s.rows != static_cast<long>(a.batch[0]) * a.batch[1] * a.m)
-      continue;
-    if (b.batch[0] != a.batch[0] || b.batch[1] != a.batch[1] || b.m != a.m || b.k != a.n) continue;
-    Launch F;
-    F.kind = Launch::kAttention;
-    F.op_index = A.op_index;
-    F.out_tensor = ctx;
-    bh_attention_params& p = F.attn;
-    p = bh_attention_params{};
-    p.batch[0] = a.batch[0];
-    p.batch[1] = a.batch[1];
-    p.rows = a.m;
-    p.keys = a.n;
-    p.head_dim = a.k;
-    p.out_dim = b.n;
-    p.q_inner_stride = p.k_inner_stride = p.v_inner_stride = p.out_inner_stride = 1;
-    for (int k = 0; k < 2; ++k) {
-      p.q_bstride[k] = a.lhs_bstride[k];
-      p.k_bstride[k] = a.rhs_bstride[k];
-      p.v_bstride[k] = b.rhs_bstride[k];
-    }
-    p.q_row_stride = a.lhs_row_stride;
-    p.k_row_stride = a.rhs_col_stride;
-    p.v_row_stride = b.rhs_k_stride;
-    p.out_bstride[1] = static_cast<int64_t>(b.m) * b.n;
-    p.out_bstride[0] = p.out_bstride[1] * b.batch[1];
-    p.out_row_stride = b.n;
-    p.qk = bh_attention_quant{a.lhs_zp, a.rhs_zp, a.out_zp, a.mult, a.shift, a.requant_fast};
-    p.pv = bh_attention_quant{b.lhs_zp, b.rhs_zp, b.out_zp, b.mult, b.shift, b.requant_fast};
-    p.table = s.table;
-    p.sm_out_scale = s.out_scale;
-    p.sm_out_zp = s.out_zp;
-    p.q = a.lhs;
-    p.k = a.rhs;
-    p.v = b.rhs;
-    p.out = b.out;
-    // the head TRANSPOSEs around the pattern
-    const int jq = absorb_in(i, oa.inputs[0], A.op_index, a.lhs, p.q_bstride, &p.q_row_stride, &p.q);
-    const int jk = oa.inputs[1] == oa.inputs[0] ? -1
-                                                : absorb_in(i, oa.inputs[1], A.op_index, a.rhs, p.k_bstride, &p.k_row_stride, &p.k);
-    const int jv = ob.inputs[1] == oa.inputs[0] || ob.inputs[1] == oa.inputs[1]
-                       ? -1
-                       : absorb_in(i, ob.inputs[1], B.op_index, b.rhs, p.v_bstride, &p.v_row_stride, &p.v);
-    int jo = -1;
-    for (size_t j = i + 3; j < ls.size() && jo < 0; ++j) {
-      const Launch& r = ls[j];
-      if (r.kind != Launch::kReindex || r.reindex.input != b.out) continue;
-      const TflOperator& op = d.ops[r.op_index];
-      std::vector<int64_t> perm;
-      if (!head_perm(op, &perm) || op.inputs[0] != ctx || r.out_tensor != op.outputs[0] ||
-          !PrivateTensor(d, *sg, ctx, r.op_index))
-        break;
-      // ctx axis perm[k] is the TRANSPOSE's output axis k
-      const std::vector<int64_t> ys = dense_strides(d.tensors[op.outputs[0]].shape);
-      std::vector<int64_t> dm(perm.size()), st(perm.size());
-      for (size_t k = 0; k < perm.size(); ++k) {
-        dm[perm[k]] = d.tensors[ctx].shape[perm[k]];
-        st[perm[k]] = ys[k];
-      }
-      operand(dm, st, p.out_bstride, &p.out_row_stride);
-      p.out = r.reindex.output;
-      F.out_tensor = r.out_tensor;
-      jo = static_cast<int>(j);
-    }
-    if (bh_attention_i8_check(&p) != 0) continue;  // over a limit: the three launches stay
-    F.kernel = bh_attention_i8_kernel(&p);
-    F.alg_ops = A.alg_ops + B.alg_ops;
-    F.alg_bytes = static_cast<double>(meta_[oa.inputs[0]]->bytes + meta_[oa.inputs[1]]->bytes + meta_[ob.inputs[1]]->bytes +
-                                      meta_[ctx]->bytes) + 1024.0;
-    sg->fused_ops.insert(S.op_index);
-    sg->fused_ops.insert(B.op_index);
-    sg->fused_tensors.insert(sc);
-    sg->fused_tensors.insert(pr);
-    for (int j : {jq, jk, jv}) {
-      if (j < 0) continue;
-      dead[j] = true;
-      sg->fused_ops.insert(ls[j].op_index);
-      sg->fused_tensors.insert(ls[j].out_tensor);
-    }
-    if (jo >= 0) {
-      dead[jo] = true;
-      sg->fused_ops.insert(ls[jo].op_index);
-      sg->fused_tensors.insert(ctx);
-    }
-    dead[i + 1] = dead[i + 2] = true;
-    ls[i] = F;
-    i += 2;
-  }
-  std::vector<Launch> out;
-  for (size_t i = 0; i < ls.size(); ++i)
-    if (!dead[i]) out.push_back(ls[i]);
-  sg->launches.swap(out);
-}
-
-// Folds `conv -> ADD/SUB(conv_out, residual)` into the conv epilogue when the
-// conv output has no other reader and nobody needs it materialised.  The
-// epilogue reproduces both TFLite ops exactly (conv requant + clamp to the
-// conv's 8-bit output, then add.cc's arithmetic), so the result is
-// bit-identical to running the two ops.
 
 }  // namespace hip
 }  // namespace band

@@ -46,7 +46,7 @@ absl::Status HipModelExecutor::PrepareJobBatches(interface::IModel* model, const
   for (int b : order) {
     JobBatchVariant v;
     v.batch = b;
-    RETURN_STATUS_IF(hm->CloneWithJobBatch(b, &v.model, device_flag_ == DeviceFlag::kGPU && gpu_detection_));
+    RETURN_STATUS_IF(hm->CloneWithJobBatch(b, &v.model, device_flag_ == DeviceFlag::kGPU && opt_.gpu_detection));
     t_variant_ctor = true;
     v.exec = std::make_unique<HipModelExecutor>(model_id_, worker_id_, device_flag_, thread_affinity_mask_,
                                                 num_threads_);
@@ -59,10 +59,7 @@ absl::Status HipModelExecutor::PrepareJobBatches(interface::IModel* model, const
     v.exec->direct_io_ = direct_io_;
     v.exec->block_sync_ = block_sync_;
     v.exec->sync_mode_ = sync_mode_;
-    v.exec->gpu_detection_ = gpu_detection_;
-    v.exec->hybrid_conv_ = hybrid_conv_;
-    v.exec->fused_attention_ = fused_attention_;
-    v.exec->fused_layernorm_f32_ = fused_layernorm_f32_;
+    v.exec->opt_ = opt_;  // latched: `base` was prepared, so this executor has bound its model
     if (device_flag_ == DeviceFlag::kCPU) {  // one host pool per worker
       if (!cpu_pool_)
         cpu_pool_ = std::make_shared<CpuPool>(num_threads_ > 0 ? num_threads_ : 1,

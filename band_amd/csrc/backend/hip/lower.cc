@@ -467,22 +467,26 @@ absl::Status HipModelExecutor::BuildLaunches(const HipModel& model, PreparedSubg
   }
   // fused chains / blocks are GPU kernels picked by on-device timing; chains
   // first (they cut more launches), blocks over what the chains left
-  if (allow_fusion_ && allow_chain_ && device_flag_ == DeviceFlag::kGPU) FuseChains(model, sg);
-  if (allow_fusion_ && allow_irb_ && device_flag_ == DeviceFlag::kGPU) FuseBlocks(model, sg);
-  if (allow_fusion_ && allow_layernorm_ && device_flag_ == DeviceFlag::kGPU) FuseLayerNorm(model, sg);
-  if (allow_fusion_ && allow_layernorm_ && fused_layernorm_f32_ == 1 && device_flag_ == DeviceFlag::kGPU) {
+  if (opt_.allow_fusion && opt_.allow_chain && device_flag_ == DeviceFlag::kGPU) FuseChains(model, sg);
+  if (opt_.allow_fusion && opt_.allow_irb && device_flag_ == DeviceFlag::kGPU) FuseBlocks(model, sg);
+  if (opt_.allow_fusion && opt_.allow_layernorm && device_flag_ == DeviceFlag::kGPU) FuseLayerNorm(model, sg);
+  if (opt_.allow_fusion && opt_.allow_layernorm && opt_.fused_layernorm_f32 && device_flag_ == DeviceFlag::kGPU) {
     FuseLayerNormF32(model, sg);
     FoldLayerNormQuant(model, sg);
   }
-  if (allow_fusion_ && fused_attention_ == 1 && device_flag_ == DeviceFlag::kGPU) FuseAttention(model, sg);
-  if (allow_fusion_) FuseGlue(model, sg);
-  if (allow_fusion_ && allow_group_ && device_flag_ == DeviceFlag::kGPU) RETURN_STATUS_IF(GroupConvs(sg));
+  if (opt_.allow_fusion && opt_.fused_attention && device_flag_ == DeviceFlag::kGPU) FuseAttention(model, sg);
+  if (opt_.allow_fusion) FuseGlue(model, sg);
+  if (opt_.allow_fusion && opt_.allow_group && device_flag_ == DeviceFlag::kGPU) RETURN_STATUS_IF(GroupConvs(sg));
   return absl::OkStatus();
 }
 
-
+// Folds `conv -> ADD/SUB(conv_out, residual)` into the conv epilogue when the
+// conv output has no other reader and nobody needs it materialised.  The
+// epilogue reproduces both TFLite ops exactly (conv requant + clamp to the
+// conv's 8-bit output, then add.cc's arithmetic), so the result is
+// bit-identical to running the two ops.
 bool HipModelExecutor::TryFuseResidualAdd(const HipModel& model, int oi, PreparedSubgraph* sg, Launch* L) {
-  if (!allow_fusion_ || !allow_add_) return false;
+  if (!opt_.allow_fusion || !opt_.allow_add) return false;
   const TflModel& d = model.desc();
   const int t = d.ops[oi].outputs[0];
   if (consumers_[t].size() != 1) return false;
@@ -491,9 +495,7 @@ bool HipModelExecutor::TryFuseResidualAdd(const HipModel& model, int oi, Prepare
   const TflOperator& add = d.ops[j];
   if ((add.builtin != kTflAdd && add.builtin != kTflSub) || add.inputs.size() != 2) return false;
   if (!GpuSupports(d, add, nullptr)) return false;
-  if (sg->no_fuse.count(t) || sg->extra_d2h.count(t)) return false;
-  if (std::find(sg->outputs.begin(), sg->outputs.end(), t) != sg->outputs.end()) return false;
-  if (std::find(d.outputs.begin(), d.outputs.end(), t) != d.outputs.end()) return false;
+  if (KeptOutside(d, *sg, t)) return false;
   const bool conv_is_first = add.inputs[0] == t;
   const int other = conv_is_first ? add.inputs[1] : add.inputs[0];
   if (other == t) return false;
@@ -561,8 +563,7 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
                            co.inputs[0] != t;
         all_fold = all_fold && folds;
       }
-      std::set<int> subgraph_outputs(sg->outputs.begin(), sg->outputs.end());
-      if (all_fold && !subgraph_outputs.count(t) && !sg->no_fuse.count(t) && !sg->extra_d2h.count(t)) {
+      if (all_fold && !KeptOutside(d, *sg, t)) {
         sg->fused_tensors.insert(t);  // never materialised: a view of it re-lowers with the copy
         *emit = false;
         return absl::OkStatus();
@@ -579,7 +580,7 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
     }
     case kTflConv2D:
     case kTflDepthwiseConv2D: {
-      if (hybrid_conv_ && IsHybridConvOp(d, op)) return LowerConvHybrid(model, oi, in_ptr, out_ptr, ckey, sg, L);
+      if (opt_.hybrid_conv && IsHybridConvOp(d, op)) return LowerConvHybrid(model, oi, in_ptr, out_ptr, ckey, sg, L);
       const bool dw = op.builtin == kTflDepthwiseConv2D;
       ConvGeometry g;
       if (!ConvArgs(d, op, &g, &why)) return Refused(op, why);
@@ -698,7 +699,7 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
 }
 
 bool HipModelExecutor::DequantFoldsIntoDetection(const TflModel& d, const PreparedSubgraph& sg, int oi) const {
-  if (device_flag_ != DeviceFlag::kGPU || !gpu_detection_ || !allow_fusion_) return false;
+  if (device_flag_ != DeviceFlag::kGPU || !opt_.gpu_detection || !opt_.allow_fusion) return false;
   const TflOperator& op = d.ops[oi];
   if (op.builtin != kTflDequantize || op.inputs.empty() || op.inputs[0] < 0 || op.outputs.empty()) return false;
   const TflTensor& in = d.tensors[op.inputs[0]];
@@ -712,9 +713,7 @@ bool HipModelExecutor::DequantFoldsIntoDetection(const TflModel& d, const Prepar
   int batch = 1;
   const TflOperator& det = d.ops[j];
   if (!DetectionSupported(d, det, nullptr, &batch) || (det.inputs[0] != t && det.inputs[1] != t)) return false;
-  if (sg.no_fuse.count(t) || sg.extra_d2h.count(t)) return false;
-  if (std::find(sg.outputs.begin(), sg.outputs.end(), t) != sg.outputs.end()) return false;
-  return std::find(d.outputs.begin(), d.outputs.end(), t) == d.outputs.end();
+  return !KeptOutside(d, sg, t);
 }
 
 absl::Status HipModelExecutor::LowerDetectionGpu(const HipModel& model, int oi, PreparedSubgraph* sg, Launch* L) {
@@ -722,7 +721,7 @@ absl::Status HipModelExecutor::LowerDetectionGpu(const HipModel& model, int oi, 
   const TflOperator& op = d.ops[oi];
   CpuDetectionParams c{};
   int batch = 1;
-  if (!gpu_detection_ || !DetectionSupported(d, op, &c, &batch))
+  if (!opt_.gpu_detection || !DetectionSupported(d, op, &c, &batch))
     return absl::InternalError("unsupported custom op " + op.custom_code);
   bh_detection_params& p = L->detg;
   p = bh_detection_params{};

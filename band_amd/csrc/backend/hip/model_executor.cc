@@ -2,7 +2,8 @@
 // construction, the op-set support checks, InvestigateModelSpec,
 // PrepareSubgraph, the metadata getters and views, and execution (graph
 // capture / replay, host copies, waits, profiling).  The lowering lives in
-// lower.cc, the fusion passes in fusion.cc, job batching in job_batch.cc.
+// lower.cc, the fusion passes in fusion.cc and fusion_transformer.cc, job
+// batching in job_batch.cc.
 #include "backend/hip/model_executor.h"
 
 #include <sys/prctl.h>
@@ -54,8 +55,36 @@ HipModelExecutor::HipModelExecutor(ModelId model_id, WorkerId worker_id, DeviceF
   direct_io_ = env::DirectIo();
   coalesce_max_ = env::Coalesce();
   coalesce_lanes_ = env::CoalesceLanes();
-  gpu_detection_ = env::GpuDetection();
-  hybrid_conv_ = env::HybridConv();
+  opt_.Latch(false);
+}
+
+void ExecOptions::Latch(bool bound) {
+  if (!bound) {
+    gpu_detection = env::GpuDetection();
+    hybrid_conv = env::HybridConv();
+  }
+  if (!bound || latched) return;
+  latched = true;
+  const char* f = env::Fusion();
+  if (f[0] == '0') allow_fusion = false;
+  if (std::strcmp(f, "noirb") == 0) allow_irb = false;  // diagnostics: one fusion kind at a time
+  if (std::strcmp(f, "noadd") == 0) allow_add = false;
+  if (std::strcmp(f, "nochain") == 0) allow_chain = false;
+  if (std::strcmp(f, "nogroup") == 0) allow_group = false;
+  if (std::strcmp(f, "noargmax") == 0) allow_argmax = false;
+  if (std::strcmp(f, "nolayernorm") == 0) allow_layernorm = false;
+  if (std::strcmp(f, "forcechain") == 0) forced_chain = ForcedChain::kPlain;  // parity tests: every feasible chain
+  if (std::strcmp(f, "forcetile") == 0) forced_chain = ForcedChain::kTile;    // ... in the tile form
+  if (std::strcmp(f, "forcedeep") == 0) forced_chain = ForcedChain::kDeep;    // ... in the deep form
+  if (std::strcmp(f, "forcestage") == 0) forced_chain = ForcedChain::kStage;  // ... in the stage form
+  if (std::strcmp(f, "forcedense") == 0) forced_chain = ForcedChain::kDense;  // ... in the dense form
+  if (std::strcmp(f, "notile") == 0) no_tile_chain = true;    // A-B: the raster chain forms only
+  if (std::strcmp(f, "nodeep") == 0) no_deep_chain = true;    // A-B: without the deep-issue forms
+  if (std::strcmp(f, "nosplit") == 0) no_split_chain = true;  // A-B: without the phase-C split forms
+  if (std::strcmp(f, "nostage") == 0) no_stage_chain = true;  // A-B: without the stage forms
+  autotune = env::Autotune();
+  fused_attention = env::FusedAttention();
+  fused_layernorm_f32 = env::FusedLayerNormF32();
 }
 
 HipModelExecutor::~HipModelExecutor() {
@@ -87,11 +116,7 @@ std::unique_ptr<HipModelExecutor> HipModelExecutor::MakeLane() {
   // kernels-only variant graphs: the coalescer moves each pass's I/O on the
   // lane's stream (from the members' views, or from the variants' mirrors)
   lane->direct_io_ = true;
-  lane->autotune_ = autotune_;
-  lane->gpu_detection_ = gpu_detection_;
-  lane->hybrid_conv_ = hybrid_conv_;
-  lane->fused_attention_ = fused_attention_;
-  lane->fused_layernorm_f32_ = fused_layernorm_f32_;
+  lane->opt_ = opt_;  // latched: a lane exists only once this executor has bound its model
   return lane;
 }
 
@@ -287,13 +312,13 @@ bool HipModelExecutor::CpuSupports(const TflModel& m, const TflOperator& op, std
 
 bool HipModelExecutor::GpuSupportsHere(const TflModel& m, const TflOperator& op, std::string* why) const {
   int batch = 1;
-  if (gpu_detection_ && DetectionSupported(m, op, nullptr, &batch)) return true;
-  if (hybrid_conv_ && IsHybridConvOp(m, op)) return FloatSupports(m, op, why, true);
+  if (opt_.gpu_detection && DetectionSupported(m, op, nullptr, &batch)) return true;
+  if (opt_.hybrid_conv && IsHybridConvOp(m, op)) return FloatSupports(m, op, why, true);
   return GpuSupports(m, op, why);
 }
 
 bool HipModelExecutor::CpuSupportsHere(const TflModel& m, const TflOperator& op, std::string* why) const {
-  if (hybrid_conv_ && IsHybridConvOp(m, op)) return FloatSupports(m, op, why, true);
+  if (opt_.hybrid_conv && IsHybridConvOp(m, op)) return FloatSupports(m, op, why, true);
   return CpuSupports(m, op, why);
 }
 
@@ -318,26 +343,7 @@ absl::Status HipModelExecutor::EnsureMeta(const HipModel& model) {
     for (int t : d.ops[i].outputs)
       if (t >= 0) producer_[t] = i;
   }
-  const char* f = env::Fusion();
-  if (f[0] == '0') allow_fusion_ = false;
-  if (std::strcmp(f, "noirb") == 0) allow_irb_ = false;   // diagnostics: one fusion kind at a time
-  if (std::strcmp(f, "noadd") == 0) allow_add_ = false;
-  if (std::strcmp(f, "nochain") == 0) allow_chain_ = false;
-  if (std::strcmp(f, "nogroup") == 0) allow_group_ = false;
-  if (std::strcmp(f, "noargmax") == 0) allow_argmax_ = false;
-  if (std::strcmp(f, "nolayernorm") == 0) allow_layernorm_ = false;
-  if (std::strcmp(f, "forcechain") == 0) forced_chain_ = ForcedChain::kPlain;  // parity tests: every feasible chain
-  if (std::strcmp(f, "forcetile") == 0) forced_chain_ = ForcedChain::kTile;  // ... in the tile form
-  if (std::strcmp(f, "notile") == 0) no_tile_chain_ = true;  // A-B: the raster chain forms only
-  if (std::strcmp(f, "nodeep") == 0) no_deep_chain_ = true;  // A-B: without the deep-issue forms
-  if (std::strcmp(f, "nosplit") == 0) no_split_chain_ = true;  // A-B: without the phase-C split forms
-  if (std::strcmp(f, "forcedeep") == 0) forced_chain_ = ForcedChain::kDeep;  // ... in the deep form
-  if (std::strcmp(f, "forcestage") == 0) forced_chain_ = ForcedChain::kStage;  // ... in the stage form
-  if (std::strcmp(f, "forcedense") == 0) forced_chain_ = ForcedChain::kDense;  // ... in the dense form
-  if (std::strcmp(f, "nostage") == 0) no_stage_chain_ = true;  // A-B: without the stage forms
-  if (!env::Autotune()) autotune_ = false;
-  if (fused_attention_ < 0) fused_attention_ = env::FusedAttention() ? 1 : 0;
-  if (fused_layernorm_f32_ < 0) fused_layernorm_f32_ = env::FusedLayerNormF32() ? 1 : 0;
+  opt_.Latch(true);  // (a lane or job-batch variant came with its parent's block)
   return absl::OkStatus();
 }
 

@@ -121,6 +121,8 @@ struct Launch {
   const char* kernel = "";
 };
 
+struct LnMatch;  // fusion_transformer.cc
+
 struct OpTiming {
   int op_index;
   const char* kernel;
@@ -159,6 +161,44 @@ struct PreparedSubgraph {
   // poll-wait (BAND_HIP_SYNC=poll): running mean of a pass's device time as
   // the waiting thread saw it (us), so it sleeps through most of the next one
   double wait_us = 0.0;
+};
+
+// What an executor latches from the environment for its lowering and fusion.
+// A top-level executor calls Latch(false) when constructed (the support sets
+// are asked before a model is bound) and Latch(true) when it binds its model;
+// a coalescer lane or job-batch variant takes its parent's block, latched.
+struct ExecOptions {
+  bool allow_fusion = true;  // BAND_HIP_FUSION=0
+  bool allow_irb = true, allow_add = true;  // BAND_HIP_FUSION=noirb / noadd: diagnostics
+  bool allow_chain = true;      // BAND_HIP_FUSION=nochain
+  bool allow_group = true;      // BAND_HIP_FUSION=nogroup: one launch per conv
+  bool allow_argmax = true;     // BAND_HIP_FUSION=noargmax: RESIZE_BILINEAR and ARG_MAX / ARG_MIN as two launches
+  bool allow_layernorm = true;  // BAND_HIP_FUSION=nolayernorm: a LayerNorm's ten ops as ten launches
+  // BAND_HIP_FUSION=forcechain / forcetile / forcedeep / forcestage / forcedense (parity
+  // tests): every feasible chain fused, in the named form where that fits
+  ForcedChain forced_chain = ForcedChain::kNone;
+  bool no_tile_chain = false;   // BAND_HIP_FUSION=notile: the tuner skips the tile form
+  bool no_deep_chain = false;   // BAND_HIP_FUSION=nodeep: the tuner skips the deep-issue forms
+  bool no_split_chain = false;  // BAND_HIP_FUSION=nosplit: the tuner skips the phase-C split forms
+  bool no_stage_chain = false;  // BAND_HIP_FUSION=nostage: the tuner skips the stage forms
+  bool autotune = true;         // BAND_HIP_AUTOTUNE=0: pick fused tiles by the static model
+  // BAND_HIP_GPU_DETECTION=1: TFLite_Detection_PostProcess is in this
+  // executor's kGPU set.  Off by default: the reference places the op on
+  // the CPU worker, and so does this backend unless asked.
+  bool gpu_detection = false;
+  // BAND_HIP_HYBRID_CONV=1: hybrid CONV_2D / DEPTHWISE_CONV_2D run (both
+  // workers: the rule changes what the op computes)
+  bool hybrid_conv = false;
+  // BAND_HIP_FUSED_ATTENTION=1: the attention core as one launch on a kGPU
+  // executor.  Off by default.
+  bool fused_attention = false;
+  // BAND_HIP_FUSED_LAYERNORM_F32=1: a float32 LayerNorm as one launch on a kGPU
+  // executor, quantising its rows for the hybrid FULLY_CONNECTEDs that read it.
+  // Off by default; BAND_HIP_FUSION=0 / nolayernorm turn it off.
+  bool fused_layernorm_f32 = false;
+  bool latched = false;
+  // bound = false: gpu_detection and hybrid_conv; bound = true: the rest, unless latched already
+  void Latch(bool bound);
 };
 
 class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
@@ -249,15 +289,25 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   void FuseBlocks(const HipModel& model, PreparedSubgraph* sg);
   // dw3x3 -> conv1x1 [+ADD] [-> conv1x1] runs into one bh_chain_i8 launch
   bool PackChainTile(bh_chain_params* q, std::shared_ptr<DeviceBlob>* blob);
+  // The privacy rule (fusion.cc).  KeptOutside: a view (no_fuse / extra_d2h) or an output needs t stored;
+  // PrivateTensor / PrivateTo: t is read by op `only_consumer` alone / by ops of `ops` alone, and not KeptOutside
+  bool KeptOutside(const TflModel& d, const PreparedSubgraph& sg, int t) const;
   bool PrivateTensor(const TflModel& d, const PreparedSubgraph& sg, int t, int only_consumer) const;
+  bool PrivateTo(const TflModel& d, const PreparedSubgraph& sg, int t, const std::set<int>& ops) const;
   void FuseChains(const HipModel& model, PreparedSubgraph* sg);
   // 8-bit unary table ops into the producing conv / FC / depthwise epilogue;
   // CONCATENATION with outer size 1 elided (producers write their slices);
   // int8 RESIZE_BILINEAR -> ARG_MAX / ARG_MIN over channels as one launch (kGPU)
   void FuseGlue(const HipModel& model, PreparedSubgraph* sg);
+  // ls[i .. i+9] are the ten launches of a LayerNorm, of the given kinds (fills *n); the loop that replaces
+  // each such run `fill` agrees to by the one launch it fills (fusion_transformer.cc)
+  bool MatchLayerNorm(const TflModel& d, const PreparedSubgraph& sg, const std::vector<Launch>& ls, size_t i,
+                      const Launch::Kind kinds[10], LnMatch* n) const;
+  void FuseTenOps(const TflModel& d, PreparedSubgraph* sg, const Launch::Kind kinds[10],
+                  const std::function<bool(const LnMatch& n, const Launch* l, Launch* F)>& fill);
   void FuseLayerNorm(const HipModel& model, PreparedSubgraph* sg);
   // the ten float32 launches of a LayerNorm into one bh_layernorm_f32 launch
-  // (fused_layernorm_f32_), then the kDynQuantRows launches that read its
+  // (ExecOptions::fused_layernorm_f32), then the kDynQuantRows launches that read its
   // result folded into that launch's epilogue
   void FuseLayerNormF32(const HipModel& model, PreparedSubgraph* sg);
   void FoldLayerNormQuant(const HipModel& model, PreparedSubgraph* sg);
@@ -295,7 +345,7 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   // scratch owned by sg, then *l as the kFcHybrid launch
   absl::Status LowerFcHybrid(const HipModel& model, int op_index, void* in_ptr, void* out_ptr, const std::string& ckey,
                              PreparedSubgraph* sg, Launch* l);
-  // hybrid CONV_2D / DEPTHWISE_CONV_2D (HybridConvArgs; hybrid_conv_): a
+  // hybrid CONV_2D / DEPTHWISE_CONV_2D (HybridConvArgs; ExecOptions::hybrid_conv): a
   // kDynQuantItems launch into a scratch owned by sg, then *l as the product
   absl::Status LowerConvHybrid(const HipModel& model, int op_index, void* in_ptr, void* out_ptr, const std::string& ckey,
                                PreparedSubgraph* sg, Launch* l);
@@ -362,38 +412,7 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   std::vector<std::unique_ptr<TensorMeta>> meta_;
   std::vector<std::vector<int>> consumers_;  // tensor -> ops reading it (whole model)
   std::vector<int> producer_;                // tensor -> op writing it (-1: input / constant)
-  bool allow_fusion_ = true;
-  bool allow_irb_ = true;  // BAND_HIP_FUSION=noirb / noadd: diagnostics
-  bool allow_add_ = true;
-  bool allow_chain_ = true;   // BAND_HIP_FUSION=nochain
-  bool allow_group_ = true;   // BAND_HIP_FUSION=nogroup: one launch per conv
-  bool allow_argmax_ = true;  // BAND_HIP_FUSION=noargmax: RESIZE_BILINEAR and ARG_MAX / ARG_MIN as two launches
-  bool allow_layernorm_ = true;  // BAND_HIP_FUSION=nolayernorm: a LayerNorm's ten ops as ten launches
-  // BAND_HIP_FUSION=forcechain / forcetile / forcedeep / forcestage / forcedense (parity
-  // tests): every feasible chain fused, in the named form where that fits
-  ForcedChain forced_chain_ = ForcedChain::kNone;
-  bool no_tile_chain_ = false;     // BAND_HIP_FUSION=notile: the tuner skips the tile form
-  bool no_deep_chain_ = false;     // BAND_HIP_FUSION=nodeep: the tuner skips the deep-issue forms
-  bool no_split_chain_ = false;    // BAND_HIP_FUSION=nosplit: the tuner skips the phase-C split forms
-  bool no_stage_chain_ = false;    // BAND_HIP_FUSION=nostage: the tuner skips the stage forms
-  bool autotune_ = true;  // BAND_HIP_AUTOTUNE=0: pick fused tiles by the static model
-  // BAND_HIP_GPU_DETECTION=1, latched at construction (lanes and job-batch
-  // variants take their parent's): TFLite_Detection_PostProcess is in this
-  // executor's kGPU set.  Off by default: the reference places the op on
-  // the CPU worker, and so does this backend unless asked.
-  bool gpu_detection_ = false;
-  // BAND_HIP_HYBRID_CONV latched at construction: hybrid CONV_2D /
-  // DEPTHWISE_CONV_2D run (both workers: the rule changes what the op computes)
-  bool hybrid_conv_ = false;
-  // BAND_HIP_FUSED_ATTENTION=1, latched when the executor binds its model
-  // (-1: not yet; lanes and job-batch variants take their parent's): the
-  // attention core as one launch on a kGPU executor.  Off by default.
-  int fused_attention_ = -1;
-  // BAND_HIP_FUSED_LAYERNORM_F32=1, latched and inherited as fused_attention_
-  // is: a float32 LayerNorm as one launch on a kGPU executor, quantising its
-  // rows for the hybrid FULLY_CONNECTEDs that read it.  Off by default;
-  // BAND_HIP_FUSION=0 / nolayernorm turn it off.
-  int fused_layernorm_f32_ = -1;
+  ExecOptions opt_;
   std::map<SubgraphKey, std::unique_ptr<PreparedSubgraph>> subgraphs_;
   int ordinal_ = -1;
   bh_stream_t stream_ = nullptr;

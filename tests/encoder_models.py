@@ -322,6 +322,18 @@ def layer_norm_model(tokens=5, dim=48, batch=1):
     return g.build()
 
 
+LN_OP_OF = {"m": 0, "a": 6}  # which of the ten ops makes the row mean m, the per-element a = x * g
+
+
+def layer_norm_with_intermediate_output(which):
+    """LayerNorm alone on [1, 3, 5] (three rows, depth 5: below every vector width of the kernels) whose
+    outputs are y and one intermediate of the pattern, `which` of LN_OP_OF"""
+    g = QGraph(np.int8, seed=92, name="layer_norm_out_" + which)
+    g.output(g.layer_norm(g.input([1, 3, 5], scale=0.05)))
+    g.output(g.mb.ops[-10:][LN_OP_OF[which]]["outputs"][0])
+    return g.build()
+
+
 # ---- the fused launch ------------------------------------------------------------------------
 LN_KERNEL = "layernorm_i8_kernel"
 LN_MAX_DEPTH = 1024

@@ -282,6 +282,18 @@ def ln_only():
     return g.build()
 
 
+LN_OP_OF = {"m": 0, "a": 6}  # which of the ten ops makes the row mean m, the per-element a = x * g
+
+
+def ln_with_intermediate_output(which):
+    """LayerNorm alone on [1, 3, 5] (three rows, depth 5: below every vector width of the kernels) whose
+    outputs are y and one intermediate of the pattern, `which` of LN_OP_OF"""
+    g = FGraph(seed=85, name="ln_out_" + which, hybrid="symmetric")
+    g.output(g.layer_norm(g.input([1, 3, 5])))
+    g.output(g.mb.ops[-10:][LN_OP_OF[which]]["outputs"][0])
+    return g.build()
+
+
 QKV_UNITS = (20, 16, 33)
 
 

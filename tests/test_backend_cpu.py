@@ -205,6 +205,34 @@ def test_cpu_worker_mnv2_cat_282_bit_exact(golden_dir):
     np.testing.assert_array_equal(out, ref)
 
 
+def test_job_batch_variants_take_their_parents_fusion_setting(monkeypatch):
+    """a variant lowers under the options its parent latched when it bound the model, not under the
+    environment of the PrepareJobBatches call.  The model is the glue zoo's: FuseGlue folds its byte
+    tables and its CONCATENATION away, BAND_HIP_FUSION=0 keeps them.  (Before the options became one
+    block the variants read BAND_HIP_FUSION themselves, and this test failed: their lists were the
+    fused ones.)"""
+    from tests.glue_models import glue_zoo
+    buf = glue_zoo(np.int8)
+
+    def bound():
+        m = HipModel(0)
+        assert m.FromBuffer(buf).ok()
+        ex = HipModelExecutor(0, 0, DeviceFlag.kCPU)
+        assert ex.PrepareSubgraph(m).ok()
+        return m, ex
+    key = SubgraphKey(0, 0)
+    monkeypatch.delenv("BAND_HIP_FUSION", raising=False)
+    fused = bound()[1].LaunchKernels(key)
+    monkeypatch.setenv("BAND_HIP_FUSION", "0")
+    m, ex = bound()
+    unfused = ex.LaunchKernels(key)
+    assert unfused != fused and len(unfused) > len(fused), (fused, unfused)  # FuseGlue changes this model's list
+    monkeypatch.delenv("BAND_HIP_FUSION")
+    st = ex.PrepareJobBatches(m, key, 2)
+    assert st.ok(), st.message()
+    assert ex.JobBatchLaunchKernels(key, 2) == unfused
+
+
 def test_prepare_wrong_model_id(golden_dir):
     m = _model(golden_dir, "add.tflite", mid=4)
     ex = HipModelExecutor(5, 0, DeviceFlag.kCPU)

@@ -163,6 +163,26 @@ def test_ln_only_is_one_launch_and_exact(gpu_lib, flag_on):
                                       err_msg="run %d" % i)
 
 
+@pytest.mark.parametrize("which", sorted(L.LN_OP_OF))
+def test_an_intermediate_that_is_a_model_output_keeps_the_ten_launches(gpu_lib, flag_on, monkeypatch, which):
+    """a LayerNorm whose row mean m, or whose a = x * g, is a model output beside y: the fused launch
+    would not store it, so with the flag on the ten ops stay ten launches, and every output is the
+    bytes of the run with BAND_HIP_FUSION=nolayernorm"""
+    buf = L.ln_with_intermediate_output(which)
+    feeds = [Y.model_feed(buf, seed=60 + i) for i in range(2)]
+    om, kernels, runs = _run(buf, feeds, "outputs")
+    assert len(om.outputs) == 2
+    assert len(kernels) == 10 and L.KERNEL not in kernels, kernels
+    assert (kernels.count("mean_kernel"), kernels.count("unary_f32_kernel"), kernels.count("eltwise_f32_kernel")) == \
+        (2, 1, 7), kernels
+    monkeypatch.setenv("BAND_HIP_FUSION", "nolayernorm")
+    _, kernels_off, runs_off = _run(buf, feeds, "outputs")
+    assert kernels == kernels_off
+    for vals, ref in zip(runs, runs_off):
+        for t in om.outputs:
+            assert vals[t].tobytes() == ref[t].tobytes(), "tensor %d" % t
+
+
 @pytest.mark.parametrize("name", ["ln_qkv_symmetric", "ln_qkv_asymmetric", "ln_mixed"])
 def test_projections_of_a_fused_layernorm_are_exact(gpu_lib, flag_on, name):
     """every FULLY_CONNECTED equals np_fc_from_q(np_dynquant(np_layernorm_f32(x))) bit for bit; ln_qkv: one LayerNorm

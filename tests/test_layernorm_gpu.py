@@ -223,6 +223,38 @@ def test_models_without_the_fused_launch(gpu_lib, monkeypatch, model_refs, fusio
             np.testing.assert_array_equal(ex.GetTensorView(key, t).GetData().reshape(refs[i][t].shape), refs[i][t])
 
 
+@pytest.mark.parametrize("which", sorted(E.LN_OP_OF))
+def test_an_intermediate_that_is_a_model_output_keeps_the_ten_launches(gpu_lib, monkeypatch, which):
+    """a LayerNorm whose row mean m, or whose a = x * g, is a model output beside y: the fused launch
+    would not store it, so the ten ops stay ten launches, and every output is the bytes of the run
+    with BAND_HIP_FUSION=nolayernorm"""
+    buf = E.layer_norm_with_intermediate_output(which)
+    xs = [E.model_input(buf, seed=70 + i) for i in range(2)]
+    runs = {}
+    for fusion in (None, "nolayernorm"):
+        if fusion:
+            monkeypatch.setenv("BAND_HIP_FUSION", fusion)
+        else:
+            monkeypatch.delenv("BAND_HIP_FUSION", raising=False)
+        m, ex, key = _exec(buf, 84)
+        assert len(ex.GetOutputs(key)) == 2
+        kernels = ex.LaunchKernels(key)
+        t_in = ex.GetInputs(key)[0]
+        outs = []
+        for x in xs:
+            ex.GetTensorView(key, t_in).GetData()[...] = x
+            assert ex.ExecuteSubgraph(key).ok()
+            outs.append([ex.GetTensorView(key, t).GetData().copy() for t in ex.GetOutputs(key)])
+        runs[fusion] = (kernels, outs)
+    kernels, outs = runs[None]
+    assert len(kernels) == 10 and E.LN_KERNEL not in kernels, kernels
+    assert kernels.count(E.MEAN_KERNEL) == 2 and kernels.count(E.SQDIFF_KERNEL) == 1, kernels
+    assert kernels == runs["nolayernorm"][0]
+    for got, ref in zip(outs, runs["nolayernorm"][1]):
+        for g, r in zip(got, ref):
+            assert g.tobytes() == r.tobytes()
+
+
 @pytest.mark.parametrize("name", sorted(E.MODELS))
 def test_models_job_batches(gpu_lib, monkeypatch, model_refs, name):
     monkeypatch.delenv("BAND_HIP_FUSION", raising=False)

@@ -13,9 +13,13 @@ the lowering is checked with
     python tools/launch_digest.py --device cpu > a.txt      (on each build)
 
 Models: the synthesiser's MobileNetV2 / V1, ShuffleNet, attention block,
-ViT-tiny, SSD (with and without postprocess), EfficientDet-Lite2 at 448,
-DeepLab (with argmax) and PoseNet, int8 and uint8 where the synthesiser
-builds both, and every .tflite under tests/golden/.
+ViT-tiny (bare, and with LayerNorm and MLP), encoder block, SSD (with and
+without postprocess), EfficientDet-Lite2 at 448, DeepLab (with argmax) and
+PoseNet, int8 and uint8 where the synthesiser builds both; from the tests'
+builders the float32 encoder block with hybrid FULLY_CONNECTEDs and a
+MobileNetV2 of hybrid convs; and every .tflite under tests/golden/.  The
+opt-in launches show when the run sets their variables (BAND_HIP_FUSED_ATTENTION,
+BAND_HIP_FUSED_LAYERNORM_F32, BAND_HIP_HYBRID_CONV, BAND_HIP_GPU_DETECTION).
 
 Job batches: PrepareJobBatches(max_batch=4) is run on every model and its
 status printed, so a variant that no longer lowers shows.  The variants'
@@ -60,7 +64,20 @@ def synth_models():
             out["%s_%s" % (name, np.dtype(dt).name)] = (lambda fn, dt: lambda batch: fn(dt, batch=batch))(fn, dt)
     out["attention_block_int8"] = lambda batch: S.attention_block(np.int8, batch=batch)  # BATCH_MATMUL: int8 only
     out["vit_tiny_int8"] = lambda batch: S.vit_tiny(np.int8, batch=batch)
+    out["encoder_block_int8"] = lambda batch: S.encoder_block(np.int8, batch=batch)  # int8 LayerNorm + GELU
+    out["vit_tiny_ln_mlp_int8"] = lambda batch: S.vit_tiny(np.int8, batch=batch, layer_norm=True, mlp=True)
     return out
+
+
+def test_models():
+    """name -> build() of the models taken from the tests' builders (batch 1 only)"""
+    from tests import hybrid_conv_models, layernorm_f32_models
+    return {
+        # float32 encoder block, hybrid FULLY_CONNECTED, Q / K / V as extra outputs (float32 LayerNorm)
+        "encoder_f32_hybrid_qkv": lambda: layernorm_f32_models.encoder_with_qkv_outputs("symmetric"),
+        # MobileNetV2 at 32 x 32 with every conv hybrid
+        "mobilenet_v2_32_hybrid_conv": hybrid_conv_models.MODELS["mobilenet_v2_32_all"],
+    }
 
 
 def digest(name, buf, device, mid, batches, full):
@@ -125,6 +142,11 @@ def main():
         for b in (2, 3, 4):
             digest("%s batch %d" % (name, b), build(b), a.device, mid, False, a.full)
             mid += 1
+    for name, build in test_models().items():
+        if want and name not in want:
+            continue
+        digest(name, build(), a.device, mid, True, a.full)
+        mid += 1
     for path in sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "*.tflite"))):
         name = os.path.basename(path)
         if want and name not in want:
