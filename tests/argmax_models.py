@@ -9,6 +9,8 @@ never greater (or smaller), so it is selected only as element 0."""
 import numpy as np
 
 from band_amd.tflite_synth import OPT, QGraph, Table, deeplab_v3_mobilenet_v2
+from oracle.tflite_fb import Model as OModel
+from tests.graph_reference import run_reference
 
 
 def arg_ref(x, axis=-1, minimum=False, out=np.int32):
@@ -72,21 +74,15 @@ def argmax_zoo_twin():
     return _zoo(False)
 
 
-def argmax_zoo_ref(twin_outputs):
-    """expected outputs of argmax_zoo from the twin's [softmax, uint8, float, logits]"""
-    sm, u, f, b = twin_outputs
+def argmax_zoo_ref(x):
+    """expected outputs of argmax_zoo for input x, from the twin's [softmax, uint8, float, logits]"""
+    twin = argmax_zoo_twin()
+    vals = run_reference(twin, x)
+    sm, u, f, b = [vals[t] for t in OModel(twin).outputs]
     return [arg_ref(sm, -1, out=np.int64), arg_ref(u, 1, minimum=True), arg_ref(f, 3), b, arg_ref(b, 3, out=np.int64)]
 
 
-def oracle_outputs(buf, x):
-    """the oracle's outputs of model bytes `buf` (model order) for one input"""
-    from oracle.runner import OracleInterpreter
-    from oracle.tflite_fb import Model as OModel
-    om = OModel(buf)
-    res = OracleInterpreter(om).run({om.inputs[0]: x})
-    return [res[t] for t in om.outputs]
-
-
 def deeplab_logits(size, x):
-    """the oracle's [1, size, size, 21] logits of the DeepLab twin (argmax=None)"""
-    return oracle_outputs(deeplab_v3_mobilenet_v2(np.int8, size=size), x)[0]
+    """the reference's [1, size, size, 21] logits of the DeepLab twin (argmax=None)"""
+    buf = deeplab_v3_mobilenet_v2(np.int8, size=size)
+    return run_reference(buf, x)[OModel(buf).outputs[0]]

@@ -17,6 +17,7 @@ import numpy as np
 from band_amd.tflite_synth import QGraph, attention_block, encoder_block, vit_tiny
 from oracle import runner as orc
 from tests import bmm_models as B
+from tests.fixed_point import round_half_away
 from tests.grouped_models import SLACK, _buffer
 
 KERNEL = "attention_i8_kernel"
@@ -83,13 +84,6 @@ class AttnCase:
 
 
 # ---- a numpy restatement of the 8-bit softmax with the row sum's order as a parameter ----
-def tfl_round(v):
-    """TfLiteRound (round half away from zero) on float32, exact"""
-    v = np.asarray(v, np.float32)
-    t = np.trunc(v)
-    return t + np.where(np.abs(v - t) >= np.float32(0.5), np.sign(v), np.float32(0)).astype(np.float32)
-
-
 def np_softmax(x, in_scale, order="forward", out_scale=1.0 / 256, out_zp=-128):
     """int8 x [rows, depth]: table gather, float32 row sum in `order` (forward: j = 0 .. depth - 1 from 0.0f, the
     reference's; reversed; pairwise: adjacent pairs, level by level), 1 / (sum * out_scale), round, clamp"""
@@ -111,7 +105,7 @@ def np_softmax(x, in_scale, order="forward", out_scale=1.0 / 256, out_zp=-128):
             s = (s + e[..., j]).astype(np.float32)
     inv = (np.float32(1.0) / (s * np.float32(out_scale)).astype(np.float32)).astype(np.float32)
     pr = (e * inv[..., None]).astype(np.float32)
-    return np.clip(tfl_round(pr).astype(np.int32) + out_zp, -128, 127).astype(np.int8)
+    return np.clip(round_half_away(pr).astype(np.int32) + out_zp, -128, 127).astype(np.int8)
 
 
 SUM_ORDER_FLOOR = 32
@@ -349,18 +343,6 @@ MODELS = {
 }
 ATTENTIONS = {"attention_17_48_3": 1, "attention_64_64_2": 1, "encoder_17_48_3_96": 1, "vit_tiny_32": 2,
               "shared_operand_64": 1}
-
-
-def model_input(buf, seed=0):
-    from tests import encoder_models as E
-    return E.model_input(buf, seed=seed)
-
-
-def run_model(buf, x):
-    """{tensor: value} of every tensor: run_with_bmm, with the LayerNorm / GELU ops of an encoder block through
-    tests.encoder_models"""
-    from tests import encoder_models as E
-    return E.run_with_encoder_ops(buf, x)
 
 
 def attention_tensors(buf):

@@ -1,5 +1,6 @@
 """Fixtures of BATCH_MATMUL (int8 / float32): the cases, the references, the
-launcher parameter blocks (host or device buffers), the models and run_with_bmm.
+launcher parameter blocks (host or device buffers), the models and eval_bmm
+(one operator for tests.graph_reference).
 
 int8 reference: the oracle's FULLY_CONNECTED (its C code, unchanged) per batch
 slice, `orc.fully_connected(lhs[b], rhs[b]^T, None, in_zp=z_l, w_zp=z_r,
@@ -19,7 +20,7 @@ import numpy as np
 from band_amd.tflite_synth import QGraph, attention_block, vit_tiny
 from oracle import runner as orc
 from tests import float_harness as H
-from tests import reindex_models as R
+from tests.fixed_point import rdbypot
 from tests.grouped_models import SLACK, _buffer
 
 BATCH_MATMUL = 126
@@ -134,17 +135,6 @@ def bmm_ref(case):
 
 
 # ---- an independent numpy restatement, with the mistakes a kernel can make -----
-def rdbypot(y, e, half_up=False):
-    if e == 0:
-        return y
-    if half_up:
-        return (y + (1 << (e - 1))) >> e
-    mask = (1 << e) - 1
-    rem = y & mask
-    thr = (mask >> 1) + (y < 0)
-    return (y >> e) + (rem > thr)
-
-
 def step1(case):
     """(int64 accumulators, the value after step 1) of the case"""
     A, B = case.views()
@@ -175,7 +165,7 @@ def np_bmm(case, wrong=None):
     if wrong != "no_kzz":
         acc = acc + (-(-K // 64) * 64 if wrong == "padded_k" else K) * case.z_l * case.z_r
     y = ((acc << max(case.shift, 0)) * int(case.mult) + (1 << 30)) >> 31
-    v = rdbypot(y, max(-case.shift, 0), half_up=wrong == "half_up") + case.z_o
+    v = rdbypot(y, max(-case.shift, 0), mutant=wrong) + case.z_o
     return np.clip(v, -128, 127).astype(np.int8).reshape(case.out_shape)
 
 
@@ -442,11 +432,8 @@ MODELS = {
 }
 
 
-def model_input(buf, seed=0):
-    return R.zoo_input(buf, seed=seed)
-
-
-def _eval_bmm(om, o, vals):
+def eval_bmm(om, o, vals):
+    """BATCH_MATMUL operator o on vals: int8 through bmm_eval, float32 as the float64 product"""
     T = om.tensors
     tl, tr, to = T[o.inputs[0]], T[o.inputs[1]], T[o.outputs[0]]
     adj_x = bool(o.options.scalar(0, "b", 0)) if o.options is not None else False
@@ -459,31 +446,3 @@ def _eval_bmm(om, o, vals):
     (s_l, z_l), (s_r, z_r), (s_o, z_o) = orc._q(tl), orc._q(tr), orc._q(to)
     mult, shift = orc.conv_multipliers(s_l, np.array([s_r], np.float32), 1, s_o, True)  # FullyConnectedMultiplier
     return [bmm_eval(lhs, rhs, adj_x, adj_y, z_l, z_r, z_o, int(mult[0]), int(shift[0]))]
-
-
-def run_with_bmm(model_bytes, inputs):
-    """{tensor: value} of every tensor of the model: BATCH_MATMUL through bmm_eval
-    (float: the float64 product), re-indexing ops through numpy, the rest
-    through the oracle interpreter, op by op"""
-    from oracle.runner import OracleInterpreter
-    from oracle.tflite_fb import Model as OModel
-    om = OModel(model_bytes)
-    interp = OracleInterpreter(om)
-    if not isinstance(inputs, dict):
-        inputs = {om.inputs[0]: inputs}
-    vals = {t.index: t.data for t in om.tensors if t.is_const}
-    for k, v in inputs.items():
-        vals[k] = np.asarray(v, om.tensors[k].np_dtype).reshape(om.tensors[k].shape)
-    for i, o in enumerate(om.operators):
-        if o.builtin == BATCH_MATMUL:
-            outs = _eval_bmm(om, o, vals)
-        elif o.builtin in R.REINDEX_OPS:
-            outs = R._eval_reindex(om, o, vals)
-        else:
-            feed = {k: vals[k] for k in o.inputs if k >= 0 and not om.tensors[k].is_const}
-            res = interp.run(feed, ops=[i])
-            outs = [res[t] for t in o.outputs]
-        for t, v in zip(o.outputs, outs):
-            assert list(v.shape) == om.tensors[t].shape, (o.builtin, v.shape, om.tensors[t].shape)
-            vals[t] = np.ascontiguousarray(v).reshape(om.tensors[t].shape)
-    return vals

@@ -29,15 +29,16 @@ Two families, kept apart because bh_conv_requant_fast_ok is per layer:
   zero point is added in int32 as well); for uint8 it is pulled in by 2^24 because the kernels fold the 128-shift of both operands
   into the bias (a term of K * 128 * 255 that TFLite itself never forms).
 
-requant_np() / epilogue_np() restate the epilogue in int64 numpy; the CPU test
-holds them to the oracle on every directed layer, then uses the same code with
-a deliberate defect switched on as the mutants.
+epilogue_np() restates the epilogue in int64 numpy (tests.fixed_point.mbqm and
+the clamp); the CPU test holds it to the oracle on every directed layer, then
+uses the same code with a deliberate defect switched on as the mutants.
 """
 import functools
 
 import numpy as np
 
 from oracle import runner as orc
+from tests.fixed_point import mbqm, srdhm
 from tests.kernel_harness import ConvCase
 
 ES = (0, 1, 2, 3, 7, 8, 12, 15, 20)
@@ -53,45 +54,9 @@ def type_range(dtype):
 
 # --- int64 restatement of the epilogue (and its mutants) --------------------
 
-def srdhm_np(a, m, trunc=False):
-    ab = np.asarray(a, np.int64) * np.asarray(m, np.int64)
-    if trunc:  # mutant: no rounding nudge
-        return np.sign(ab) * (np.abs(ab) >> 31)
-    q = ab + np.where(ab >= 0, 1 << 30, 1 - (1 << 30))
-    return np.sign(q) * (np.abs(q) >> 31)  # C division truncates
-
-
-def rdbypot_np(x, e):
-    mask = (np.int64(1) << e) - 1
-    rem = x & mask
-    thr = (mask >> 1) + (x < 0)
-    return (x >> e) + (rem > thr)
-
-
-def requant_np(acc, mult, shift, mutant=None):
-    """MultiplyByQuantizedMultiplier per channel (last axis)"""
-    acc = np.asarray(acc, np.int64)
-    mult = np.asarray(mult, np.int64)
-    shift = np.asarray(shift, np.int64)
-    left = np.maximum(shift, 0)
-    e = np.maximum(-shift, 0)
-    if mutant == "no_left":
-        left = np.zeros_like(left)
-    a = acc << left
-    if mutant == "single":  # one rounding of acc * M / 2^(31 + e), half away from zero
-        n = a * mult
-        t = 31 + e
-        return np.sign(n) * ((np.abs(n) + (np.int64(1) << (t - 1))) >> t)
-    x = srdhm_np(a, mult, trunc=mutant == "trunc1")
-    if mutant == "floor2":
-        return x >> e
-    if mutant == "half_up":
-        return (x + np.where(e > 0, np.int64(1) << np.maximum(e - 1, 0), 0)) >> e
-    return rdbypot_np(x, e)
-
-
 def epilogue_np(acc, mult, shift, out_zp, amin, amax, dtype, mutant=None):
-    v = requant_np(acc, mult, shift, mutant)
+    """MultiplyByQuantizedMultiplier per channel (last axis), zero point, clamp"""
+    v = mbqm(acc, mult, shift, mutant)
     if mutant == "clamp_first":
         out = np.clip(v, amin, amax) + out_zp
     elif mutant == "wrap":
@@ -105,7 +70,7 @@ def ties(acc, mult, shift):
     """(positive, negative) step-2 rounding ties: masks over acc"""
     shift = np.asarray(shift, np.int64)
     e = np.maximum(-shift, 0)
-    x = srdhm_np(np.asarray(acc, np.int64) << np.maximum(shift, 0), mult)
+    x = srdhm(np.asarray(acc, np.int64) << np.maximum(shift, 0), mult)
     tie = (e > 0) & ((x & ((np.int64(1) << e) - 1)) == (np.int64(1) << np.maximum(e - 1, 0)))
     return tie & (x > 0), tie & (x < 0)
 
@@ -130,9 +95,9 @@ def tie_acc(m, e, sign, scale=3):
         return None
     x0 = sign * ((1 << (e - 1)) + (0 if scale is None else 1 << (e + scale)))
     guess = (x0 << 31) // m
-    srdhm = orc.lib().tfl_srdhm
+    tfl_srdhm = orc.lib().tfl_srdhm
     for d in range(-4, 5):
-        if -(1 << 31) <= guess + d < (1 << 31) and srdhm(guess + d, m) == x0:
+        if -(1 << 31) <= guess + d < (1 << 31) and tfl_srdhm(guess + d, m) == x0:
             return guess + d
     raise AssertionError("no accumulator maps to %d under multiplier %d" % (x0, m))
 

@@ -2,7 +2,7 @@
 SQUARED_DIFFERENCE, RSQRT, GELU): numpy restatements written from the formulas
 (TFLite 2.9.2 reduce.cc, squared_difference.cc, elementwise.cc, activations.cc)
 and not from the C++ of this project, the launcher cases, the models and
-run_with_encoder_ops.
+eval_encoder_op (one operator for tests.graph_reference).
 
 Parity unpinned: no fixture of the reference holds outputs of these ops, and the
 TFLite sources are not at hand; the restatements follow the arithmetic as it is
@@ -19,49 +19,12 @@ import numpy as np
 
 from band_amd.tflite_synth import QGraph, encoder_block, vit_tiny
 from oracle import runner as orc
-from tests import bmm_models as B
-from tests import reindex_models as R
+from tests.fixed_point import mbqm, rdbypot, round_half_away, sat_shl, srdhm
 from tests.grouped_models import SLACK, _buffer
 
 MEAN, RSQRT, SQUARED_DIFFERENCE, GELU = 40, 76, 99, 150
 MEAN_KERNEL, SQDIFF_KERNEL = "mean_rows_kernel", "eltwise_sqdiff_kernel"
 F = np.float32
-
-
-# ---- fixed point ---------------------------------------------------------------------
-def srdhm(a, b):
-    """SaturatingRoundingDoublingHighMul on int64 arrays / ints (never a == b == INT32_MIN here)"""
-    ab = np.asarray(a, np.int64) * np.int64(b) if not isinstance(a, int) else a * b
-    if isinstance(ab, int):
-        nudge = (1 << 30) if ab >= 0 else 1 - (1 << 30)
-        q = abs(ab + nudge) >> 31  # C++ division truncates toward zero
-        return q if ab + nudge >= 0 else -q
-    nudge = np.where(ab >= 0, 1 << 30, 1 - (1 << 30))
-    t = ab + nudge
-    return np.where(t >= 0, t >> 31, -((-t) >> 31))
-
-
-def rdbypot(x, e):
-    """RoundingDivideByPOT: round half away from zero"""
-    if e == 0:
-        return x
-    mask = (1 << e) - 1
-    rem = x & mask
-    thr = (mask >> 1) + (x < 0)
-    return (x >> e) + (rem > thr)
-
-
-def mbqm(x, mult, shift):
-    """MultiplyByQuantizedMultiplier (shift > 0 is a left shift)"""
-    left, right = max(shift, 0), max(-shift, 0)
-    return rdbypot(srdhm(x * (1 << left), mult), right)
-
-
-def round_half_away(v):
-    """TfLiteRound on float32 values, exact"""
-    v = np.asarray(v, F)
-    t = np.trunc(v)
-    return t + np.where(np.abs(v - t) >= F(0.5), np.sign(v), F(0)).astype(F)
 
 
 # ---- the four ops ---------------------------------------------------------------------
@@ -105,11 +68,6 @@ def np_sqdiff(a, b, s1, z1, s2, z2, so, zo):
     return np.clip(rdbypot(srdhm(d * d, mo), -ho) + zo, -128, 127).astype(np.int8)
 
 
-def _sat_shl(x, e):
-    thr = (1 << (31 - e)) - 1
-    return (1 << 31) - 1 if x > thr else (-(1 << 31) if x < -thr else x << e)
-
-
 def inv_sqrt_multiplier(v):
     """gemmlowp's GetInvSqrtQuantizedMultiplierExp(v, reverse_shift = -1) on a Python int"""
     if v <= 1:
@@ -124,8 +82,8 @@ def inv_sqrt_multiplier(v):
     half_in = rdbypot(v >> 1, 1)
     x = 1 << 28  # 1.0 with 3 integer bits
     for _ in range(5):
-        x3 = _sat_shl(srdhm(srdhm(x, x), x), 6)
-        x = _sat_shl(srdhm((1 << 28) + (1 << 27), x) - srdhm(half_in, x3), 3)
+        x3 = sat_shl(srdhm(srdhm(x, x), x), 6)
+        x = sat_shl(srdhm((1 << 28) + (1 << 27), x) - srdhm(half_in, x3), 3)
     x = srdhm(x, 1518500250)
     if shift < 0:
         x <<= -shift
@@ -378,7 +336,8 @@ class LnCase:
         self.x = model_input(self.buf, seed=seed + rows + C)
 
     def ref(self):
-        return run_with_encoder_ops(self.buf, self.x)[self.om.outputs[0]].reshape(self.rows, self.C)
+        from tests.graph_reference import run_reference
+        return run_reference(self.buf, self.x)[self.om.outputs[0]].reshape(self.rows, self.C)
 
     def params(self, in_ptr, gamma_ptr, beta_ptr, table_ptr, out_ptr):
         from band_amd import _abi
@@ -444,16 +403,25 @@ def model_input(buf, seed=0):
     return np.clip(z + np.round(rng.normal(0, 30, t.shape)), -128, 127).astype(np.int8)
 
 
-def _eval_new(om, o, vals):
+def is_encoder_op(om, o):
+    """the 8-bit ops restated here: SQUARED_DIFFERENCE, RSQRT, GELU, and MEAN over the last axis
+    (8-bit MEAN over H, W and the float forms are the oracle's)"""
+    T = om.tensors
+    if o.builtin not in (MEAN, SQUARED_DIFFERENCE, RSQRT, GELU) or T[o.inputs[0]].np_dtype not in (np.int8, np.uint8):
+        return False
+    if o.builtin != MEAN:
+        return True
+    axes = [int(v) for v in np.asarray(T[o.inputs[1]].data).reshape(-1)]
+    return axes in ([-1], [len(T[o.inputs[0]].shape) - 1])
+
+
+def eval_encoder_op(om, o, vals):
+    """operator o (is_encoder_op) on vals"""
     T = om.tensors
     ti, to = T[o.inputs[0]], T[o.outputs[0]]
     x = vals[o.inputs[0]]
-    if ti.np_dtype == np.float32:
-        raise NotImplementedError("float models are not run here")
     (s_i, z_i), (s_o, z_o) = orc._q(ti), orc._q(to)
     if o.builtin == MEAN:
-        axes = [int(v) for v in np.asarray(T[o.inputs[1]].data).reshape(-1)]
-        assert axes in ([-1], [x.ndim - 1])
         return [np_mean_rows(x, s_i, z_i, s_o, z_o).reshape(to.shape)]
     if o.builtin == SQUARED_DIFFERENCE:
         s_b, z_b = orc._q(T[o.inputs[1]])
@@ -463,31 +431,3 @@ def _eval_new(om, o, vals):
         return [lut(x, np_rsqrt_table(s_i, z_i, s_o, z_o))]
     approximate = bool(o.options.scalar(0, "b", 0)) if o.options is not None else False
     return [lut(x, np_gelu_table(ti.np_dtype == np.int8, approximate, s_i, z_i, s_o, z_o))]
-
-
-def run_with_encoder_ops(model_bytes, inputs):
-    """{tensor: value} of every tensor: MEAN / SQUARED_DIFFERENCE / RSQRT / GELU
-    through the restatements above, the rest as tests.bmm_models.run_with_bmm"""
-    from oracle.runner import OracleInterpreter
-    from oracle.tflite_fb import Model as OModel
-    om = OModel(model_bytes)
-    interp = OracleInterpreter(om)
-    if not isinstance(inputs, dict):
-        inputs = {om.inputs[0]: inputs}
-    vals = {t.index: t.data for t in om.tensors if t.is_const}
-    for k, v in inputs.items():
-        vals[k] = np.asarray(v, om.tensors[k].np_dtype).reshape(om.tensors[k].shape)
-    for i, o in enumerate(om.operators):
-        if o.builtin in (MEAN, SQUARED_DIFFERENCE, RSQRT, GELU):
-            outs = _eval_new(om, o, vals)
-        elif o.builtin == B.BATCH_MATMUL:
-            outs = B._eval_bmm(om, o, vals)
-        elif o.builtin in R.REINDEX_OPS:
-            outs = R._eval_reindex(om, o, vals)
-        else:
-            feed = {k: vals[k] for k in o.inputs if k >= 0 and not om.tensors[k].is_const}
-            res = interp.run(feed, ops=[i])
-            outs = [res[t] for t in o.outputs]
-        for t, v in zip(o.outputs, outs):
-            vals[t] = np.ascontiguousarray(v).reshape(om.tensors[t].shape)
-    return vals

@@ -63,6 +63,15 @@ SOFTMAX  y_k = e_k / S, e_k = exp(a_k), a_k = (x_k - max) beta, S = sum_j e_j
     Where exp((x_k - max) beta) underflows the reference is below 2^-126 and
     0 is accepted by the floor.
 
+MEAN over the last axis of n values: n - 1 additions in any order and one
+    division, n roundings, each relative to a partial sum of at most sum|x|:
+        |got - y| <= gamma(n) mean |x| + 2^-126.
+GELU: tests.encoder_models.gelu_f32_bound, which takes the ulp count of the
+    library's erf / tanh (1 for glibc, 16 for the device library).
+BATCH_MATMUL: |got - y| <= gamma(K + 2) sum_k |a_k| |b_k| + 2^-126.
+TRANSPOSE, the slicing ops, SPLIT / SPLIT_V, DEPTH_TO_SPACE / SPACE_TO_DEPTH
+    copy elements: exact (tests.reindex_models.eval_reindex).
+
 Non-finite values: the comparison first requires NaN exactly where the
 reference has NaN and +-inf exactly where it has +-inf; numpy's clip
 propagates NaN as TFLite's std::min(std::max(v, lo), hi) does.
@@ -70,6 +79,8 @@ propagates NaN as TFLite's std::min(std::max(v, lo), hi) does.
 import numpy as np
 
 from oracle import float_ref as F
+from tests import encoder_models as E
+from tests import reindex_models as R
 
 U = 2.0 ** -24
 FLOOR = 2.0 ** -126
@@ -235,7 +246,7 @@ def accepts(got, ref, tol):
 
 
 # ---- graphs: one reference per op, on the executor's own inputs ------------
-SQUARED_DIFFERENCE, RSQRT = 99, 76  # BuiltinOperator codes the oracle's table leaves out
+SQUARED_DIFFERENCE, RSQRT, BATCH_MATMUL, GELU = 99, 76, 126, 150  # BuiltinOperator codes the oracle's table leaves out
 
 
 def _const(om, t):
@@ -249,7 +260,7 @@ def _const(om, t):
     return None
 
 
-def op_reference(om, o, vals):
+def op_reference(om, o, vals, gelu_ulps=1):
     """(float64 reference, bound or None) of operator o, its inputs taken from
     vals {tensor: array} where present and from the model's constants otherwise"""
     def get(i):
@@ -292,6 +303,25 @@ def op_reference(om, o, vals):
         return softmax_ref(x, opt.scalar(0, "f", 1.0) if opt is not None else 1.0)
     if name == "RESHAPE":
         return x.astype(F64), None
+    if name == "MEAN":
+        assert [int(v) for v in om.tensors[o.inputs[1]].data.reshape(-1)] in ([-1], [x.ndim - 1])
+        keep = om.tensors[o.outputs[0]].shape
+        ref = x.astype(F64).mean(axis=-1).reshape(keep)
+        mag = np.abs(x).astype(F64).mean(axis=-1).reshape(keep)
+        return ref, gamma(x.shape[-1]) * mag + FLOOR
+    if code == GELU:
+        approx = bool(opt.scalar(0, "b", 0)) if opt is not None else False
+        ref = np.vectorize(lambda v: E.gelu_real(float(v), approx))(x).astype(F64)
+        return ref, E.gelu_f32_bound(x, ref, gelu_ulps)
+    if code == BATCH_MATMUL:
+        adj_x = bool(opt.scalar(0, "b", 0)) if opt is not None else False
+        adj_y = bool(opt.scalar(1, "b", 0)) if opt is not None else False
+        a, b = x.astype(F64), get(1).astype(F64)
+        a = np.swapaxes(a, -1, -2) if adj_x else a
+        b = np.swapaxes(b, -1, -2) if adj_y else b
+        return np.matmul(a, b), gamma(a.shape[-1] + 2) * np.matmul(np.abs(a), np.abs(b)) + FLOOR
+    if code in R.REINDEX_OPS:
+        return R.eval_reindex(om, o, vals)[0].astype(F64), None
     raise NotImplementedError("float harness: op %s" % name)
 
 
@@ -304,18 +334,32 @@ def graph_reference(om, feed):
     return vals
 
 
-def check_graph_ops(om, vals, what=""):
+def check_graph_ops(om, vals, what="", gelu_ulps=1):
     """Each op against its reference on the tensors in vals (the executor's
-    own); returns {op name: largest |got - ref| / tol}."""
-    worst = {}
+    own).  A dynamic-range FULLY_CONNECTED / CONV_2D / DEPTHWISE_CONV_2D (int8
+    weights) must equal its rule bit for bit (tests.hybrid_models,
+    tests.hybrid_conv_models); every other op is held to op_reference's bound.
+    gelu_ulps: 1 for glibc, 16 for the device library.  Returns ({op name:
+    largest |got - ref| / tol}, {"fc", "conv": bit-exact ops checked})."""
+    from tests import hybrid_conv_models as C
+    from tests import hybrid_models as Y
+    worst, exact = {}, {"fc": 0, "conv": 0}
     for i, o in enumerate(om.operators):
+        got = vals[o.outputs[0]]
+        rule = ("fc", Y.hybrid_fc_reference) if Y.is_hybrid_fc(om, o) else \
+            ("conv", C.hybrid_conv_reference) if C.is_hybrid_conv(om, o) else None
+        if rule:
+            np.testing.assert_array_equal(np.asarray(got).reshape(om.tensors[o.outputs[0]].shape),
+                                          rule[1](om, o, vals[o.inputs[0]]),
+                                          err_msg="%s op %d hybrid %s" % (what, i, o.name))
+            exact[rule[0]] += 1
+            continue
         with np.errstate(invalid="ignore"):  # inf - inf in a non-finite case
-            ref, tol = op_reference(om, o, vals)
-        name = o.name if not o.name.startswith("OP") else {SQUARED_DIFFERENCE: "SQUARED_DIFFERENCE",
-                                                           RSQRT: "RSQRT"}[o.builtin]
-        r = check(vals[o.outputs[0]], ref, tol, "%s op %d %s" % (what, i, name))
+            ref, tol = op_reference(om, o, vals, gelu_ulps)
+        name = {SQUARED_DIFFERENCE: "SQUARED_DIFFERENCE", RSQRT: "RSQRT"}.get(o.builtin, o.name)
+        r = check(got, ref, tol, "%s op %d %s" % (what, i, name))
         worst[name] = max(worst.get(name, 0.0), r)
-    return worst
+    return worst, exact
 
 
 def run_executor(buf, feeds, flag, worker, view_all):

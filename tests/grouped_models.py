@@ -1,6 +1,6 @@
 """Fixtures of grouped CONV_2D (filter [oc, kh, kw, icg] with icg != ic): the
 shapes, the cases, the reference, the launcher parameter blocks (host or device
-buffers), the models and run_with_grouped.
+buffers), the models and eval_grouped (one operator for tests.graph_reference).
 
 The reference is the oracle's dense conv per group: output channels
 [g ocg, (g+1) ocg) are orc.conv2d of input channels [g icg, (g+1) icg) with
@@ -13,7 +13,6 @@ import numpy as np
 
 from band_amd.tflite_synth import OPT, ModelBuilder, QGraph, conv_options
 from oracle import runner as orc
-from tests import reindex_models as R
 from tests.kernel_harness import ConvCase, dom, rand_q, xor_of
 
 CONV_2D = 3
@@ -345,7 +344,7 @@ def is_grouped(om, o):
             om.tensors[o.inputs[1]].shape[3] != om.tensors[o.inputs[0]].shape[3])
 
 
-def _eval_grouped(om, o, vals):
+def eval_grouped(om, o, vals):
     """the oracle interpreter's CONV_2D (oracle/runner.py OracleInterpreter._op) per group"""
     T = om.tensors
     opt = o.options
@@ -377,31 +376,3 @@ def _eval_grouped(om, o, vals):
             mult=np.ascontiguousarray(mult[sl]), shift=np.ascontiguousarray(shift[sl]), amin=amin, amax=amax,
             stride=(sh, sw), dilation=(dh_, dw_), pad=pad, out_hw=(oh, ow)))
     return [np.concatenate(outs, axis=3)]
-
-
-def run_with_grouped(model_bytes, inputs):
-    """{tensor: value} of every tensor of the model: grouped CONV_2D through the
-    per-group oracle conv, re-indexing ops through numpy, the rest through the
-    oracle interpreter, op by op"""
-    from oracle.runner import OracleInterpreter
-    from oracle.tflite_fb import Model as OModel
-    om = OModel(model_bytes)
-    interp = OracleInterpreter(om)
-    if not isinstance(inputs, dict):
-        inputs = {om.inputs[0]: inputs}
-    vals = {t.index: t.data for t in om.tensors if t.is_const}
-    for k, v in inputs.items():
-        vals[k] = np.asarray(v, om.tensors[k].np_dtype).reshape(om.tensors[k].shape)
-    for i, o in enumerate(om.operators):
-        if is_grouped(om, o):
-            outs = _eval_grouped(om, o, vals)
-        elif o.builtin in R.REINDEX_OPS:
-            outs = R._eval_reindex(om, o, vals)
-        else:
-            feed = {k: vals[k] for k in o.inputs if k >= 0 and not om.tensors[k].is_const}
-            res = interp.run(feed, ops=[i])
-            outs = [res[t] for t in o.outputs]
-        for t, v in zip(o.outputs, outs):
-            assert list(v.shape) == om.tensors[t].shape, (o.builtin, v.shape, om.tensors[t].shape)
-            vals[t] = np.ascontiguousarray(v).reshape(om.tensors[t].shape)
-    return vals

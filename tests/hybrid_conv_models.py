@@ -1,8 +1,8 @@
 """Fixtures of the dynamic-range ("hybrid") CONV_2D / DEPTHWISE_CONV_2D -
 float32 input, constant int8 filter with zero points 0, each batch item
 quantised at run time: the numpy restatement of the rule, its deliberately
-wrong variants, the launcher cases, the models and the per-op check of a
-dynamic-range CNN.
+wrong variants, the launcher cases, the models and the rule on one operator of
+a graph (hybrid_conv_reference, for tests.float_harness.check_graph_ops).
 
 The rule (DESIGN 4 holds it in words; restated from memory of TFLite's conv.cc
 EvalHybrid / EvalHybridPerChannel, depthwise_conv.cc EvalHybridPerChannel and
@@ -567,33 +567,6 @@ def hybrid_conv_reference(om, o, x):
     x = np.asarray(x, F).reshape(T[o.inputs[0]].shape)
     g = H.Geom(x.shape[1:3], w.shape[1:3], (sh, sw), (dlh, dlw), opt.scalar(0, "b", 0) == 0)
     return np_conv_hybrid(x, w.data, ws, bias, g, form, act, out_c // x.shape[3] if dw else 1)
-
-
-def check_hybrid_conv_graph(om, vals, what="", gelu_ulps=1):
-    """tests.hybrid_models.check_hybrid_graph for a dynamic-range CNN: each op on the tensors in
-    vals (the executor's own).  A hybrid CONV_2D / DEPTHWISE_CONV_2D and a hybrid FULLY_CONNECTED
-    must equal their rules bit for bit; every other op keeps float_harness's bound.  Returns the
-    number of hybrid convolutions checked."""
-    n = 0
-    for i, o in enumerate(om.operators):
-        got = vals[o.outputs[0]]
-        shape = om.tensors[o.outputs[0]].shape
-        if is_hybrid_conv(om, o):
-            np.testing.assert_array_equal(np.asarray(got).reshape(shape), hybrid_conv_reference(om, o, vals[o.inputs[0]]),
-                                          err_msg="%s op %d hybrid %s" % (what, i, o.name))
-            n += 1
-            continue
-        if Y.is_hybrid_fc(om, o):
-            np.testing.assert_array_equal(np.asarray(got).reshape(shape), Y.hybrid_fc_reference(om, o, vals[o.inputs[0]]),
-                                          err_msg="%s op %d hybrid FULLY_CONNECTED" % (what, i))
-            continue
-        with np.errstate(invalid="ignore"):
-            if o.builtin in (Y.MEAN, Y.GELU, Y.B.BATCH_MATMUL) or o.builtin in Y.R.REINDEX_OPS:
-                ref, tol = Y._extra_reference(om, o, vals, gelu_ulps)
-            else:
-                ref, tol = H.op_reference(om, o, vals)
-        H.check(got, ref, tol, "%s op %d %s" % (what, i, o.name))
-    return n
 
 
 # ---- support checks ----------------------------------------------------------------------

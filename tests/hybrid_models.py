@@ -1,7 +1,8 @@
 """Fixtures of the dynamic-range ("hybrid") FULLY_CONNECTED - float32 input,
 constant int8 weights with one scale, each input row quantised at run time:
 the numpy restatement of the rule, its deliberately wrong variants, the
-launcher cases, the models and the per-op check of a hybrid graph.
+launcher cases, the models and the rule on one operator of a graph
+(hybrid_fc_reference, for tests.float_harness.check_graph_ops).
 
 The rule (DESIGN 4 holds it in words; restated from memory of TFLite's
 fully_connected.cc EvalHybrid and tensor_utils::{Symmetric,Asymmetric}
@@ -30,14 +31,12 @@ import math
 import numpy as np
 
 from band_amd.tflite_synth import FGraph, encoder_block, vit_tiny
-from tests import bmm_models as B
-from tests import encoder_models as E
 from tests import float_harness as H
-from tests import reindex_models as R
+from tests.fixed_point import round_half_away, round_half_away64
 
 F = np.float32
 F64 = np.float64
-FULLY_CONNECTED, MEAN, TRANSPOSE, GELU = 9, 40, 39, 150
+FULLY_CONNECTED, MEAN = 9, 40
 DQ_KERNEL, FC_KERNEL = "dynquant_rows_kernel", "fc_hybrid_kernel"
 ACTS = ("NONE", "RELU", "RELU_N1_TO_1", "RELU6")
 SLACK = 16  # bytes past every output that a launch must leave alone
@@ -45,10 +44,6 @@ NAN_WORD = 0x7fc0dead  # the pattern output buffers are filled with
 
 
 # ---- the rule ----------------------------------------------------------------------------
-def round_half_away64(z):
-    return math.copysign(math.floor(abs(z) + 0.5), z)
-
-
 def np_dynquant(x, asymmetric, half_even=False):
     """(q int8 [rows][depth], s float32 [rows], off int32 [rows]) of float32 rows x.
     half_even: the wrong variant that rounds ties to even."""
@@ -57,7 +52,7 @@ def np_dynquant(x, asymmetric, half_even=False):
     q = np.zeros((rows, depth), np.int8)
     s = np.ones(rows, F)
     off = np.zeros(rows, np.int32)
-    rnd = (lambda v: np.rint(v).astype(F)) if half_even else E.round_half_away
+    rnd = (lambda v: np.rint(v).astype(F)) if half_even else round_half_away
     for i in range(rows):
         row = x[i]
         if not asymmetric:
@@ -381,55 +376,3 @@ def hybrid_fc_reference(om, o, x):
     depth = w.shape[1]
     y = np_fc_hybrid(np.asarray(x, F).reshape(-1, depth), w.data, float(w.scale[0]), bias, act, asym)
     return y.reshape(T[o.outputs[0]].shape)
-
-
-def _extra_reference(om, o, vals, gelu_ulps):
-    """(float64 reference, bound or None) of the float ops tests.float_harness leaves out"""
-    x = np.asarray(vals[o.inputs[0]])
-    if o.builtin == MEAN:
-        # n - 1 additions in any order and one division: n roundings, each relative to a partial
-        # sum of at most sum|x|
-        n = x.shape[-1]
-        keep = om.tensors[o.outputs[0]].shape
-        ref = x.astype(F64).mean(axis=-1).reshape(keep)
-        mag = np.abs(x).astype(F64).mean(axis=-1).reshape(keep)
-        return ref, H.gamma(n) * mag + H.FLOOR
-    if o.builtin == GELU:
-        approx = bool(o.options.scalar(0, "b", 0)) if o.options is not None else False
-        ref = np.vectorize(lambda v: E.gelu_real(float(v), approx))(x).astype(F64)
-        return ref, E.gelu_f32_bound(x, ref, gelu_ulps)
-    if o.builtin == B.BATCH_MATMUL:
-        # tests/bmm_models.py: gamma(K + 2) sum|a||b| + 2^-126
-        adj_x = bool(o.options.scalar(0, "b", 0)) if o.options is not None else False
-        adj_y = bool(o.options.scalar(1, "b", 0)) if o.options is not None else False
-        a, b = x.astype(F64), np.asarray(vals[o.inputs[1]]).astype(F64)
-        a = np.swapaxes(a, -1, -2) if adj_x else a
-        b = np.swapaxes(b, -1, -2) if adj_y else b
-        return np.matmul(a, b), H.gamma(a.shape[-1] + 2) * np.matmul(np.abs(a), np.abs(b)) + H.FLOOR
-    assert o.builtin in R.REINDEX_OPS, o.builtin
-    return R._eval_reindex(om, o, vals)[0].astype(F64), None
-
-
-def check_hybrid_graph(om, vals, what="", gelu_ulps=1):
-    """tests.float_harness.check_graph_ops for a hybrid graph: each op on the
-    tensors in vals (the executor's own).  A hybrid FULLY_CONNECTED must equal
-    the rule bit for bit; every other op keeps float_harness's bound (MEAN,
-    GELU, BATCH_MATMUL and the re-indexing ops, which it leaves out, the bounds
-    above).  gelu_ulps: 1 for glibc, 16 for the device library
-    (tests/test_layernorm_gpu.py).  Returns the number of hybrid ops checked."""
-    n = 0
-    for i, o in enumerate(om.operators):
-        got = vals[o.outputs[0]]
-        if is_hybrid_fc(om, o):
-            np.testing.assert_array_equal(np.asarray(got).reshape(om.tensors[o.outputs[0]].shape),
-                                          hybrid_fc_reference(om, o, vals[o.inputs[0]]),
-                                          err_msg="%s op %d hybrid FULLY_CONNECTED" % (what, i))
-            n += 1
-            continue
-        with np.errstate(invalid="ignore"):
-            if o.builtin in (MEAN, GELU, B.BATCH_MATMUL) or o.builtin in R.REINDEX_OPS:
-                ref, tol = _extra_reference(om, o, vals, gelu_ulps)
-            else:
-                ref, tol = H.op_reference(om, o, vals)
-        H.check(got, ref, tol, "%s op %d %s" % (what, i, o.name))
-    return n

@@ -1,11 +1,10 @@
 """Fixtures of the re-indexing ops (TRANSPOSE, STRIDED_SLICE, SLICE, SPLIT,
 SPLIT_V, SPACE_TO_DEPTH, DEPTH_TO_SPACE): the numpy references, the fills, the
-launcher cases, the model zoo and run_with_reindex.
+launcher cases, the model zoo and eval_reindex.
 
 The reference is numpy and nothing else: every op copies elements, so parity
-is exact.  The oracle does not know these ops; run_with_reindex walks a model
-op by op, sends every op the oracle knows through OracleInterpreter.run(vals,
-ops=[i]) and evaluates the re-indexing ops with the references below, so an
+is exact.  The oracle does not know these ops; tests.graph_reference walks a
+model op by op and evaluates the re-indexing ops with eval_reindex below, so an
 expected value never comes from the product."""
 import numpy as np
 
@@ -251,8 +250,9 @@ def zoo_input(buf, seed=0):
     return rng.integers(info.min, info.max + 1, t.shape).astype(t.np_dtype)
 
 
-# ---- the reference run -----------------------------------------------------------
-def _eval_reindex(om, o, vals):
+# ---- the reference of one operator (tests.graph_reference) -------------------------
+def eval_reindex(om, o, vals):
+    """outputs of re-indexing operator o on vals: the synthesiser's shapes are numpy's"""
     T = om.tensors
 
     def const(i):
@@ -276,29 +276,3 @@ def _eval_reindex(om, o, vals):
         return [depth_to_space_ref(vals[o.inputs[0]], opt(0))]
     assert b == SPACE_TO_DEPTH
     return [space_to_depth_ref(vals[o.inputs[0]], opt(0))]
-
-
-def run_with_reindex(model_bytes, inputs):
-    """{tensor: value} of every tensor of the model for inputs {tensor: array}
-    (or one array for a single-input model)"""
-    from oracle.runner import OracleInterpreter
-    from oracle.tflite_fb import Model as OModel
-    om = OModel(model_bytes)
-    interp = OracleInterpreter(om)
-    if not isinstance(inputs, dict):
-        inputs = {om.inputs[0]: inputs}
-    vals = {t.index: t.data for t in om.tensors if t.is_const}
-    for k, v in inputs.items():
-        vals[k] = np.asarray(v, om.tensors[k].np_dtype).reshape(om.tensors[k].shape)
-    for i, o in enumerate(om.operators):
-        if o.builtin in REINDEX_OPS:
-            outs = _eval_reindex(om, o, vals)
-            for t, v in zip(o.outputs, outs):  # the synthesiser's shapes are numpy's
-                assert list(v.shape) == om.tensors[t].shape, (o.builtin, v.shape, om.tensors[t].shape)
-        else:
-            feed = {k: vals[k] for k in o.inputs if k >= 0 and not om.tensors[k].is_const}
-            res = interp.run(feed, ops=[i])
-            outs = [res[t] for t in o.outputs]
-        for t, v in zip(o.outputs, outs):
-            vals[t] = np.ascontiguousarray(v).reshape(om.tensors[t].shape)
-    return vals

@@ -11,8 +11,7 @@ import pytest
 
 from band_amd import DeviceFlag, HipModel, HipModelExecutor, SubgraphKey
 from band_amd.tflite_synth import QGraph, deeplab_v3_mobilenet_v2
-from tests.argmax_models import (arg_ref, argmax_zoo, argmax_zoo_ref, argmax_zoo_twin, deeplab_logits,
-                                 oracle_outputs, tied_pixels)
+from tests.argmax_models import (arg_ref, argmax_zoo, argmax_zoo_ref, deeplab_logits, tied_pixels)
 
 
 def _model(buf, mid=0):
@@ -35,7 +34,7 @@ def _run(buf, x, flag=DeviceFlag.kCPU, worker=0):
 @pytest.fixture(scope="module")
 def zoo_case():
     x = np.random.default_rng(7).integers(-128, 128, (1, 6, 5, 8)).astype(np.int8)
-    return x, argmax_zoo_ref(oracle_outputs(argmax_zoo_twin(), x))
+    return x, argmax_zoo_ref(x)
 
 
 @pytest.fixture(scope="module")
@@ -137,7 +136,7 @@ def test_deeplab_argmax_on_cpu_executor(deeplab_case, out):
 def test_job_batch_of_3_on_cpu(zoo_case, deeplab_case):
     rng = np.random.default_rng(11)
     for buf, shape, expect in (
-            (argmax_zoo(), (1, 6, 5, 8), lambda x: argmax_zoo_ref(oracle_outputs(argmax_zoo_twin(), x))),
+            (argmax_zoo(), (1, 6, 5, 8), argmax_zoo_ref),
             (deeplab_v3_mobilenet_v2(np.int8, size=64, argmax=np.int32), (1, 64, 64, 3),
              lambda x: [arg_ref(deeplab_logits(64, x), 3)])):
         m = _model(buf)

@@ -1,5 +1,5 @@
 """The fused attention launch without a GPU: the composed reference of
-tests.attention_models against run_with_bmm on a model, the case set's
+tests.attention_models against run_reference on a model, the case set's
 coverage, every refusal of bh_attention_i8_check with its reason, the LDS a
 launch takes, the directed properties of the reference (clamped scores, flat
 rows, an underflowing table, the sum-order case) and the kCPU executor, which
@@ -14,16 +14,19 @@ from oracle import runner as orc
 from oracle.tflite_fb import Model as OModel
 from tests import attention_models as A
 from tests import bmm_models as B
+from tests import encoder_models as E
+from tests import reindex_models as R
+from tests.graph_reference import run_reference
 
 CASES = A.launcher_cases()
 
 
 def test_composed_reference_equals_run_with_bmm_on_a_model():
-    """scores / probabilities / context of attention_block(17, 48, 3) taken from run_with_bmm's q, k, v through
+    """scores / probabilities / context of attention_block(17, 48, 3) taken from run_reference's q, k, v through
     AttnCase's three steps"""
     buf = A.MODELS["attention_17_48_3"]()
     om = OModel(buf)
-    vals = B.run_with_bmm(buf, B.model_input(buf, seed=3))
+    vals = run_reference(buf, R.zoo_input(buf, seed=3))
     (sc, pr, ctx), = A.attention_tensors(buf)
     first = next(o for o in om.operators if o.outputs[0] == sc)
     second = next(o for o in om.operators if o.outputs[0] == ctx)
@@ -163,8 +166,8 @@ def test_cpu_executor_ignores_the_flag(monkeypatch):
     monkeypatch.setenv("BAND_HIP_FUSED_ATTENTION", "1")
     monkeypatch.delenv("BAND_HIP_FUSION", raising=False)
     buf = A.MODELS["attention_17_48_3"]()
-    x = A.model_input(buf, seed=5)
-    ref = A.run_model(buf, x)
+    x = E.model_input(buf, seed=5)
+    ref = run_reference(buf, x)
     m = HipModel(0)
     assert m.FromBuffer(buf).ok()
     ex = HipModelExecutor(0, 0, DeviceFlag.kCPU)

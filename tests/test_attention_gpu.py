@@ -8,7 +8,7 @@ again; the flag unset or BAND_HIP_FUSION=0: the default launch list; job batches
 2, 3, 5; an over-limit model), a GPU-only engine and the kCPU executor.
 
 Reference: tests.attention_models (the oracle's FULLY_CONNECTED per batch slice
-and the oracle's softmax) and run_model for models; everything is compared with
+and the oracle's softmax) and run_reference for models; everything is compared with
 assert_array_equal."""
 import ctypes
 
@@ -18,7 +18,8 @@ import pytest
 from band_amd import DeviceFlag, HipModel, HipModelExecutor, SubgraphKey
 from oracle.tflite_fb import Model as OModel
 from tests import attention_models as A
-from tests import bmm_models as B
+from tests import encoder_models as E
+from tests.graph_reference import run_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -83,8 +84,8 @@ def model_refs():
     out = {}
     for name, build in A.MODELS.items():
         buf = build()
-        xs = [A.model_input(buf, seed=70 + i) for i in range(5)]
-        out[name] = (buf, xs, [A.run_model(buf, x) for x in xs])
+        xs = [E.model_input(buf, seed=70 + i) for i in range(5)]
+        out[name] = (buf, xs, [run_reference(buf, x) for x in xs])
     return out
 
 
@@ -194,8 +195,8 @@ def test_over_limit_model_stays_unfused(gpu_lib, monkeypatch):
     monkeypatch.setenv(FLAG, "1")
     monkeypatch.delenv("BAND_HIP_FUSION", raising=False)
     buf = A.shared_operand_model(1025)
-    x = A.model_input(buf, seed=4)
-    ref = B.run_with_bmm(buf, x)
+    x = E.model_input(buf, seed=4)
+    ref = run_reference(buf, x)
     m, ex, key = _exec(buf, 95)
     kernels = _kernels(ex, key)
     assert kernels == ["bmm_mfma_kernel", "softmax_kernel", "bmm_mfma_kernel"], kernels

@@ -15,6 +15,8 @@ from band_amd.tflite_reader_py import OPTION_FIELDS, read
 from band_amd.tflite_synth import OPT
 from tests import bmm_models as B
 from tests import float_harness as H
+from tests import reindex_models as R
+from tests.graph_reference import run_reference
 from tests.grouped_models import HostBuffer
 from tests.test_float_cpu import assert_float_close
 
@@ -227,8 +229,8 @@ def model_refs():
     out = {}
     for name, build in B.MODELS.items():
         buf = build()
-        xs = [B.model_input(buf, seed=30 + s) for s in range(3)]
-        out[name] = (buf, xs, [B.run_with_bmm(buf, x) for x in xs])
+        xs = [R.zoo_input(buf, seed=30 + s) for s in range(3)]
+        out[name] = (buf, xs, [run_reference(buf, x) for x in xs])
     return out
 
 
@@ -301,8 +303,8 @@ def test_rank2_activation_is_not_batchable_but_runs():
     st = ex.PrepareJobBatches(m, key, 3)
     assert not st.ok() and "job batching: BATCH_MATMUL with a rank-2 activation operand" in st.message(), st.message()
     assert ex.MaxJobBatch(key) == 1
-    x = B.model_input(buf, seed=4)
-    ref = B.run_with_bmm(buf, x)
+    x = R.zoo_input(buf, seed=4)
+    ref = run_reference(buf, x)
     ex.GetTensorView(key, ex.GetInputs(key)[0]).GetData()[...] = x
     assert ex.ExecuteSubgraph(key).ok()
     t = ex.GetOutputs(key)[0]

@@ -7,7 +7,7 @@ job batches 2, 3, 5) and the engine.
 
 Reference: tests.bmm_models.bmm_ref (the oracle's FULLY_CONNECTED per batch
 slice; float64 with the bound gamma(K + 2) sum|a||b| + 2^-126 for floats) and
-run_with_bmm for models.  int8 tensors are compared with assert_array_equal,
+run_reference for models.  int8 tensors are compared with assert_array_equal,
 float model tensors at the tolerance of tests/test_float_cpu.py."""
 import ctypes
 
@@ -18,6 +18,8 @@ from band_amd import DeviceFlag, HipModel, HipModelExecutor, SubgraphKey
 from oracle.tflite_fb import Model as OModel
 from tests import bmm_models as B
 from tests import float_harness as H
+from tests import reindex_models as R
+from tests.graph_reference import run_reference
 from tests.test_float_cpu import assert_float_close
 
 pytestmark = pytest.mark.gpu
@@ -94,12 +96,12 @@ def _compare(name, t, got, ref):
 
 @pytest.fixture(scope="module")
 def model_refs():
-    """per model: its bytes, 5 inputs and run_with_bmm of each"""
+    """per model: its bytes, 5 inputs and run_reference of each"""
     out = {}
     for name, build in B.MODELS.items():
         buf = build()
-        xs = [B.model_input(buf, seed=40 + i) for i in range(5)]
-        out[name] = (buf, xs, [B.run_with_bmm(buf, x) for x in xs])
+        xs = [R.zoo_input(buf, seed=40 + i) for i in range(5)]
+        out[name] = (buf, xs, [run_reference(buf, x) for x in xs])
     return out
 
 
@@ -159,8 +161,8 @@ def test_rank2_model_runs_unbatched(gpu_lib, monkeypatch):
     assert ex.MaxJobBatch(key) == 1
     t_in, t_out = ex.GetInputs(key)[0], ex.GetOutputs(key)[0]
     for seed in (1, 2):
-        x = B.model_input(buf, seed=seed)
-        ref = B.run_with_bmm(buf, x)
+        x = R.zoo_input(buf, seed=seed)
+        ref = run_reference(buf, x)
         ex.GetTensorView(key, t_in).GetData()[...] = x
         assert ex.ExecuteSubgraph(key).ok()
         np.testing.assert_array_equal(ex.GetTensorView(key, t_out).GetData().reshape(ref[t_out].shape), ref[t_out])
@@ -172,8 +174,8 @@ def test_engine_gpu_worker_only_serves_attention_block(gpu_lib, tmp_path, monkey
     from band_amd.engine import Engine, JobStatus, Model, SchedulerType, make_config, kBandOk
     monkeypatch.delenv("BAND_HIP_FUSION", raising=False)
     buf = B.MODELS["attention_17_48_3"]()
-    x = B.model_input(buf, seed=9)
-    ref = B.run_with_bmm(buf, x)
+    x = R.zoo_input(buf, seed=9)
+    ref = run_reference(buf, x)
     outputs = OModel(buf).outputs
     e = Engine(make_config([SchedulerType.kRoundRobin], [DeviceFlag.kGPU]))
     path = str(tmp_path / "attention_block.tflite")

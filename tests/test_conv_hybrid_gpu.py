@@ -119,7 +119,7 @@ def test_models_gpu_executor(gpu_lib, hybrid_conv, name, view_all):
     assert hybrid >= 1
     if view_all:
         for i, vals in enumerate(runs):
-            assert C.check_hybrid_conv_graph(om, vals, "%s run %d" % (name, i), gelu_ulps=16) == hybrid
+            assert H.check_graph_ops(om, vals, "%s run %d" % (name, i), gelu_ulps=16)[1]["conv"] == hybrid
         return
     _, full = H.run_executor(buf, feeds, DeviceFlag.kGPU, 1, view_all=True)
     for i, vals in enumerate(runs):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from tests import directed_harness as dh
+from tests.fixed_point import mbqm
 
 FAMILIES = [(f, d, kind) for f in ("fast", "two") for d in (np.int8, np.uint8) for kind in ("conv", "dw")]
 
@@ -78,7 +79,7 @@ def _applies(mutant, c, ref):
     if mutant == "clamp_first":
         return e.out_zp != 0
     if mutant == "wrap":  # some exact result has to leave the window
-        v = dh.requant_np(c.acc, e.mult, e.shift) + e.out_zp
+        v = mbqm(c.acc, e.mult, e.shift) + e.out_zp
         return bool(((v < e.amin) | (v > e.amax)).any())
     return True  # single, trunc1, floor2: any layer with a right shift
 
@@ -109,7 +110,7 @@ def test_half_up_differs_on_negative_ties_only():
     for c, _ in layers("fast", np.int8, "conv"):
         e = c.epi
         _, neg = dh.ties(c.acc, e.mult, e.shift)
-        diff = dh.requant_np(c.acc, e.mult, e.shift) != dh.requant_np(c.acc, e.mult, e.shift, "half_up")
+        diff = mbqm(c.acc, e.mult, e.shift) != mbqm(c.acc, e.mult, e.shift, "half_up")
         assert (diff == neg).all(), e.name
 
 

@@ -166,7 +166,7 @@ def test_models_on_cpu_executor_every_tensor(name):
     om, runs = H.run_executor(buf, [Y.model_feed(buf, seed=11)], DeviceFlag.kCPU, 0, view_all=True)
     hybrid = sum(Y.is_hybrid_fc(om, o) for o in om.operators)
     assert hybrid >= 1
-    assert Y.check_hybrid_graph(om, runs[0], name, gelu_ulps=1) == hybrid
+    assert H.check_graph_ops(om, runs[0], name, gelu_ulps=1)[1]["fc"] == hybrid
 
 
 def test_launch_kernels_of_a_hybrid_model():

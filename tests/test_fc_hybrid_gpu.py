@@ -83,7 +83,7 @@ def test_models_gpu_executor_every_tensor(gpu_lib, name):
     hybrid = sum(Y.is_hybrid_fc(om, o) for o in om.operators)
     assert hybrid >= 1
     for i, vals in enumerate(runs):
-        assert Y.check_hybrid_graph(om, vals, "%s run %d" % (name, i), gelu_ulps=16) == hybrid
+        assert H.check_graph_ops(om, vals, "%s run %d" % (name, i), gelu_ulps=16)[1]["fc"] == hybrid
 
 
 def test_models_job_batches(gpu_lib):

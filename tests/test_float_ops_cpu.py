@@ -34,7 +34,7 @@ def nonfinite_feed(om):
 def check_all_ops(buf, flag, worker, feed_fn, what):
     from oracle.tflite_fb import Model as OModel
     om, (vals,) = H.run_executor(buf, [feed_fn(OModel(buf))], flag, worker, view_all=True)
-    return H.check_graph_ops(om, vals, what)
+    return H.check_graph_ops(om, vals, what)[0]
 
 
 def check_outputs_only(buf, flag, worker, what):

@@ -12,6 +12,8 @@ from band_amd import DeviceFlag, HipModel, HipModelExecutor, SubgraphKey, _abi
 from band_amd.tflite_reader_py import read
 from band_amd.tflite_synth import mobilenet_v2
 from tests import grouped_models as G
+from tests import reindex_models as R
+from tests.graph_reference import run_reference
 
 RANDOM = G.random_cases()
 DIRECTED = G.directed_cases()
@@ -127,7 +129,7 @@ def non_constant_tensors(buf):
 
 
 def _run_every_tensor(buf, x, name):
-    ref = G.run_with_grouped(buf, x)
+    ref = run_reference(buf, x)
     m = _model(buf)
     ex = HipModelExecutor(0, 0, DeviceFlag.kCPU)
     assert ex.InvestigateModelSpec(m).unsupported_ops[DeviceFlag.kCPU] == set()
@@ -145,7 +147,7 @@ def _run_every_tensor(buf, x, name):
 @pytest.mark.parametrize("cid", [c[0] for c in RANDOM])
 def test_one_op_models_on_cpu_executor(refs, cid):
     """the model carries the case's scales, so the executor derives the case's
-    multipliers: run_with_grouped and grouped_ref agree, and the executor with both"""
+    multipliers: run_reference and grouped_ref agree, and the executor with both"""
     case, ref = refs[cid]
     buf = G.one_op_model(case)
     ex, key, vals = _run_every_tensor(buf, case.x, cid)
@@ -160,7 +162,7 @@ def test_shufflenet_on_cpu_executor_every_tensor(dtype):
     from oracle.tflite_fb import Model as OModel
     om = OModel(buf)
     assert sum(G.is_grouped(om, o) for o in om.operators) >= 5
-    x = G.R.zoo_input(buf, seed=4)
+    x = R.zoo_input(buf, seed=4)
     ex, key, ref = _run_every_tensor(buf, x, "shufflenet_v1")
     kernels = ex.LaunchKernels(key)
     assert sum(k.startswith("conv_grouped_host") for k in kernels) == sum(G.is_grouped(om, o) for o in om.operators)
@@ -172,14 +174,14 @@ def test_shufflenet_on_cpu_executor_every_tensor(dtype):
 @pytest.mark.parametrize("dtype", G.DTYPES, ids=["int8", "uint8"])
 def test_following_add_and_relu6_on_cpu(build, dtype):
     buf = build(dtype)
-    _run_every_tensor(buf, G.R.zoo_input(buf, seed=6), build.__name__)
+    _run_every_tensor(buf, R.zoo_input(buf, seed=6), build.__name__)
     # with only the outputs viewed the ADD / the unary ops fold into the conv
     m = _model(buf)
     ex = HipModelExecutor(0, 0, DeviceFlag.kCPU)
     assert ex.PrepareSubgraph(m).ok()
     key = SubgraphKey(0, 0)
-    x = G.R.zoo_input(buf, seed=7)
-    ref = G.run_with_grouped(buf, x)
+    x = R.zoo_input(buf, seed=7)
+    ref = run_reference(buf, x)
     ex.GetTensorView(key, ex.GetInputs(key)[0]).GetData()[...] = x
     assert ex.ExecuteSubgraph(key).ok()
     t = ex.GetOutputs(key)[0]
@@ -196,12 +198,12 @@ def test_job_batch_of_3_on_cpu():
     key = SubgraphKey(0, 0)
     st = ex.PrepareJobBatches(m, key, 3)
     assert st.ok(), st.message()
-    xs = [G.R.zoo_input(buf, seed=10 + s) for s in range(3)]
+    xs = [R.zoo_input(buf, seed=10 + s) for s in range(3)]
     for s, x in enumerate(xs):
         ex.GetJobSlotView(key, ex.GetInputs(key)[0], 3, s).GetData()[...] = x
     assert ex.ExecuteJobBatch(key, 3).ok()
     for s, x in enumerate(xs):
-        ref = G.run_with_grouped(buf, x)
+        ref = run_reference(buf, x)
         for t in ex.GetOutputs(key):
             np.testing.assert_array_equal(ex.GetJobSlotView(key, t, 3, s).GetData().reshape(ref[t].shape), ref[t])
 

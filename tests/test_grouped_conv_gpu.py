@@ -11,6 +11,8 @@ import pytest
 from band_amd import DeviceFlag, HipModel, HipModelExecutor, SubgraphKey
 from oracle.tflite_fb import Model as OModel
 from tests import grouped_models as G
+from tests import reindex_models as R
+from tests.graph_reference import run_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -108,12 +110,12 @@ def _same(name, t, got, ref):
 
 @pytest.fixture(scope="module")
 def shuffle_refs():
-    """per dtype: the model, 3 inputs and run_with_grouped of each"""
+    """per dtype: the model, 3 inputs and run_reference of each"""
     out = {}
     for dt in G.DTYPES:
         buf = G.shufflenet_small(dt)
-        xs = [G.R.zoo_input(buf, seed=20 + i) for i in range(3)]
-        out[np.dtype(dt).name] = (buf, xs, [G.run_with_grouped(buf, x) for x in xs])
+        xs = [R.zoo_input(buf, seed=20 + i) for i in range(3)]
+        out[np.dtype(dt).name] = (buf, xs, [run_reference(buf, x) for x in xs])
     return out
 
 
@@ -188,8 +190,8 @@ def test_following_add_and_relu6(gpu_lib, monkeypatch, build, dtype):
     monkeypatch.delenv("BAND_HIP_FUSION", raising=False)
     buf = build(dtype)
     om = OModel(buf)
-    xs = [G.R.zoo_input(buf, seed=30 + i) for i in range(3)]
-    refs = [G.run_with_grouped(buf, x) for x in xs]
+    xs = [R.zoo_input(buf, seed=30 + i) for i in range(3)]
+    refs = [run_reference(buf, x) for x in xs]
     for all_tensors in (False, True):
         m, ex, key = _exec(buf, 73)
         watch = [t.index for t in om.tensors if not t.is_const] if all_tensors else list(ex.GetOutputs(key))
@@ -220,8 +222,8 @@ def test_engine_one_gpu_worker_whole_model(gpu_lib, tmp_path, monkeypatch):
     assert e.RegisterModel(m)
     subs = e.GetSubgraphs(m)
     assert len(subs) == 1 and subs[0][0] == 0, subs  # one subgraph: the whole model on the GPU worker
-    x = G.R.zoo_input(buf, seed=50)
-    ref = G.run_with_grouped(buf, x)[om.outputs[0]]
+    x = R.zoo_input(buf, seed=50)
+    ref = run_reference(buf, x)[om.outputs[0]]
     t = e.CreateInputTensor(m, 0)
     t.data()[...] = x
     out = [e.CreateOutputTensor(m, 0)]
@@ -252,8 +254,8 @@ def test_engine_gpu_and_cpu_worker(gpu_lib, tmp_path, monkeypatch):
     assert {k[0] for k in e.GetSubgraphs(m)} == {0, 1}  # both workers prepared the model
     served = []
     for i, worker in enumerate((0, 1, 1, 0)):
-        x = G.R.zoo_input(buf, seed=40 + i)
-        ref = G.run_with_grouped(buf, x)[om.outputs[0]]
+        x = R.zoo_input(buf, seed=40 + i)
+        ref = run_reference(buf, x)[om.outputs[0]]
         t, out = e.CreateInputTensor(m, 0), [e.CreateOutputTensor(m, 0)]
         t.data()[...] = x
         opt = RequestOptionGetDefault()
@@ -281,8 +283,8 @@ def test_concurrent_execute_subgraph_coalesces(gpu_lib, monkeypatch):
     monkeypatch.setenv("BAND_HIP_COALESCE_LANES", "2")
     buf = G.shufflenet_small(np.int8)
     om = OModel(buf)
-    xs = [G.R.zoo_input(buf, seed=60 + i) for i in range(4)]
-    refs = [G.run_with_grouped(buf, x) for x in xs]
+    xs = [R.zoo_input(buf, seed=60 + i) for i in range(4)]
+    refs = [run_reference(buf, x) for x in xs]
     mid = 74
     m = HipModel(mid)
     assert m.FromBuffer(buf).ok()

@@ -15,6 +15,7 @@ from band_amd import DeviceFlag, HipModel, HipModelExecutor, SubgraphKey, _abi
 from band_amd.tflite_reader_py import read
 from band_amd.tflite_synth import OPT, ModelBuilder, Table, attention_block, vit_tiny
 from tests import encoder_models as E
+from tests.graph_reference import run_reference
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "band_amd", "csrc")
@@ -228,7 +229,7 @@ def model_refs():
     for name, build in E.MODELS.items():
         buf = build()
         xs = [E.model_input(buf, seed=40 + s) for s in range(3)]
-        out[name] = (buf, xs, [E.run_with_encoder_ops(buf, x) for x in xs])
+        out[name] = (buf, xs, [run_reference(buf, x) for x in xs])
     return out
 
 

@@ -157,9 +157,9 @@ def test_cpu_worker_ignores_the_variable(monkeypatch):
 
 
 def test_cpu_worker_runs_the_ten_host_kernels_with_the_variable_set(monkeypatch):
-    """and its result stays within the ops' bounds (tests.hybrid_models.check_hybrid_graph)"""
+    """and its result stays within the ops' bounds (tests.float_harness.check_graph_ops)"""
     from tests import hybrid_models as Y
     monkeypatch.setenv(L.FLAG, "1")
     buf = L.ln_qkv("symmetric")
     om, runs = H.run_executor(buf, [Y.model_feed(buf, seed=3)], DeviceFlag.kCPU, 0, view_all=True)
-    assert Y.check_hybrid_graph(om, runs[0], "ln_qkv kCPU") == 3
+    assert H.check_graph_ops(om, runs[0], "ln_qkv kCPU")[1]["fc"] == 3

@@ -8,7 +8,7 @@ layernorm_i8_kernel launch per LayerNorm - and every tensor viewed - nothing
 fused; BAND_HIP_FUSION=nolayernorm; job batches 2, 3, 5) and a GPU-only engine.
 
 References: the numpy restatements of tests.encoder_models (held against the
-real-valued functions in tests/test_layernorm_cpu.py) and run_with_encoder_ops;
+real-valued functions in tests/test_layernorm_cpu.py) and run_reference;
 every int8 / uint8 tensor is compared with assert_array_equal."""
 import ctypes
 
@@ -18,6 +18,7 @@ import pytest
 from band_amd import DeviceFlag, HipModel, HipModelExecutor, SubgraphKey, _abi
 from oracle.tflite_fb import Model as OModel
 from tests import encoder_models as E
+from tests.graph_reference import run_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -172,7 +173,7 @@ def model_refs():
     for name, build in E.MODELS.items():
         buf = build()
         xs = [E.model_input(buf, seed=60 + i) for i in range(5)]
-        out[name] = (buf, xs, [E.run_with_encoder_ops(buf, x) for x in xs])
+        out[name] = (buf, xs, [run_reference(buf, x) for x in xs])
     return out
 
 
@@ -283,7 +284,7 @@ def test_engine_gpu_worker_only_serves_encoder_block(gpu_lib, tmp_path, monkeypa
     monkeypatch.delenv("BAND_HIP_FUSION", raising=False)
     buf = E.MODELS["encoder_17_48_3_96"]()
     x = E.model_input(buf, seed=9)
-    ref = E.run_with_encoder_ops(buf, x)
+    ref = run_reference(buf, x)
     outputs = OModel(buf).outputs
     e = Engine(make_config([SchedulerType.kRoundRobin], [DeviceFlag.kGPU]))
     path = str(tmp_path / "encoder_block.tflite")

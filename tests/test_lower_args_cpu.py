@@ -13,8 +13,9 @@ import numpy as np
 import pytest
 
 from band_amd import DeviceFlag, HipModel, HipModelExecutor, SubgraphKey
-from tests import grouped_models as G
 from tests import lower_args_models as L
+from tests import reindex_models as R
+from tests.graph_reference import run_reference
 from tests.test_float_cpu import assert_float_close
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -45,8 +46,8 @@ def _model(buf):
 @pytest.fixture(scope="module")
 def families():
     buf = L.families()
-    xs = [G.R.zoo_input(buf, seed=40 + s) for s in range(2)]
-    return buf, xs, [G.run_with_grouped(buf, x) for x in xs]
+    xs = [R.zoo_input(buf, seed=40 + s) for s in range(2)]
+    return buf, xs, [run_reference(buf, x) for x in xs]
 
 
 def test_families_model_bit_exact_on_cpu(families):

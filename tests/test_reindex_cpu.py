@@ -13,6 +13,7 @@ from band_amd import DeviceFlag, HipModel, HipModelExecutor, SubgraphKey, _abi
 from band_amd.tflite_reader_py import OPTION_FIELDS, read
 from band_amd.tflite_synth import OPT, ModelBuilder, Table, int8_from_uint8
 from tests import reindex_models as R
+from tests.graph_reference import run_reference
 from tests.test_float_cpu import assert_float_close
 
 
@@ -288,7 +289,7 @@ def zoo_refs():
     for name, build in R.ZOO.items():
         buf = build()
         x = R.zoo_input(buf, seed=3)
-        out[name] = (buf, x, R.run_with_reindex(buf, x))
+        out[name] = (buf, x, run_reference(buf, x))
     return out
 
 
@@ -333,7 +334,7 @@ def test_job_batch_of_3_on_cpu(name):
         ex.GetJobSlotView(key, ex.GetInputs(key)[0], 3, s).GetData()[...] = x
     assert ex.ExecuteJobBatch(key, 3).ok()
     for s, x in enumerate(xs):
-        ref = R.run_with_reindex(buf, x)
+        ref = run_reference(buf, x)
         for t in ex.GetOutputs(key):
             _compare(name, t, ex.GetJobSlotView(key, t, 3, s).GetData().reshape(ref[t].shape), ref[t])
 
@@ -387,14 +388,14 @@ def test_job_batch_rule(name):
         ex.GetJobSlotView(key, t_in, 3, s).GetData()[...] = x
     assert ex.ExecuteJobBatch(key, 3).ok()
     for s, x in enumerate(xs):
-        ref = R.run_with_reindex(buf, x)[t_out]
+        ref = run_reference(buf, x)[t_out]
         np.testing.assert_array_equal(ex.GetJobSlotView(key, t_out, 3, s).GetData().reshape(ref.shape), ref)
 
 
 def test_batch_axis_transpose_still_runs():
     buf = R.batch_axis_transpose()
     x = R.zoo_input(buf, seed=1)
-    ref = R.run_with_reindex(buf, x)
+    ref = run_reference(buf, x)
     got, = _run_raw(buf, x)
     t = read(buf)["outputs"][0]
     np.testing.assert_array_equal(got.reshape(ref[t].shape), ref[t])
@@ -426,7 +427,7 @@ def test_python_reader_round_trips_the_option_tables():
     # rewritten through the reader: the uint8 detector head as int8
     buf = int8_from_uint8(R.detector_head(np.uint8))
     x = R.zoo_input(buf, seed=5)
-    ref = R.run_with_reindex(buf, x)
+    ref = run_reference(buf, x)
     got = _run_raw(buf, x)
     for t, g in zip(read(buf)["outputs"], got):
         np.testing.assert_array_equal(g.reshape(ref[t].shape), ref[t])

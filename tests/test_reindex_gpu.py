@@ -4,7 +4,7 @@ model zoo through the kGPU executor (eager and replayed, every tensor viewed
 and outputs only, job batches) and the engine.
 
 Reference: numpy (the contiguous copy of the view a case is made of), and
-tests.reindex_models.run_with_reindex for models.  Integer tensors are compared
+tests.graph_reference.run_reference for models.  Integer tensors are compared
 with assert_array_equal, float tensors at the tolerance of
 tests/test_float_cpu.py."""
 import ctypes
@@ -15,6 +15,7 @@ import pytest
 from band_amd import DeviceFlag, HipModel, HipModelExecutor, SubgraphKey
 from oracle.tflite_fb import Model as OModel
 from tests import reindex_models as R
+from tests.graph_reference import run_reference
 from tests.test_float_cpu import assert_float_close
 
 pytestmark = pytest.mark.gpu
@@ -90,12 +91,12 @@ def _compare(name, t, got, ref):
 
 @pytest.fixture(scope="module")
 def zoo_refs():
-    """per model: its bytes, 5 inputs and run_with_reindex of each"""
+    """per model: its bytes, 5 inputs and run_reference of each"""
     out = {}
     for name, build in R.ZOO.items():
         buf = build()
         xs = [R.zoo_input(buf, seed=20 + i) for i in range(5)]
-        out[name] = (buf, xs, [R.run_with_reindex(buf, x) for x in xs])
+        out[name] = (buf, xs, [run_reference(buf, x) for x in xs])
     return out
 
 
@@ -167,7 +168,7 @@ def test_batch_axis_transpose_runs_unbatched(gpu_lib, monkeypatch):
     t_in, t_out = ex.GetInputs(key)[0], ex.GetOutputs(key)[0]
     for seed in (1, 2):
         x = R.zoo_input(buf, seed=seed)
-        ref = R.run_with_reindex(buf, x)
+        ref = run_reference(buf, x)
         ex.GetTensorView(key, t_in).GetData()[...] = x
         assert ex.ExecuteSubgraph(key).ok()
         np.testing.assert_array_equal(ex.GetTensorView(key, t_out).GetData().reshape(ref[t_out].shape), ref[t_out])
@@ -180,7 +181,7 @@ def test_engine_gpu_worker_only_serves_detector_head(gpu_lib, tmp_path, monkeypa
     monkeypatch.delenv("BAND_HIP_FUSION", raising=False)
     buf = R.detector_head(np.int8)
     x = R.zoo_input(buf, seed=9)
-    ref = R.run_with_reindex(buf, x)
+    ref = run_reference(buf, x)
     outputs = OModel(buf).outputs
     e = Engine(make_config([SchedulerType.kRoundRobin], [DeviceFlag.kGPU]))
     path = str(tmp_path / "detector_head.tflite")

@@ -151,7 +151,7 @@ def main():
             # the values first: every op of a run with every tensor viewed
             os.environ["BAND_HIP_HYBRID_CONV"] = "1" if hc else "0"
             _, runs = H.run_executor(buf, [feed], DeviceFlag.kGPU, 1, view_all=True)
-            n = C.check_hybrid_conv_graph(om, runs[0], name + " " + tag, gelu_ulps=16)
+            n = H.check_graph_ops(om, runs[0], name + " " + tag, gelu_ulps=16)[1]["conv"]
             assert (n > 0) == bool(hc), (name, tag, n)
             m = HipModel(mid)
             assert m.FromBuffer(buf).ok()
