@@ -836,7 +836,7 @@ void CpuDetectionPostprocess(const CpuDetectionParams& p, CpuPool& pool) {
   p.out_num[0] = static_cast<float>(selected.size());
 }
 
-void CpuMean(const CpuMeanParams& p, CpuPool& pool) {
+void CpuMean(const bh_mean_params& p, CpuPool& pool) {
   pool.ParallelFor(p.outer * p.inner, [&](long lo, long hi) {
     for (long o = lo; o < hi; ++o) {
       const long a = o / p.inner, c = o % p.inner;

@@ -47,7 +47,7 @@ class CpuPool {
   bool stop_ = false;
 };
 
-// the launch kinds of model_executor.h with their host implementations
+// the launch kinds of launch.h with their host implementations
 void CpuConv(const bh_conv_params& p, CpuPool& pool);
 // grouped CONV_2D: p with the total channel counts, filters packed with K = K_g
 void CpuConvGrouped(const bh_conv_params& p, int groups, CpuPool& pool);
@@ -94,15 +94,8 @@ void CpuDetectionPostprocess(const CpuDetectionParams& p, CpuPool& pool);
 // [inner] and reduced over the middle.  Quantized (8-bit): TFLite 2.9.2
 // optimized_integer_ops::Mean / optimized_ops::Mean (4-D, keep_dims, axes
 // {1, 2}): acc = sum; MultiplyByQuantizedMultiplier(acc, multiplier, shift)
-// + bias, clamped to the type's range.  Float: sum / count.
-struct CpuMeanParams {
-  long outer, reduce, inner;
-  int type;  // 0 float32, 1 int8, 2 uint8
-  int32_t multiplier, shift, bias;
-  const void* input;
-  void* output;
-};
-void CpuMean(const CpuMeanParams& p, CpuPool& pool);
+// + bias, clamped to the type's range.  Float: sum / count.  bh_mean's host twin.
+void CpuMean(const bh_mean_params& p, CpuPool& pool);
 // MEAN of an 8-bit tensor over its last axis (bh_mean_rows's host twin):
 // reference_ops::Mean when p.exact, else reference_ops::QuantizedMeanOrSum in
 // float32, one rounding per operation (this library's host code is built with

@@ -1,6 +1,6 @@
 // Helpers shared by the HipModelExecutor translation units (model_executor.cc,
 // lower.cc, fusion.cc, fusion_transformer.cc, job_batch.cc): small accessors and the float32 op set.
-// The per-family Args functions are in lower_args.h.
+// The per-family Args functions are in lower_args.h, the launch record in launch.h.
 #pragma once
 
 #include <algorithm>

@@ -21,49 +21,56 @@ namespace {
 // the arena; constants are filtered out by the caller).  false: a launch kind
 // not analysed here - grouping treats it as a barrier.
 bool LaunchIo(const Launch& l, std::vector<const void*>* rd, std::vector<const void*>* wr) {
-  switch (l.kind) {
+  switch (l.kind()) {
     case Launch::kConv:
     case Launch::kConvGrouped:
-      *rd = {l.conv.input, l.conv.residual};
-      *wr = {l.conv.output};
+      *rd = {l.conv().input, l.conv().residual};
+      *wr = {l.conv().output};
       return true;
     case Launch::kDwConv:
-      *rd = {l.dw.input};
-      *wr = {l.dw.output};
+      *rd = {l.as<bh_dwconv_params>().input};
+      *wr = {l.as<bh_dwconv_params>().output};
       return true;
-    case Launch::kChain:
-      *rd = {l.chain.dw.input, l.chain.pw1.residual};
-      *wr = {l.chain.pw1.output, l.chain.has_pw2 ? l.chain.pw2.output : nullptr};
+    case Launch::kChain: {
+      const bh_chain_params& c = l.as<bh_chain_params>();
+      *rd = {c.dw.input, c.pw1.residual};
+      *wr = {c.pw1.output, c.has_pw2 ? c.pw2.output : nullptr};
       return true;
+    }
     case Launch::kIrb:
-      *rd = {l.irb.input};
-      *wr = {l.irb.output};
+      *rd = {l.as<bh_irb_params>().input};
+      *wr = {l.as<bh_irb_params>().output};
       return true;
     case Launch::kFc:
-      *rd = {l.fc.input};
-      *wr = {l.fc.output};
+      *rd = {l.as<bh_fc_params>().input};
+      *wr = {l.as<bh_fc_params>().output};
       return true;
     case Launch::kEltwise:
-      *rd = {l.elt.a, l.elt.b};
-      *wr = {l.elt.out};
+      *rd = {l.as<bh_eltwise_params>().a, l.as<bh_eltwise_params>().b};
+      *wr = {l.as<bh_eltwise_params>().out};
       return true;
     case Launch::kPool:
-      *rd = {l.pool.input};
-      *wr = {l.pool.output};
+      *rd = {l.as<bh_pool_params>().input};
+      *wr = {l.as<bh_pool_params>().output};
       return true;
     case Launch::kLutU8:
+      *rd = {l.as<LutArgs>().src};
+      *wr = {l.as<LutArgs>().dst};
+      return true;
     case Launch::kCopy:
-      *rd = {l.src};
-      *wr = {l.dst};
+      *rd = {l.as<CopyArgs>().src};
+      *wr = {l.as<CopyArgs>().dst};
       return true;
-    case Launch::kConcat:
-      rd->assign(l.concat.input, l.concat.input + l.concat.n_inputs);
-      *wr = {l.concat.output};
+    case Launch::kConcat: {
+      const bh_concat_params& c = l.as<bh_concat_params>();
+      rd->assign(c.input, c.input + c.n_inputs);
+      *wr = {c.output};
       return true;
+    }
     case Launch::kConvGroup:
       rd->clear();
       wr->clear();
-      for (const bh_conv_params& m : l.members) {
+      for (const bh_conv_params& m : l.as<ConvGroupArgs>().members) {
         rd->push_back(m.input);
         rd->push_back(m.residual);
         wr->push_back(m.output);
@@ -151,7 +158,7 @@ absl::Status HipModelExecutor::GroupConvs(PreparedSubgraph* sg) {
     for (int one = 1; one >= 0; --one) {
       std::vector<const Launch*> ms;
       for (const Pending& p : set) {
-        const bh_conv_params& c = p.l.conv;
+        const bh_conv_params& c = p.l.as<bh_conv_params>();
         const int is1 = c.k_h == 1 && c.k_w == 1 && c.pad_h == 0 && c.pad_w == 0;
         if (is1 == one) ms.push_back(&p.l);
       }
@@ -161,25 +168,25 @@ absl::Status HipModelExecutor::GroupConvs(PreparedSubgraph* sg) {
         continue;
       }
       Launch G;
-      G.kind = Launch::kConvGroup;
+      ConvGroupArgs& ga = G.Set<Launch::kConvGroup>();
       G.op_index = ms[0]->op_index;
       G.out_tensor = ms[0]->out_tensor;
       G.kernel = "conv_group_kernel";
       for (const Launch* m : ms) {
-        G.members.push_back(m->conv);
+        ga.members.push_back(m->as<bh_conv_params>());
         G.alg_bytes += m->alg_bytes;
         G.alg_ops += m->alg_ops;
       }
       std::vector<char> host(bh_conv_group_table_bytes(static_cast<int>(ms.size())));
-      if (host.empty() || bh_conv_group_plan(G.members.data(), static_cast<int>(ms.size()), host.data(),
-                                             &G.cgroup) != 0) {
+      if (host.empty() || bh_conv_group_plan(ga.members.data(), static_cast<int>(ms.size()), host.data(),
+                                             &ga.cgroup) != 0) {
         for (const Launch* m : ms) out.push_back(*m);  // not groupable after all: keep them
         continue;
       }
       auto blob = std::make_shared<DeviceBlob>(ordinal_, host.size());
       if (!blob->ok() || !blob->Upload(0, host.data(), host.size())) return HipErr(1, "upload conv group table");
       sg->consts.push_back(blob);
-      G.cgroup.table = blob->ptr();
+      ga.cgroup.table = blob->ptr();
       out.push_back(std::move(G));
     }
     set.clear();
@@ -195,12 +202,12 @@ absl::Status HipModelExecutor::GroupConvs(PreparedSubgraph* sg) {
     }
     const std::vector<Acc> rd = accesses(rdp);
     std::vector<Acc> wr = accesses(wrp);
-    if (l.kind == Launch::kConv) {
-      const Acc w = conv_write(l.conv);
+    if (l.kind() == Launch::kConv) {
+      const Acc w = conv_write(l.as<bh_conv_params>());
       wr.clear();
       if (w.slot >= 0) wr.push_back(w);
     }
-    const bool groupable = l.kind == Launch::kConv && bh_conv_group_ok(&l.conv) && !rd.empty() && !wr.empty();
+    const bool groupable = l.kind() == Launch::kConv && bh_conv_group_ok(&l.as<bh_conv_params>()) && !rd.empty() && !wr.empty();
     // pending convs this launch depends on (reads or overwrites their
     // output) or that depend on it (it overwrites their input)
     std::vector<Pending> hit, keep;
@@ -358,34 +365,34 @@ void HipModelExecutor::FuseBlocks(const HipModel& model, PreparedSubgraph* sg) {
     // candidate run: [E] D P
     const Launch* E = nullptr;
     size_t j = i;
-    if (L[i].kind == Launch::kConv && i + 2 < L.size() && L[i + 1].kind == Launch::kDwConv &&
-        L[i + 2].kind == Launch::kConv) {
+    if (L[i].kind() == Launch::kConv && i + 2 < L.size() && L[i + 1].kind() == Launch::kDwConv &&
+        L[i + 2].kind() == Launch::kConv) {
       E = &L[i];
       j = i + 1;
-    } else if (!(L[i].kind == Launch::kDwConv && i + 1 < L.size() && L[i + 1].kind == Launch::kConv)) {
+    } else if (!(L[i].kind() == Launch::kDwConv && i + 1 < L.size() && L[i + 1].kind() == Launch::kConv)) {
       out.push_back(L[i]);
       continue;
     }
     const Launch& D = L[j];
     const Launch& P = L[j + 1];
-    const bh_dwconv_params& dw = D.dw;
-    const bh_conv_params& pc = P.conv;
+    const bh_dwconv_params& dw = D.as<bh_dwconv_params>();
+    const bh_conv_params& pc = P.as<bh_conv_params>();
     bool ok = dw.in_xor == 0 && dw.w_zp == 0 && dw.depth_multiplier == 1 && dw.k_h == 3 && dw.k_w == 3 &&
               dw.dil_h == 1 && dw.dil_w == 1 && dw.stride_h == dw.stride_w && pc.in_xor == 0 && pc.w_zp == 0 &&
               Is1x1S1(pc) && pc.input == dw.output &&
               PrivateTensor(d, *sg, d.ops[D.op_index].outputs[0], P.op_index);
     if (ok && E) {
-      const bh_conv_params& ec = E->conv;
+      const bh_conv_params& ec = E->as<bh_conv_params>();
       ok = ec.in_xor == 0 && ec.w_zp == 0 && Is1x1S1(ec) && !ec.residual && ec.output == dw.input &&
            PrivateTensor(d, *sg, d.ops[E->op_index].outputs[0], D.op_index);
     }
     if (ok && pc.residual) {
-      const void* x = E ? E->conv.input : dw.input;
+      const void* x = E ? E->as<bh_conv_params>().input : dw.input;
       ok = pc.residual == x;
     }
     bh_irb_params q{};
     if (ok) {
-      const bh_conv_params* ec = E ? &E->conv : nullptr;
+      const bh_conv_params* ec = E ? &E->as<bh_conv_params>() : nullptr;
       q.batch = dw.batch;
       q.in_h = dw.in_h; q.in_w = dw.in_w;
       q.in_c = ec ? ec->in_c : dw.in_c;
@@ -441,8 +448,7 @@ void HipModelExecutor::FuseBlocks(const HipModel& model, PreparedSubgraph* sg) {
           }
           if (measured) {
             Launch F;
-            F.kind = Launch::kIrb;
-            F.irb = q;
+            F.Set<Launch::kIrb>(q);
             if (best.Offer(TimeLaunches({&F}, 10))) tile = t;
           }
         }
@@ -457,10 +463,9 @@ void HipModelExecutor::FuseBlocks(const HipModel& model, PreparedSubgraph* sg) {
       continue;
     }
     Launch F;
-    F.kind = Launch::kIrb;
+    F.Set<Launch::kIrb>(q);
     F.op_index = E ? E->op_index : D.op_index;
     F.out_tensor = P.out_tensor;
-    F.irb = q;
     F.kernel = "irb_kernel";
     // algorithmic bytes: block input + block output + all filters/tables
     const double x_bytes = static_cast<double>(q.batch) * q.in_h * q.in_w * q.in_c;
@@ -529,8 +534,9 @@ void HipModelExecutor::FuseChains(const HipModel& model, PreparedSubgraph* sg) {
   std::vector<Launch> out;
   const auto& L = sg->launches;
   for (size_t i = 0; i < L.size(); ++i) {
-    const bool head = L[i].kind == Launch::kDwConv && i + 1 < L.size() && L[i + 1].kind == Launch::kConv &&
-                      L[i + 1].conv.input == L[i].dw.output && !L[i].dw.out_table &&
+    const bool head = L[i].kind() == Launch::kDwConv && i + 1 < L.size() && L[i + 1].kind() == Launch::kConv &&
+                      L[i + 1].as<bh_conv_params>().input == L[i].as<bh_dwconv_params>().output &&
+                      !L[i].as<bh_dwconv_params>().out_table &&
                       PrivateTensor(d, *sg, L[i].out_tensor, L[i + 1].op_index);
     if (!head) {
       out.push_back(L[i]);
@@ -538,20 +544,23 @@ void HipModelExecutor::FuseChains(const HipModel& model, PreparedSubgraph* sg) {
     }
     const Launch& D = L[i];
     const Launch& P1 = L[i + 1];
+    const bh_dwconv_params& ddw = D.as<bh_dwconv_params>();
+    const bh_conv_params& p1 = P1.as<bh_conv_params>();
     const Launch* P2 = nullptr;
-    if (i + 2 < L.size() && L[i + 2].kind == Launch::kConv && L[i + 2].conv.input == P1.conv.output &&
-        Is1x1S1(L[i + 2].conv) && !L[i + 2].conv.residual)
-      P2 = &L[i + 2];
+    if (i + 2 < L.size() && L[i + 2].kind() == Launch::kConv) {
+      const bh_conv_params& p2 = L[i + 2].as<bh_conv_params>();
+      if (p2.input == p1.output && Is1x1S1(p2) && !p2.residual) P2 = &L[i + 2];
+    }
     bh_chain_params c{};
-    c.dw = D.dw;
-    c.pw1 = P1.conv;
+    c.dw = ddw;
+    c.pw1 = p1;
     c.px_blocks = 4;
     // the two candidate forms: with the second conv, and without it
     bh_chain_params c3 = c, c2 = c;
     bool ok3 = false;
     if (P2) {
       c3.has_pw2 = 1;
-      c3.pw2 = P2->conv;
+      c3.pw2 = P2->as<bh_conv_params>();
       if (PrivateTensor(d, *sg, P1.out_tensor, P2->op_index)) c3.pw1.output = nullptr;
       ok3 = bh_chain_lds_bytes(&c3) > 0;
     }
@@ -572,8 +581,8 @@ void HipModelExecutor::FuseChains(const HipModel& model, PreparedSubgraph* sg) {
     };
     char key[256];
     std::snprintf(key, sizeof(key), "ch%d:%d:%d:%dx%dx%d:s%dd%d:%d:%d:%d:%d:f%d%d%d%d", kChainTuneVersion, ordinal_,
-                  tune_batch_ > 0 ? tune_batch_ : D.dw.batch, D.dw.in_h, D.dw.in_w, D.dw.in_c, D.dw.stride_h, D.dw.dil_h,
-                  P1.conv.out_c, P1.conv.residual ? 1 : 0, ok3 ? c3.pw2.out_c : 0, ok3 && c3.pw1.output ? 1 : 0,
+                  tune_batch_ > 0 ? tune_batch_ : ddw.batch, ddw.in_h, ddw.in_w, ddw.in_c, ddw.stride_h, ddw.dil_h,
+                  p1.out_c, p1.residual ? 1 : 0, ok3 ? c3.pw2.out_c : 0, ok3 && c3.pw1.output ? 1 : 0,
                   opt_.no_tile_chain, opt_.no_deep_chain, opt_.no_split_chain, opt_.no_stage_chain);
     const bool forced = opt_.forced_chain != ForcedChain::kNone;
     const std::optional<int> cached = opt_.autotune && !forced ? TuneLookup(key) : std::nullopt;
@@ -596,8 +605,7 @@ void HipModelExecutor::FuseChains(const HipModel& model, PreparedSubgraph* sg) {
         if (!measured || FilteredOut(f, opt_.no_tile_chain, opt_.no_deep_chain, opt_.no_split_chain, opt_.no_stage_chain)) return;
         for (f.launches = 3; f.launches >= 2; --f.launches) {
           Launch F;
-          F.kind = Launch::kChain;
-          if (!HasLaunches(f, f.launches) || !instantiate(f, &F.chain)) continue;
+          if (!HasLaunches(f, f.launches) || !instantiate(f, &F.Set<Launch::kChain>())) continue;
           const double us = TimeLaunches({&F}, 10);
           // the 2-launch form leaves the second 1x1 a launch of its own
           const double total = us + (f.launches == 2 && ok3 ? u_p2 : 0.0);
@@ -608,27 +616,27 @@ void HipModelExecutor::FuseChains(const HipModel& model, PreparedSubgraph* sg) {
       else form = ForcedForm(ForcedChain::kPlain, ok3 ? c3 : c2);  // no device timing: 3 launches when they apply
     }
     Launch F;
-    F.kind = Launch::kChain;
+    bh_chain_params& fc = F.Set<Launch::kChain>();
     F.op_index = D.op_index;
-    if (form.launches == 0 || !instantiate(form, &F.chain)) {
+    if (form.launches == 0 || !instantiate(form, &fc)) {
       out.push_back(L[i]);
       continue;
     }
-    if (F.chain.tile_blob) sg->consts.push_back(form.launches == 3 ? blob3 : blob2);  // owned by the subgraph
+    if (fc.tile_blob) sg->consts.push_back(form.launches == 3 ? blob3 : blob2);  // owned by the subgraph
     const bool three = form.launches == 3;
     F.out_tensor = three ? P2->out_tensor : P1.out_tensor;
-    F.kernel = F.chain.dense   ? "chain_dense_kernel"
-               : F.chain.stage ? "chain_stage_kernel"
-                               : (F.chain.tile ? "chain_tile_kernel" : "chain_kernel");
-    const bh_dwconv_params& dw = F.chain.dw;
-    const bh_conv_params& a = F.chain.pw1;
+    F.kernel = fc.dense   ? "chain_dense_kernel"
+               : fc.stage ? "chain_stage_kernel"
+                          : (fc.tile ? "chain_tile_kernel" : "chain_kernel");
+    const bh_dwconv_params& dw = fc.dw;
+    const bh_conv_params& a = fc.pw1;
     const double px = static_cast<double>(dw.batch) * dw.out_h * dw.out_w;
     F.alg_bytes = static_cast<double>(dw.batch) * dw.in_h * dw.in_w * dw.in_c + 9.0 * dw.out_c + 28.0 * dw.out_c +
                   (a.residual ? px * a.out_c : 0.0) + (a.output ? px * a.out_c : 0.0) +
                   static_cast<double>(a.out_c) * a.in_c + 12.0 * a.out_c;
     F.alg_ops = D.alg_ops + P1.alg_ops;
     if (three) {
-      const bh_conv_params& b = F.chain.pw2;
+      const bh_conv_params& b = fc.pw2;
       F.alg_bytes += px * b.out_c + static_cast<double>(b.out_c) * b.in_c + 12.0 * b.out_c;
       F.alg_ops += P2->alg_ops;
       if (!a.output) sg->fused_tensors.insert(P1.out_tensor);
@@ -642,25 +650,28 @@ void HipModelExecutor::FuseChains(const HipModel& model, PreparedSubgraph* sg) {
 
 namespace {
 void** OutSlot(Launch& l) {
-  switch (l.kind) {
-    case Launch::kChain: return l.chain.has_pw2 ? &l.chain.pw2.output : &l.chain.pw1.output;
+  switch (l.kind()) {
+    case Launch::kChain: {
+      bh_chain_params& c = l.as<bh_chain_params>();
+      return c.has_pw2 ? &c.pw2.output : &c.pw1.output;
+    }
     case Launch::kConv:
-    case Launch::kConvGrouped: return &l.conv.output;
-    case Launch::kDwConv: return &l.dw.output;
-    case Launch::kFc: return &l.fc.output;
-    case Launch::kEltwise: return &l.elt.out;
-    case Launch::kPool: return &l.pool.output;
-    case Launch::kIrb: return &l.irb.output;
-    case Launch::kLutU8: return &l.dst;
+    case Launch::kConvGrouped: return &l.conv().output;
+    case Launch::kDwConv: return &l.as<bh_dwconv_params>().output;
+    case Launch::kFc: return &l.as<bh_fc_params>().output;
+    case Launch::kEltwise: return &l.as<bh_eltwise_params>().out;
+    case Launch::kPool: return &l.as<bh_pool_params>().output;
+    case Launch::kIrb: return &l.as<bh_irb_params>().output;
+    case Launch::kLutU8: return &l.as<LutArgs>().dst;
     default: return nullptr;
   }
 }
 const void** TableSlot(Launch& l) {
-  switch (l.kind) {
+  switch (l.kind()) {
     case Launch::kConv:
-    case Launch::kConvGrouped: return l.conv.residual ? nullptr : &l.conv.out_table;  // + ADD epilogue: keep apart
-    case Launch::kDwConv: return &l.dw.out_table;
-    case Launch::kFc: return &l.fc.out_table;
+    case Launch::kConvGrouped: return l.conv().residual ? nullptr : &l.conv().out_table;  // + ADD epilogue: keep apart
+    case Launch::kDwConv: return &l.as<bh_dwconv_params>().out_table;
+    case Launch::kFc: return &l.as<bh_fc_params>().out_table;
     default: return nullptr;
   }
 }
@@ -697,22 +708,23 @@ void HipModelExecutor::FuseGlue(const HipModel& model, PreparedSubgraph* sg) {
   // hand it on to its producers in (2))
   for (size_t i = 0; i < sg->launches.size(); ++i) {
     Launch& L = sg->launches[i];
-    if (L.kind != Launch::kLutU8) continue;
-    const int j = producer_of(i, L.src);
+    if (L.kind() != Launch::kLutU8) continue;
+    const LutArgs& lut = L.as<LutArgs>();
+    const int j = producer_of(i, lut.src);
     if (j < 0 || dead[j]) continue;
     Launch& P = sg->launches[j];
     std::vector<int> chain;
-    if (P.kind == Launch::kConcat) {
-      bool plain = P.concat.output == L.src;
-      for (int k = 0; k < P.concat.n_inputs && plain; ++k) plain = P.concat.table[k] == nullptr;
+    if (bh_concat_params* pc = P.get_if<bh_concat_params>()) {
+      bool plain = pc->output == lut.src;
+      for (int k = 0; k < pc->n_inputs && plain; ++k) plain = pc->table[k] == nullptr;
       if (!plain || !private_chain(P.out_tensor, L.op_index, &chain)) continue;
-      for (int k = 0; k < P.concat.n_inputs; ++k) P.concat.table[k] = L.table;
-      P.concat.output = L.dst;
+      for (int k = 0; k < pc->n_inputs; ++k) pc->table[k] = lut.table;
+      pc->output = lut.dst;
     } else {
       const void** ts = TableSlot(P);
       if (!ts || *ts || !private_chain(P.out_tensor, L.op_index, &chain)) continue;
-      *ts = L.table;
-      *OutSlot(P) = L.dst;
+      *ts = lut.table;
+      *OutSlot(P) = lut.dst;
     }
     P.out_tensor = L.out_tensor;
     P.alg_bytes += 0;  // same bytes: the table gather happens on the stored value
@@ -726,39 +738,41 @@ void HipModelExecutor::FuseGlue(const HipModel& model, PreparedSubgraph* sg) {
   // at the concat's row stride (bh_conv_params.out_img_stride); an input
   // copy table moves into the producer's epilogue table
   for (size_t i = 0; i < sg->launches.size(); ++i) {
-    Launch& C = sg->launches[i];
-    if (C.kind != Launch::kConcat) continue;
-    const bool strided = C.concat.outer != 1;
+    const Launch& C = sg->launches[i];
+    if (C.kind() != Launch::kConcat) continue;
+    const bh_concat_params& cc = C.as<bh_concat_params>();
+    const bool strided = cc.outer != 1;
     if (strided && device_flag_ != DeviceFlag::kGPU) continue;  // (the host conv stores dense images)
     long total_row = 0;
-    for (int k = 0; k < C.concat.n_inputs; ++k) total_row += C.concat.row[k];
+    for (int k = 0; k < cc.n_inputs; ++k) total_row += cc.row[k];
     bool ok = true;
-    std::vector<int> prod(C.concat.n_inputs, -1);
+    std::vector<int> prod(cc.n_inputs, -1);
     std::vector<int> chain;
-    for (int k = 0; k < C.concat.n_inputs && ok; ++k) {
-      const int j = producer_of(i, C.concat.input[k]);
+    for (int k = 0; k < cc.n_inputs && ok; ++k) {
+      const int j = producer_of(i, cc.input[k]);
       ok = j >= 0 && !dead[j] && OutSlot(sg->launches[j]) &&
            private_chain(sg->launches[j].out_tensor, C.op_index, &chain);
-      if (ok && C.concat.table[k]) {
+      if (ok && cc.table[k]) {
         const void** ts = TableSlot(sg->launches[j]);
         ok = ts && *ts == nullptr;
       }
       if (ok && strided) {
         const Launch& P = sg->launches[j];
-        ok = P.kind == Launch::kConv && P.conv.out_img_stride == 0 && P.conv.batch == C.concat.outer &&
-             static_cast<long>(P.conv.out_h) * P.conv.out_w * P.conv.out_c == C.concat.row[k];
+        const bh_conv_params* pc = P.get_if<bh_conv_params>();  // kConv alone
+        ok = pc && pc->out_img_stride == 0 && pc->batch == cc.outer &&
+             static_cast<long>(pc->out_h) * pc->out_w * pc->out_c == cc.row[k];
       }
       if (ok) prod[k] = j;
       for (int kk = 0; kk < k && ok; ++kk) ok = prod[kk] != j;  // one producer per slice
     }
     if (!ok) continue;
     long off = 0;
-    for (int k = 0; k < C.concat.n_inputs; ++k) {
+    for (int k = 0; k < cc.n_inputs; ++k) {
       Launch& P = sg->launches[prod[k]];
-      *OutSlot(P) = static_cast<char*>(C.concat.output) + off;
-      if (C.concat.table[k]) *TableSlot(P) = C.concat.table[k];
-      if (strided) P.conv.out_img_stride = total_row;
-      off += C.concat.row[k];
+      *OutSlot(P) = static_cast<char*>(cc.output) + off;
+      if (cc.table[k]) *TableSlot(P) = cc.table[k];
+      if (strided) P.as<bh_conv_params>().out_img_stride = total_row;
+      off += cc.row[k];
     }
     for (int t : chain) sg->fused_tensors.insert(t);
     sg->fused_ops.insert(C.op_index);
@@ -770,29 +784,29 @@ void HipModelExecutor::FuseGlue(const HipModel& model, PreparedSubgraph* sg) {
   // refuses geometries whose blended rows do not fit LDS: those keep both.
   for (size_t i = 0; opt_.allow_argmax && device_flag_ == DeviceFlag::kGPU && i < sg->launches.size(); ++i) {
     Launch& A = sg->launches[i];
-    if (A.kind != Launch::kArgMinMax || A.argmm.in_type != BH_ARG_I8 || A.argmm.inner != 1) continue;
+    const bh_argminmax_params* am = A.get_if<bh_argminmax_params>();
+    if (!am || am->in_type != BH_ARG_I8 || am->inner != 1) continue;
     int j = -1;
-    for (size_t k = i; k-- > 0 && j < 0;)
-      if (!dead[k] && sg->launches[k].kind == Launch::kResizeBilinear && sg->launches[k].rbil.output == A.argmm.input)
-        j = static_cast<int>(k);
+    for (size_t k = i; k-- > 0 && j < 0;) {
+      const bh_resize_bilinear_params* r = sg->launches[k].get_if<bh_resize_bilinear_params>();
+      if (!dead[k] && r && r->output == am->input) j = static_cast<int>(k);
+    }
     if (j < 0) continue;
-    Launch& R = sg->launches[j];
+    const Launch& R = sg->launches[j];
+    const bh_resize_bilinear_params& rb = R.as<bh_resize_bilinear_params>();
     const int t = R.out_tensor;
-    if (A.argmm.axis_len != R.rbil.channels ||
-        A.argmm.outer != static_cast<long>(R.rbil.batch) * R.rbil.out_h * R.rbil.out_w)
-      continue;
+    if (am->axis_len != rb.channels || am->outer != static_cast<long>(rb.batch) * rb.out_h * rb.out_w) continue;
     if (!PrivateTensor(d, *sg, t, A.op_index)) continue;
     bh_resize_argminmax_params q{};
-    q.rz = R.rbil;
-    q.rz.output = A.argmm.output;
-    q.is_min = A.argmm.is_min;
-    q.out_bytes = A.argmm.out_bytes;
+    q.rz = rb;
+    q.rz.output = am->output;
+    q.is_min = am->is_min;
+    q.out_bytes = am->out_bytes;
     if (bh_resize_bilinear_argminmax_i8_ok(&q) != 0) continue;
     // reads the small map, writes the indices; the resized tensor is gone
-    A.alg_bytes = static_cast<double>(R.rbil.batch) * R.rbil.in_h * R.rbil.in_w * R.rbil.channels +
-                  static_cast<double>(A.argmm.outer) * q.out_bytes;
-    A.kind = Launch::kResizeArgMinMax;
-    A.rzarg = q;
+    A.alg_bytes = static_cast<double>(rb.batch) * rb.in_h * rb.in_w * rb.channels +
+                  static_cast<double>(am->outer) * q.out_bytes;
+    A.Set<Launch::kResizeArgMinMax>(q);  // (replaces the payload `am` points at)
     A.kernel = "resize_bilinear_argminmax_kernel";
     sg->fused_tensors.insert(t);
     sg->fused_ops.insert(R.op_index);

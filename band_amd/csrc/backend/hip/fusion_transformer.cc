@@ -36,7 +36,7 @@ bool HipModelExecutor::MatchLayerNorm(const TflModel& d, const PreparedSubgraph&
   std::set<int> inside;
   for (int k = 0; k < 10; ++k) {
     const Launch& l = ls[i + k];
-    if (l.kind != kinds[k] || l.op_index < 0) return false;
+    if (l.kind() != kinds[k] || l.op_index < 0) return false;
     const TflOperator& op = d.ops[l.op_index];
     if (op.builtin != kPattern[k] || op.outputs.size() != 1 || l.out_tensor != op.outputs[0] ||
         op.inputs.size() < (k == 4 ? 1u : 2u))
@@ -109,27 +109,29 @@ void HipModelExecutor::FuseLayerNorm(const HipModel& model, PreparedSubgraph* sg
     for (int t : {n.m, n.v, n.e, n.r})
       ok = ok && d.tensors[t].num_elements() * static_cast<size_t>(n.depth) == tx.num_elements();
     if (!ok) return false;
-    F->kind = Launch::kLayerNorm;
-    bh_layernorm_params& p = F->ln;
-    p.rows = l[0].mrows.rows;
+    auto block = std::make_shared<bh_layernorm_params>();
+    bh_layernorm_params& p = *block;
+    auto elt = [&](int k) -> const bh_eltwise_params& { return l[k].as<bh_eltwise_params>(); };
+    p.mean_x = l[0].as<bh_mean_rows_params>();
+    p.rows = p.mean_x.rows;
     p.depth = static_cast<int>(n.depth);
-    p.mean_x = l[0].mrows;
-    p.sqdiff = l[1].elt;
-    p.mean_d = l[2].mrows;
-    p.add_eps = l[3].elt;
-    p.rsqrt_table = l[4].table;
-    p.mul_gamma = l[5].elt;
-    p.mul_x = l[6].elt;
-    p.mul_m = l[7].elt;
-    p.sub_beta = l[8].elt;
-    p.add_out = l[9].elt;
+    p.sqdiff = elt(1);
+    p.mean_d = l[2].as<bh_mean_rows_params>();
+    p.add_eps = elt(3);
+    p.rsqrt_table = l[4].as<LutArgs>().table;
+    p.mul_gamma = elt(5);
+    p.mul_x = elt(6);
+    p.mul_m = elt(7);
+    p.sub_beta = elt(8);
+    p.add_out = elt(9);
     p.eps_q = static_cast<int8_t>(d.tensors[n.eps].data[0]);
-    p.input = l[0].mrows.input;
-    p.gamma = l[5].elt.b;
-    p.beta = l[8].elt.a;
-    p.output = l[9].elt.out;
+    p.input = p.mean_x.input;
+    p.gamma = p.mul_gamma.b;
+    p.beta = p.sub_beta.a;
+    p.output = p.add_out.out;
     if (p.mean_d.rows != p.rows || bh_layernorm_i8_check(&p) != 0) return false;
     F->kernel = bh_layernorm_i8_kernel(&p);
+    F->Set<Launch::kLayerNorm>({std::move(block)});
     F->alg_bytes = 2.0 * static_cast<double>(tx.num_elements()) + 2.0 * n.depth + 256.0;
     return true;
   });
@@ -157,9 +159,10 @@ void HipModelExecutor::FuseLayerNormF32(const HipModel& model, PreparedSubgraph*
                                BH_ELTF_ADD};
   const float inf = std::numeric_limits<float>::infinity();
   FuseTenOps(d, sg, kKinds, [&](const LnMatch& n, const Launch* l, Launch* F) {
-    bool ok = l[4].unary_kind == BH_UNARY_RSQRT && d.tensors[n.eps].data_size >= 4;
+    auto eltf = [&](int k) -> const bh_eltwise_f32_params& { return l[k].as<bh_eltwise_f32_params>(); };
+    bool ok = l[4].as<UnaryF32Args>().kind == BH_UNARY_RSQRT && d.tensors[n.eps].data_size >= 4;
     for (int k = 0; k < 10; ++k)
-      ok = ok && (kElt[k] < 0 || (l[k].eltf.kind == kElt[k] && l[k].eltf.act_min == -inf && l[k].eltf.act_max == inf));
+      ok = ok && (kElt[k] < 0 || (eltf(k).kind == kElt[k] && eltf(k).act_min == -inf && eltf(k).act_max == inf));
     for (int t : {n.x, n.m, n.dd, n.v, n.e, n.r, n.g, n.a, n.b, n.c, n.y, n.eps, n.gamma, n.beta})
       ok = ok && d.tensors[t].type == DataType::kFloat32;
     // the row statistics keep the input's rank with a last axis of 1 (keep_dims)
@@ -169,21 +172,20 @@ void HipModelExecutor::FuseLayerNormF32(const HipModel& model, PreparedSubgraph*
     for (int t : {n.m, n.v, n.e, n.r}) ok = ok && d.tensors[t].shape == stat;
     // MEAN over the last axis alone: rows x depth x 1
     for (int k : {0, 2}) {
-      const CpuMeanParams& q = l[k].mean;
+      const bh_mean_params& q = l[k].as<bh_mean_params>();
       ok = ok && q.type == 0 && q.inner == 1 && q.reduce == n.depth &&
            q.outer * n.depth == static_cast<long>(tx.num_elements());
     }
     if (!ok) return false;
-    F->kind = Launch::kLayerNormF32;
-    bh_layernorm_f32_params& p = F->lnf;
-    p.rows = l[0].mean.outer;
+    bh_layernorm_f32_params& p = F->Set<Launch::kLayerNormF32>();
+    p.rows = l[0].as<bh_mean_params>().outer;
     p.depth = static_cast<int>(n.depth);
     std::memcpy(&p.eps, d.tensors[n.eps].data, sizeof(float));
-    p.input = static_cast<const float*>(l[0].mean.input);
-    p.gamma = l[5].eltf.b;
-    p.beta = l[8].eltf.a;
-    p.output = l[9].eltf.out;
-    if (l[6].eltf.a != p.input || bh_layernorm_f32_check(&p) != 0) return false;
+    p.input = static_cast<const float*>(l[0].as<bh_mean_params>().input);
+    p.gamma = eltf(5).b;
+    p.beta = eltf(8).a;
+    p.output = eltf(9).out;
+    if (eltf(6).a != p.input || bh_layernorm_f32_check(&p) != 0) return false;
     F->kernel = bh_layernorm_f32_kernel(&p);
     F->alg_bytes = 8.0 * static_cast<double>(tx.num_elements()) + 8.0 * n.depth;
     return true;
@@ -205,20 +207,21 @@ void HipModelExecutor::FoldLayerNormQuant(const HipModel& model, PreparedSubgrap
   std::vector<Launch>& ls = sg->launches;
   std::vector<bool> dead(ls.size(), false);
   for (size_t i = 0; i < ls.size(); ++i) {
-    if (ls[i].kind != Launch::kLayerNormF32 || ls[i].lnf.q) continue;
-    bh_layernorm_f32_params& p = ls[i].lnf;
+    bh_layernorm_f32_params* lnf = ls[i].get_if<bh_layernorm_f32_params>();
+    if (!lnf || lnf->q) continue;
+    bh_layernorm_f32_params& p = *lnf;
     const int y = ls[i].out_tensor;
     std::set<int> folded;  // ops whose quantisation this launch takes over
     const bh_dynquant_params* first = nullptr;
     for (size_t j = i + 1; j < ls.size(); ++j) {
       const Launch& q = ls[j];
-      if (q.kind != Launch::kDynQuantRows || dead[j] || q.op_index < 0) continue;
+      const bh_dynquant_params* dq = q.get_if<bh_dynquant_params>();
+      if (!dq || dead[j] || q.op_index < 0) continue;
       const TflOperator& op = d.ops[q.op_index];
-      if (op.inputs.empty() || op.inputs[0] != y || q.dq.input != p.output || q.dq.rows != p.rows ||
-          q.dq.depth != p.depth)
+      if (op.inputs.empty() || op.inputs[0] != y || dq->input != p.output || dq->rows != p.rows || dq->depth != p.depth)
         continue;
-      if (first && (q.dq.asymmetric != 0) != (first->asymmetric != 0)) continue;
-      if (!first) first = &q.dq;
+      if (first && (dq->asymmetric != 0) != (first->asymmetric != 0)) continue;
+      if (!first) first = dq;
       folded.insert(q.op_index);
       dead[j] = true;
     }
@@ -228,10 +231,10 @@ void HipModelExecutor::FoldLayerNormQuant(const HipModel& model, PreparedSubgrap
     p.offset = first->offset;
     p.asymmetric = first->asymmetric;
     for (Launch& l : ls)
-      if (l.kind == Launch::kFcHybrid && folded.count(l.op_index)) {
-        l.fch.q = p.q;
-        l.fch.in_scale = p.scale;
-        l.fch.in_offset = p.offset;
+      if (bh_fc_hybrid_params* fch = folded.count(l.op_index) ? l.get_if<bh_fc_hybrid_params>() : nullptr) {
+        fch->q = p.q;
+        fch->in_scale = p.scale;
+        fch->in_offset = p.offset;
       }
     bool needed = KeptOutside(d, *sg, y);
     for (int consumer : consumers_[y]) needed = needed || !folded.count(consumer);
@@ -299,7 +302,7 @@ void HipModelExecutor::FuseAttention(const HipModel& model, PreparedSubgraph* sg
                        const void** src) -> int {
     for (size_t j = before; j-- > 0;) {
       const Launch& r = ls[j];
-      if (dead[j] || r.kind != Launch::kReindex || r.reindex.output != ptr || r.out_tensor != t) continue;
+      if (dead[j] || r.kind() != Launch::kReindex || r.as<bh_reindex_params>().output != ptr || r.out_tensor != t) continue;
       const TflOperator& op = d.ops[r.op_index];
       std::vector<int64_t> perm;
       if (!head_perm(op, &perm) || op.outputs[0] != t || !PrivateTensor(d, *sg, t, reader)) return -1;
@@ -311,14 +314,14 @@ void HipModelExecutor::FuseAttention(const HipModel& model, PreparedSubgraph* sg
         st.push_back(xs[p]);
       }
       operand(dm, st, bstride, row);
-      *src = r.reindex.input;
+      *src = r.as<bh_reindex_params>().input;
       return static_cast<int>(j);
     }
     return -1;
   };
   for (size_t i = 0; i + 2 < ls.size(); ++i) {
     const Launch &A = ls[i], &S = ls[i + 1], &B = ls[i + 2];
-    if (A.kind != Launch::kBatchMatMul || S.kind != Launch::kSoftmax || B.kind != Launch::kBatchMatMul) continue;
+    if (A.kind() != Launch::kBatchMatMul || S.kind() != Launch::kSoftmax || B.kind() != Launch::kBatchMatMul) continue;
     if (A.op_index < 0 || S.op_index < 0 || B.op_index < 0) continue;
     const TflOperator &oa = d.ops[A.op_index], &os = d.ops[S.op_index], &ob = d.ops[B.op_index];
     if (oa.builtin != kTflBatchMatMul || os.builtin != kTflSoftmax || ob.builtin != kTflBatchMatMul) continue;
@@ -330,18 +333,16 @@ void HipModelExecutor::FuseAttention(const HipModel& model, PreparedSubgraph* sg
       continue;
     if (d.tensors[sc].type != DataType::kInt8 || d.tensors[pr].type != DataType::kInt8) continue;
     if (!PrivateTensor(d, *sg, sc, S.op_index) || !PrivateTensor(d, *sg, pr, B.op_index)) continue;
-    const bh_batch_matmul_params &a = A.bmm, &b = B.bmm;
-    const bh_softmax_params& s = S.softmax;
+    const bh_batch_matmul_params &a = A.as<bh_batch_matmul_params>(), &b = B.as<bh_batch_matmul_params>();
+    const bh_softmax_params& s = S.as<bh_softmax_params>();
     if (s.input != a.out || s.output != b.lhs || !s.is_signed || s.depth != a.n ||
         s.rows != static_cast<long>(a.batch[0]) * a.batch[1] * a.m)
       continue;
     if (b.batch[0] != a.batch[0] || b.batch[1] != a.batch[1] || b.m != a.m || b.k != a.n) continue;
     Launch F;
-    F.kind = Launch::kAttention;
     F.op_index = A.op_index;
     F.out_tensor = ctx;
-    bh_attention_params& p = F.attn;
-    p = bh_attention_params{};
+    bh_attention_params& p = F.Set<Launch::kAttention>();
     p.batch[0] = a.batch[0];
     p.batch[1] = a.batch[1];
     p.rows = a.m;
@@ -379,7 +380,7 @@ void HipModelExecutor::FuseAttention(const HipModel& model, PreparedSubgraph* sg
     int jo = -1;
     for (size_t j = i + 3; j < ls.size() && jo < 0; ++j) {
       const Launch& r = ls[j];
-      if (r.kind != Launch::kReindex || r.reindex.input != b.out) continue;
+      if (r.kind() != Launch::kReindex || r.as<bh_reindex_params>().input != b.out) continue;
       const TflOperator& op = d.ops[r.op_index];
       std::vector<int64_t> perm;
       if (!head_perm(op, &perm) || op.inputs[0] != ctx || r.out_tensor != op.outputs[0] ||
@@ -393,7 +394,7 @@ void HipModelExecutor::FuseAttention(const HipModel& model, PreparedSubgraph* sg
         st[perm[k]] = ys[k];
       }
       operand(dm, st, p.out_bstride, &p.out_row_stride);
-      p.out = r.reindex.output;
+      p.out = r.as<bh_reindex_params>().output;
       F.out_tensor = r.out_tensor;
       jo = static_cast<int>(j);
     }

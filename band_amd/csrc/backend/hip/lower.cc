@@ -36,15 +36,13 @@ ConvQuant QuantOf(const TflModel& d, const ConvGeometry& g, const TflTensor& out
 // operands (Bt rows are K-contiguous, bias_eff identical).  True when *L was
 // rewritten.
 bool GemvAsFc(Launch* L) {
-  const bh_conv_params c = L->conv;
+  const bh_conv_params c = L->as<bh_conv_params>();
   const long M = static_cast<long>(c.batch) * c.out_h * c.out_w;
   if (c.k_h != 1 || c.k_w != 1 || c.stride_h != 1 || c.stride_w != 1 || M > 4) return false;
   Launch F;
-  F.kind = Launch::kFc;
   F.op_index = L->op_index;
   F.out_tensor = L->out_tensor;
-  bh_fc_params& f = F.fc;
-  f = bh_fc_params{};
+  bh_fc_params& f = F.Set<Launch::kFc>();
   f.rows = static_cast<int>(M); f.depth = c.in_c; f.depth_pad = c.k_pad; f.units = c.out_c;
   f.in_xor = c.in_xor; f.in_zp = c.in_zp; f.w_zp = c.w_zp; f.out_zp = c.out_zp;
   f.act_min = c.act_min; f.act_max = c.act_max; f.input = c.input; f.output = c.output;
@@ -151,8 +149,9 @@ absl::Status HipModelExecutor::PackedConv(const HipModel& model, int oi, const C
     return absl::OkStatus();
   }, &blob));
   const int32_t* tab = reinterpret_cast<const int32_t*>(static_cast<char*>(blob->ptr()) + wbytes);
-  bh_conv_params& p = L->conv;
-  p = bh_conv_params{};
+  if (g.groups == 1) L->Set<Launch::kConv>();
+  else L->Set<Launch::kConvGrouped>({bh_conv_params{}, g.groups});
+  bh_conv_params& p = L->conv();
   SetGeometry(g, &p);
   p.k_pad = kp; p.n_pad = np; p.in_xor = i8 ? 0 : 0x80;
   p.in_zp = q.in_zp; p.w_zp = q.w_zp; p.out_zp = Zp(out); p.act_min = q.amin; p.act_max = q.amax;
@@ -165,14 +164,11 @@ absl::Status HipModelExecutor::PackedConv(const HipModel& model, int oi, const C
   L->alg_bytes = static_cast<double>(g.batch) * g.in_h * g.in_w * g.in_c + M * oc + static_cast<double>(oc) * K +
                  12.0 * oc;
   if (g.groups == 1) {
-    L->kind = Launch::kConv;
     L->kernel = bh_conv2d_i8_kernel(&p);  // the kernel bh_conv2d_i8 dispatches to
     if (GemvAsFc(L)) return absl::OkStatus();
   } else {
-    L->kind = Launch::kConvGrouped;
-    L->conv_groups = g.groups;
-    const bh_conv_grouped_params gp{p, g.groups};
-    L->kernel = device_flag_ == DeviceFlag::kCPU ? "conv_grouped_host" : bh_conv2d_grouped_i8_kernel(&gp);
+    L->kernel = device_flag_ == DeviceFlag::kCPU ? "conv_grouped_host"
+                                                 : bh_conv2d_grouped_i8_kernel(&L->as<bh_conv_grouped_params>());
   }
   TryFuseResidualAdd(model, oi, sg, L);  // the grouped kernel shares the dense epilogue
   return absl::OkStatus();
@@ -209,15 +205,14 @@ absl::Status HipModelExecutor::LowerTransposeConv(const HipModel& model, int oi,
   if (!scratch->ok()) return absl::InternalError("HBM scratch allocation failed");
   sg->consts.push_back(scratch);
   Launch Z;
-  Z.kind = Launch::kZeroInsert;
   Z.op_index = oi;
   Z.kernel = "zero_insert_kernel";
-  Z.zi = bh_zero_insert_params{};
-  Z.zi.batch = g.batch; Z.zi.in_h = g.in_h; Z.zi.in_w = g.in_w; Z.zi.channels = g.in_c;
-  Z.zi.stride_h = g.stride_h; Z.zi.stride_w = g.stride_w; Z.zi.out_h = uh; Z.zi.out_w = uw;
-  Z.zi.fill = static_cast<uint32_t>(Zp(x)) & 0xffu;
-  Z.zi.input = x_ptr;
-  Z.zi.output = scratch->ptr();
+  bh_zero_insert_params& zi = Z.Set<Launch::kZeroInsert>();
+  zi.batch = g.batch; zi.in_h = g.in_h; zi.in_w = g.in_w; zi.channels = g.in_c;
+  zi.stride_h = g.stride_h; zi.stride_w = g.stride_w; zi.out_h = uh; zi.out_w = uw;
+  zi.fill = static_cast<uint32_t>(Zp(x)) & 0xffu;
+  zi.input = x_ptr;
+  zi.output = scratch->ptr();
   Z.alg_bytes = static_cast<double>(x.num_elements()) + static_cast<double>(ubytes);
   sg->launches.push_back(Z);
   // the stride-1 conv over U: flipped filters, folded bias (int8 filters: zero point 0)
@@ -251,15 +246,11 @@ absl::Status HipModelExecutor::LowerGlue(const HipModel& model, int oi, void* in
     case kTflHardSwish:
     case kTflRsqrt:
     case kTflGelu: {
-      L->src = in_ptr;
-      L->dst = out_ptr;
-      L->count = static_cast<long>(out.num_elements());
+      const long count = static_cast<long>(out.num_elements());
       if (op.builtin == kTflQuantize && in.type == DataType::kFloat32) {
-        L->kind = Launch::kQuantF32;
+        L->Set<Launch::kQuantF32>({static_cast<const float*>(in_ptr), out_ptr, count, Scale(out), Zp(out),
+                                   out.type == DataType::kInt8 ? 1 : 0});
         L->kernel = "quantize_f32_kernel";
-        L->q_scale = Scale(out);
-        L->q_zp = Zp(out);
-        L->q_signed = out.type == DataType::kInt8 ? 1 : 0;
         return absl::OkStatus();
       }
       uint8_t table[256];
@@ -280,20 +271,17 @@ absl::Status HipModelExecutor::LowerGlue(const HipModel& model, int oi, void* in
         const float hi = op.builtin == kTflRelu6 ? 6.0f : 1.0f;
         ReluTable(i8, Scale(in), Zp(in), Scale(out), Zp(out), lo, hi, op.builtin == kTflRelu, table);
       }
-      RETURN_STATUS_IF(UploadConst(ckey + "/lut", table, sizeof(table), sg, &L->table));
-      L->kind = Launch::kLutU8;
+      LutArgs& a = L->Set<Launch::kLutU8>({in_ptr, out_ptr, count, nullptr});
+      RETURN_STATUS_IF(UploadConst(ckey + "/lut", table, sizeof(table), sg, &a.table));
       L->kernel = "lut_u8_kernel";
       return absl::OkStatus();
     }
     case kTflDequantize: {
       float table[256];
       DequantizeTable(i8, Scale(in), Zp(in), table);
-      RETURN_STATUS_IF(UploadConst(ckey + "/lut", table, sizeof(table), sg, &L->table));
-      L->kind = Launch::kLutF32;
+      LutArgs& a = L->Set<Launch::kLutF32>({in_ptr, out_ptr, static_cast<long>(out.num_elements()), nullptr});
+      RETURN_STATUS_IF(UploadConst(ckey + "/lut", table, sizeof(table), sg, &a.table));
       L->kernel = "lut_f32_kernel";
-      L->src = in_ptr;
-      L->dst = out_ptr;
-      L->count = static_cast<long>(out.num_elements());
       return absl::OkStatus();
     }
     case kTflSoftmax: {
@@ -302,8 +290,7 @@ absl::Status HipModelExecutor::LowerGlue(const HipModel& model, int oi, void* in
       SoftmaxExpTable(Scale(in), beta, table);
       const void* dt = nullptr;
       RETURN_STATUS_IF(UploadConst(ckey + "/exp", table, sizeof(table), sg, &dt));
-      bh_softmax_params& p = L->softmax;
-      p = bh_softmax_params{};
+      bh_softmax_params& p = L->Set<Launch::kSoftmax>();
       p.depth = in.shape.back();
       p.rows = static_cast<long>(in.num_elements() / std::max(p.depth, 1));
       p.is_signed = i8 ? 1 : 0;
@@ -312,7 +299,6 @@ absl::Status HipModelExecutor::LowerGlue(const HipModel& model, int oi, void* in
       p.out_zp = Zp(out);
       p.input = in_ptr;
       p.output = out_ptr;
-      L->kind = Launch::kSoftmax;
       L->kernel = "softmax_kernel";
       return absl::OkStatus();
     }
@@ -324,8 +310,7 @@ absl::Status HipModelExecutor::LowerGlue(const HipModel& model, int oi, void* in
       long outer = 1, inner = static_cast<long>(GetDataTypeBytes(out.type));
       for (int i = 0; i < axis; ++i) outer *= out.shape[i];
       for (int i = axis + 1; i < rank; ++i) inner *= out.shape[i];
-      bh_concat_params& p = L->concat;
-      p = bh_concat_params{};
+      bh_concat_params& p = L->Set<Launch::kConcat>();
       p.n_inputs = static_cast<int>(op.inputs.size());
       p.outer = outer;
       p.output = out_ptr;
@@ -345,7 +330,6 @@ absl::Status HipModelExecutor::LowerGlue(const HipModel& model, int oi, void* in
           RETURN_STATUS_IF(UploadConst(ckey + "/lut" + std::to_string(k), table, sizeof(table), sg, &p.table[k]));
         }
       }
-      L->kind = Launch::kConcat;
       L->kernel = "concat_kernel";
       return absl::OkStatus();
     }
@@ -360,8 +344,7 @@ absl::Status HipModelExecutor::LowerGlue(const HipModel& model, int oi, void* in
       std::vector<int64_t> given;
       if (!mirror && ConstInts(T(op.inputs[1]), &given))  // PAD / PADV2
         std::copy_n(given.begin(), std::min(given.size(), pads.size()), pads.begin());
-      bh_pad_params& p = L->pad;
-      p = bh_pad_params{};
+      bh_pad_params& p = L->Set<Launch::kPad>();
       p.elem_bytes = static_cast<int>(GetDataTypeBytes(in.type));
       Shape4(in.shape, p.in_shape);
       const int lead = 4 - rank;
@@ -380,7 +363,6 @@ absl::Status HipModelExecutor::LowerGlue(const HipModel& model, int oi, void* in
       p.mode = mirror;
       p.input = in_ptr;
       p.output = out_ptr;
-      L->kind = Launch::kPad;
       L->kernel = "pad_kernel";
       return absl::OkStatus();
     }
@@ -397,15 +379,13 @@ absl::Status HipModelExecutor::LowerGlue(const HipModel& model, int oi, void* in
         for (int x = 0; x < ow; ++x) tab[oh + x] = NearestNeighborIndex(x, iw, ow, ac, hp);
         const void* dt = nullptr;
         RETURN_STATUS_IF(UploadConst(ckey + "/idx", tab.data(), tab.size() * 4, sg, &dt));
-        bh_resize_nearest_params& p = L->rnear;
-        p = bh_resize_nearest_params{};
+        bh_resize_nearest_params& p = L->Set<Launch::kResizeNearest>();
         p.batch = b; p.in_h = ih; p.in_w = iw; p.out_h = oh; p.out_w = ow;
         p.row_bytes = c * static_cast<int>(GetDataTypeBytes(in.type));
         p.y_index = static_cast<const int32_t*>(dt);
         p.x_index = static_cast<const int32_t*>(dt) + oh;
         p.input = in_ptr;
         p.output = out_ptr;
-        L->kind = Launch::kResizeNearest;
         L->kernel = "resize_nearest_kernel";
       } else if (in.type == DataType::kUInt8) {
         // uint8: optimized_ops::ResizeBilinear's float path
@@ -422,8 +402,7 @@ absl::Status HipModelExecutor::LowerGlue(const HipModel& model, int oi, void* in
         const void* dt = nullptr;
         RETURN_STATUS_IF(UploadConst(ckey + "/tab8", blob.data(), blob.size() * 4, sg, &dt));
         const int32_t* t32 = static_cast<const int32_t*>(dt);
-        bh_resize_bilinear_u8_params& p = L->rbil8;
-        p = bh_resize_bilinear_u8_params{};
+        bh_resize_bilinear_u8_params& p = L->Set<Launch::kResizeBilinearU8>();
         p.batch = b; p.in_h = ih; p.in_w = iw; p.channels = c; p.out_h = oh; p.out_w = ow;
         p.y_idx = t32;
         p.x_idx = t32 + 2 * oh;
@@ -431,7 +410,6 @@ absl::Status HipModelExecutor::LowerGlue(const HipModel& model, int oi, void* in
         p.x_frac = reinterpret_cast<const float*>(t32 + 3 * oh + 2 * ow);
         p.input = in_ptr;
         p.output = out_ptr;
-        L->kind = Launch::kResizeBilinearU8;
         L->kernel = "resize_bilinear_u8_kernel";
       } else {
         std::vector<int32_t> ty, tx;
@@ -440,14 +418,12 @@ absl::Status HipModelExecutor::LowerGlue(const HipModel& model, int oi, void* in
         ty.insert(ty.end(), tx.begin(), tx.end());
         const void* dt = nullptr;
         RETURN_STATUS_IF(UploadConst(ckey + "/tab", ty.data(), ty.size() * 4, sg, &dt));
-        bh_resize_bilinear_params& p = L->rbil;
-        p = bh_resize_bilinear_params{};
+        bh_resize_bilinear_params& p = L->Set<Launch::kResizeBilinear>();
         p.batch = b; p.in_h = ih; p.in_w = iw; p.channels = c; p.out_h = oh; p.out_w = ow;
         p.y_tab = static_cast<const int32_t*>(dt);
         p.x_tab = static_cast<const int32_t*>(dt) + 3 * oh;
         p.input = in_ptr;
         p.output = out_ptr;
-        L->kind = Launch::kResizeBilinear;
         L->kernel = "resize_bilinear_kernel";  // (row forms resize_bilinear_rows_kernel / resize_bilinear_cols_kernel when the rows fit LDS)
       }
       return absl::OkStatus();
@@ -513,7 +489,7 @@ bool HipModelExecutor::TryFuseResidualAdd(const HipModel& model, int oi, Prepare
   const TflTensor& t1 = d.tensors[add.inputs[0]];
   const TflTensor& t2 = d.tensors[add.inputs[1]];
   const AddParams ap = AddSubParams(Scale(t1), Scale(t2), Scale(to), add.builtin == kTflSub);
-  bh_conv_params& p = L->conv;
+  bh_conv_params& p = L->conv();
   p.residual = rptr;
   p.output = optr;
   p.add_left_shift = ap.left_shift;
@@ -570,12 +546,9 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
       }
       const float* dev = nullptr;
       RETURN_STATUS_IF(upload(ckey + "/f32", FloatData(d, t), &dev));
-      L->kind = Launch::kCopy;
+      const CopyArgs& c = L->Set<Launch::kCopy>({out_ptr, dev, 4 * out.num_elements()});
       L->kernel = "copy";
-      L->src = dev;
-      L->dst = out_ptr;
-      L->bytes = 4 * out.num_elements();
-      L->alg_bytes = 2.0 * L->bytes;
+      L->alg_bytes = 2.0 * c.bytes;
       return absl::OkStatus();
     }
     case kTflConv2D:
@@ -594,8 +567,7 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
         for (int c = 0; c < oc; ++c)
           for (int k = 0; k < K; ++k) laid[static_cast<size_t>(k) * oc + c] = wf[static_cast<size_t>(c) * K + k];
       }
-      bh_conv_f32_params& p = L->convf;
-      p = bh_conv_f32_params{};
+      bh_conv_f32_params& p = L->Set<Launch::kConvF32>();
       RETURN_STATUS_IF(upload(ckey + "/w", laid, &p.weights));
       if (g.bias >= 0) RETURN_STATUS_IF(upload(ckey + "/b", FloatData(d, g.bias), &p.bias));
       SetGeometry(g, &p);
@@ -604,7 +576,6 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
       FloatActRange(g.act, &p.act_min, &p.act_max);
       p.input = static_cast<const float*>(in_ptr);
       p.output = static_cast<float*>(out_ptr);
-      L->kind = Launch::kConvF32;
       L->kernel = dw ? "dwconv_f32_kernel" : "conv_f32_kernel";
       L->alg_ops = 2.0 * g.batch * g.out_h * g.out_w * oc * g.k_h * g.k_w * (dw ? 1 : g.in_c);
       L->alg_bytes = io_bytes + 4.0 * laid.size() + 4.0 * oc;
@@ -614,8 +585,7 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
       if (IsHybridWeightOp(d, op)) return LowerFcHybrid(model, oi, in_ptr, out_ptr, ckey, sg, L);
       FcGeometry g;
       if (!FcArgs(d, op, &g, &why)) return Refused(op, why);
-      bh_fc_f32_params& p = L->fcf;
-      p = bh_fc_f32_params{};
+      bh_fc_f32_params& p = L->Set<Launch::kFcF32>();
       RETURN_STATUS_IF(upload(ckey + "/w", FloatData(d, g.filter), &p.weights));
       if (g.bias >= 0) RETURN_STATUS_IF(upload(ckey + "/b", FloatData(d, g.bias), &p.bias));
       p.rows = g.rows;
@@ -624,7 +594,6 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
       FloatActRange(g.act, &p.act_min, &p.act_max);
       p.input = static_cast<const float*>(in_ptr);
       p.output = static_cast<float*>(out_ptr);
-      L->kind = Launch::kFcF32;
       L->kernel = "fc_f32_kernel";
       L->alg_ops = 2.0 * p.rows * g.units * g.depth;
       L->alg_bytes = io_bytes + 4.0 * g.units * g.depth;
@@ -638,8 +607,7 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
       if (!BroadcastArgs(d, op, &s, &why)) return Refused(op, why);
       void* b_ptr = nullptr;
       RETURN_STATUS_IF(DevicePtr(model, op.inputs[1], sg, &b_ptr));
-      bh_eltwise_f32_params& p = L->eltf;
-      p = bh_eltwise_f32_params{};
+      bh_eltwise_f32_params& p = L->Set<Launch::kEltwiseF32>();
       p.kind = op.builtin == kTflAdd   ? BH_ELTF_ADD
                : op.builtin == kTflSub ? BH_ELTF_SUB
                : op.builtin == kTflMul ? BH_ELTF_MUL
@@ -649,7 +617,6 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
       p.a = static_cast<const float*>(in_ptr);
       p.b = static_cast<const float*>(b_ptr);
       p.out = static_cast<float*>(out_ptr);
-      L->kind = Launch::kEltwiseF32;
       L->kernel = "eltwise_f32_kernel";
       L->alg_bytes += 4.0 * T(op.inputs[1]).num_elements();
       return absl::OkStatus();
@@ -658,41 +625,38 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
     case kTflMaxPool2D: {
       PoolGeometry g;
       if (!PoolArgs(d, op, &g, &why)) return Refused(op, why);
-      bh_pool_f32_params& p = L->poolf;
-      p = bh_pool_f32_params{};
+      bh_pool_f32_params& p = L->Set<Launch::kPoolF32>();
       p.kind = op.builtin == kTflAveragePool2D ? BH_POOL_AVG : BH_POOL_MAX;
       SetGeometry(g, &p);
       FloatActRange(g.act, &p.act_min, &p.act_max);
       p.input = static_cast<const float*>(in_ptr);
       p.output = static_cast<float*>(out_ptr);
-      L->kind = Launch::kPoolF32;
       L->kernel = "pool_f32_kernel";
       return absl::OkStatus();
     }
-    case kTflSoftmax:
-      L->kind = Launch::kSoftmaxF32;
+    case kTflSoftmax: {
+      const int depth = in.shape.back();
+      L->Set<Launch::kSoftmaxF32>({static_cast<const float*>(in_ptr), static_cast<float*>(out_ptr),
+                                   static_cast<long>(in.num_elements() / std::max(depth, 1)), depth,
+                                   op.options.valid() ? op.options.Float(0, 1.0f) : 1.0f});
       L->kernel = "softmax_f32_kernel";
-      L->beta = op.options.valid() ? op.options.Float(0, 1.0f) : 1.0f;
-      L->depth = in.shape.back();
-      L->count = static_cast<long>(in.num_elements() / std::max(L->depth, 1));
-      L->src = in_ptr;
-      L->dst = out_ptr;
       return absl::OkStatus();
+    }
     case kTflBatchMatMul:
       return LowerBatchMatMul(model, oi, in_ptr, out_ptr, sg, L);
     default: {  // RELU / RELU6 / RELU_N1_TO_1 / LOGISTIC / RSQRT / GELU
-      L->kind = Launch::kUnaryF32;
+      UnaryF32Args& a = L->Set<Launch::kUnaryF32>();
       L->kernel = "unary_f32_kernel";
       const bool approximate = op.builtin == kTflGelu && op.options.valid() && op.options.Bool(0, false);
-      L->unary_kind = op.builtin == kTflLogistic ? BH_UNARY_LOGISTIC
-                      : op.builtin == kTflRsqrt  ? BH_UNARY_RSQRT
-                      : op.builtin == kTflGelu   ? (approximate ? BH_UNARY_GELU_TANH : BH_UNARY_GELU)
-                                                 : BH_UNARY_CLAMP;
-      L->lo = op.builtin == kTflReluN1To1 ? -1.f : 0.f;
-      L->hi = op.builtin == kTflRelu6 ? 6.f : (op.builtin == kTflReluN1To1 ? 1.f : std::numeric_limits<float>::infinity());
-      L->count = static_cast<long>(in.num_elements());
-      L->src = in_ptr;
-      L->dst = out_ptr;
+      a.kind = op.builtin == kTflLogistic ? BH_UNARY_LOGISTIC
+               : op.builtin == kTflRsqrt  ? BH_UNARY_RSQRT
+               : op.builtin == kTflGelu   ? (approximate ? BH_UNARY_GELU_TANH : BH_UNARY_GELU)
+                                          : BH_UNARY_CLAMP;
+      a.lo = op.builtin == kTflReluN1To1 ? -1.f : 0.f;
+      a.hi = op.builtin == kTflRelu6 ? 6.f : (op.builtin == kTflReluN1To1 ? 1.f : std::numeric_limits<float>::infinity());
+      a.count = static_cast<long>(in.num_elements());
+      a.src = static_cast<const float*>(in_ptr);
+      a.dst = static_cast<float*>(out_ptr);
       return absl::OkStatus();
     }
   }
@@ -723,8 +687,7 @@ absl::Status HipModelExecutor::LowerDetectionGpu(const HipModel& model, int oi, 
   int batch = 1;
   if (!opt_.gpu_detection || !DetectionSupported(d, op, &c, &batch))
     return absl::InternalError("unsupported custom op " + op.custom_code);
-  bh_detection_params& p = L->detg;
-  p = bh_detection_params{};
+  bh_detection_params& p = L->Set<Launch::kDetectionGpu>();
   p.batch = batch;
   p.num_boxes = c.num_boxes;
   p.num_classes = c.num_classes;
@@ -773,7 +736,6 @@ absl::Status HipModelExecutor::LowerDetectionGpu(const HipModel& model, int oi, 
   if (!scratch->ok()) return absl::InternalError("HBM scratch allocation failed");
   sg->consts.push_back(scratch);
   p.scratch = scratch->ptr();
-  L->kind = Launch::kDetectionGpu;
   L->kernel = "detection_postprocess_kernel";
   L->alg_bytes = bytes;
   return absl::OkStatus();
@@ -792,29 +754,26 @@ absl::Status HipModelExecutor::LowerReindex(const HipModel& model, int oi, Prepa
     L.op_index = oi;
     L.out_tensor = op.outputs[k];
     const char* why = "";
-    if (!ReindexArgs(d, op, k, &L.reindex, &why))
+    bh_reindex_params& r = L.Set<Launch::kReindex>();
+    if (!ReindexArgs(d, op, k, &r, &why))
       return absl::InternalError(std::string("unsupported ") + TflBuiltinName(op.builtin) + ": " + why);
     void* out_ptr = nullptr;
     RETURN_STATUS_IF(DevicePtr(model, op.outputs[k], sg, &out_ptr));
-    L.reindex.input = in_ptr;
-    L.reindex.output = out_ptr;
+    r.input = in_ptr;
+    r.output = out_ptr;
     bh_reindex_params c;
-    if (bh_reindex_canonical(&L.reindex, &c) != 0)
+    if (bh_reindex_canonical(&r, &c) != 0)
       return absl::InternalError(std::string(TflBuiltinName(op.builtin)) + ": " + bh_last_error());
     const size_t bytes = meta_[op.outputs[k]]->bytes;
     L.alg_bytes = 2.0 * bytes;
     if (c.rank == 1 && c.in_stride[0] == 1 && c.in_offset == 0) {
       // the identity (a TRANSPOSE that only moves unit dims, a SLICE of
       // everything): same bytes, as RESHAPE
-      L.kind = Launch::kCopy;
+      if (in_ptr == out_ptr) continue;
+      L.Set<Launch::kCopy>({out_ptr, in_ptr, bytes});
       L.kernel = "copy";
-      L.src = in_ptr;
-      L.dst = out_ptr;
-      L.bytes = bytes;
-      if (L.src == L.dst) continue;
     } else {
-      L.kind = Launch::kReindex;
-      L.kernel = device_flag_ == DeviceFlag::kCPU ? "reindex_host" : bh_reindex_kernel(&L.reindex);
+      L.kernel = device_flag_ == DeviceFlag::kCPU ? "reindex_host" : bh_reindex_kernel(&r);
     }
     sg->launches.push_back(L);
   }
@@ -830,17 +789,16 @@ absl::Status HipModelExecutor::LowerBatchMatMul(const HipModel& model, int oi, v
   const TflModel& d = model.desc();
   const TflOperator& op = d.ops[oi];
   const char* why = "";
-  bh_batch_matmul_params& p = L->bmm;
+  const bool f32 = d.tensors[op.inputs[0]].type == DataType::kFloat32;
+  bh_batch_matmul_params& p = L->Set(f32 ? Launch::kBatchMatMulF32 : Launch::kBatchMatMul, bh_batch_matmul_params{});
   if (!BatchMatMulArgs(d, op, &p, &why)) return absl::InternalError(std::string("unsupported BATCH_MATMUL: ") + why);
   void* rhs_ptr = nullptr;
   RETURN_STATUS_IF(DevicePtr(model, op.inputs[1], sg, &rhs_ptr));
   p.lhs = lhs_ptr;
   p.rhs = rhs_ptr;
   p.out = out_ptr;
-  const bool f32 = d.tensors[op.inputs[0]].type == DataType::kFloat32;
   if (bh_batch_matmul_check(&p, f32 ? 4 : 1) != 0) return absl::InternalError(std::string("BATCH_MATMUL: ") + bh_last_error());
   const bool cpu = device_flag_ == DeviceFlag::kCPU;
-  L->kind = f32 ? Launch::kBatchMatMulF32 : Launch::kBatchMatMul;
   L->kernel = f32 ? (cpu ? "batch_matmul_f32_host" : "bmm_f32_kernel")
                   : (cpu ? "batch_matmul_host" : bh_batch_matmul_i8_kernel(&p));
   L->alg_ops = 2.0 * p.batch[0] * p.batch[1] * p.m * p.n * p.k;
@@ -881,8 +839,7 @@ absl::Status HipModelExecutor::LowerDepthwise(const HipModel& model, int oi, voi
     return absl::OkStatus();
   }, &blob));
   const int32_t* tab = reinterpret_cast<const int32_t*>(static_cast<char*>(blob->ptr()) + wpad);
-  bh_dwconv_params& p = L->dw;
-  p = bh_dwconv_params{};
+  bh_dwconv_params& p = L->Set<Launch::kDwConv>();
   SetGeometry(g, &p);
   p.depth_multiplier = g.depth_multiplier;
   p.in_xor = i8 ? 0 : 0x80; p.in_zp = q.in_zp; p.w_zp = q.w_zp; p.out_zp = Zp(out);
@@ -891,7 +848,6 @@ absl::Status HipModelExecutor::LowerDepthwise(const HipModel& model, int oi, voi
   p.bias = tab; p.mult = tab + oc; p.shift = tab + 2 * oc;
   if (dot && !blob->host()) p.taps = tab + 3 * oc;
   p.requant_fast = bh_conv_requant_fast_ok(q.mult.data(), q.shift.data(), oc, kh * kw, MaxAbs(q.bias, oc));
-  L->kind = Launch::kDwConv;
   L->kernel = bh_dwconv2d_i8_kernel(&p);  // the kernel bh_dwconv2d_i8 dispatches to
   const double M = static_cast<double>(g.batch) * g.out_h * g.out_w;
   L->alg_ops = 2.0 * M * oc * kh * kw;
@@ -938,14 +894,12 @@ absl::Status HipModelExecutor::LowerFc(const HipModel& model, int oi, void* in_p
     return absl::OkStatus();
   }, &blob));
   const int32_t* tab = reinterpret_cast<const int32_t*>(static_cast<char*>(blob->ptr()) + wbytes);
-  bh_fc_params& p = L->fc;
-  p = bh_fc_params{};
+  bh_fc_params& p = L->Set<Launch::kFc>();
   p.rows = rows; p.depth = depth; p.depth_pad = depth_pad; p.units = units;
   p.in_xor = i8 ? 0 : 0x80; p.in_zp = in_zp; p.w_zp = w_zp; p.out_zp = Zp(out);
   p.act_min = amin; p.act_max = amax; p.input = in_ptr; p.output = out_ptr;
   p.weights = static_cast<const int8_t*>(blob->ptr());
   p.bias_eff = tab; p.mult = tab + units; p.shift = tab + 2 * units;
-  L->kind = Launch::kFc;
   L->kernel = "fc_kernel";
   L->alg_ops = 2.0 * rows * units * depth;
   L->alg_bytes = static_cast<double>(rows) * depth + static_cast<double>(rows) * units +
@@ -996,29 +950,27 @@ absl::Status HipModelExecutor::LowerFcHybrid(const HipModel& model, int oi, void
   char* sp = static_cast<char*>(scratch->ptr());
   const bool cpu = device_flag_ == DeviceFlag::kCPU;
   Launch Q;
-  Q.kind = Launch::kDynQuantRows;
   Q.op_index = oi;
-  Q.dq = bh_dynquant_params{};
-  Q.dq.rows = rows; Q.dq.depth = depth; Q.dq.asymmetric = h.asymmetric ? 1 : 0;
-  Q.dq.input = static_cast<const float*>(in_ptr);
-  Q.dq.q = reinterpret_cast<int8_t*>(sp);
-  Q.dq.scale = reinterpret_cast<float*>(sp + qbytes);
-  Q.dq.offset = reinterpret_cast<int32_t*>(sp + qbytes + 4ull * rows);
-  Q.kernel = cpu ? "dynquant_rows_host" : bh_dynquant_rows_kernel(&Q.dq);
+  bh_dynquant_params dq{};
+  dq.rows = rows; dq.depth = depth; dq.asymmetric = h.asymmetric ? 1 : 0;
+  dq.input = static_cast<const float*>(in_ptr);
+  dq.q = reinterpret_cast<int8_t*>(sp);
+  dq.scale = reinterpret_cast<float*>(sp + qbytes);
+  dq.offset = reinterpret_cast<int32_t*>(sp + qbytes + 4ull * rows);
+  Q.Set<Launch::kDynQuantRows>(dq);
+  Q.kernel = cpu ? "dynquant_rows_host" : bh_dynquant_rows_kernel(&dq);
   Q.alg_bytes = 5.0 * rows * depth + 8.0 * rows;
   sg->launches.push_back(Q);
   const char* base = static_cast<const char*>(blob->ptr());
-  bh_fc_hybrid_params& p = L->fch;
-  p = bh_fc_hybrid_params{};
+  bh_fc_hybrid_params& p = L->Set<Launch::kFcHybrid>();
   p.rows = rows; p.depth = depth; p.depth_pad = depth_pad; p.units = units;
   p.w_scale = h.w_scale;
   FloatActRange(g.act, &p.act_min, &p.act_max);
-  p.q = Q.dq.q; p.in_scale = Q.dq.scale; p.in_offset = Q.dq.offset;
+  p.q = dq.q; p.in_scale = dq.scale; p.in_offset = dq.offset;
   p.weights = reinterpret_cast<const int8_t*>(base);
   p.w_row_sum = reinterpret_cast<const int32_t*>(base + wbytes);
   p.bias = g.bias >= 0 ? reinterpret_cast<const float*>(base + wbytes + 4ull * units) : nullptr;
   p.output = static_cast<float*>(out_ptr);
-  L->kind = Launch::kFcHybrid;
   L->kernel = cpu ? "fc_hybrid_host" : bh_fc_hybrid_kernel(&p);
   L->alg_ops = 2.0 * rows * units * depth;
   L->alg_bytes = static_cast<double>(rows) * depth + 8.0 * rows + 4.0 * rows * units +
@@ -1084,21 +1036,20 @@ absl::Status HipModelExecutor::LowerConvHybrid(const HipModel& model, int oi, vo
   char* sp = static_cast<char*>(scratch->ptr());
   const bool cpu = device_flag_ == DeviceFlag::kCPU;
   Launch Q;
-  Q.kind = Launch::kDynQuantItems;
   Q.op_index = oi;
-  Q.dqi = bh_dynquant_items_params{};
-  Q.dqi.items = items; Q.dqi.item_size = item_size; Q.dqi.asymmetric = h.per_channel ? 1 : 0;
-  Q.dqi.input = static_cast<const float*>(in_ptr);
-  Q.dqi.q = reinterpret_cast<int8_t*>(sp);
-  Q.dqi.pairs = reinterpret_cast<float*>(sp + qbytes);
-  Q.dqi.scale = reinterpret_cast<float*>(sp + qbytes + pbytes);
-  Q.dqi.offset = reinterpret_cast<int32_t*>(sp + qbytes + pbytes + 4ull * items);
-  Q.kernel = cpu ? "dynquant_items_host" : bh_dynquant_items_kernel(&Q.dqi);
+  bh_dynquant_items_params dqi{};
+  dqi.items = items; dqi.item_size = item_size; dqi.asymmetric = h.per_channel ? 1 : 0;
+  dqi.input = static_cast<const float*>(in_ptr);
+  dqi.q = reinterpret_cast<int8_t*>(sp);
+  dqi.pairs = reinterpret_cast<float*>(sp + qbytes);
+  dqi.scale = reinterpret_cast<float*>(sp + qbytes + pbytes);
+  dqi.offset = reinterpret_cast<int32_t*>(sp + qbytes + pbytes + 4ull * items);
+  Q.Set<Launch::kDynQuantItems>(dqi);
+  Q.kernel = cpu ? "dynquant_items_host" : bh_dynquant_items_kernel(&dqi);
   Q.alg_bytes = 5.0 * items * item_size + 8.0 * items;
   sg->launches.push_back(Q);
   const char* base = static_cast<const char*>(blob->ptr());
-  bh_conv_hybrid_params& p = L->convh;
-  p = bh_conv_hybrid_params{};
+  bh_conv_hybrid_params& p = L->Set(dw ? Launch::kDwConvHybrid : Launch::kConvHybrid, bh_conv_hybrid_params{});
   p.batch = g.batch; p.in_h = g.in_h; p.in_w = g.in_w; p.in_c = g.in_c;
   p.out_h = g.out_h; p.out_w = g.out_w; p.out_c = oc;
   p.k_h = g.k_h; p.k_w = g.k_w; p.stride_h = g.stride_h; p.stride_w = g.stride_w;
@@ -1107,13 +1058,12 @@ absl::Status HipModelExecutor::LowerConvHybrid(const HipModel& model, int oi, vo
   p.depth_multiplier = g.depth_multiplier;
   p.per_channel = h.per_channel ? 1 : 0;
   FloatActRange(g.act, &p.act_min, &p.act_max);
-  p.q = Q.dqi.q; p.in_scale = Q.dqi.scale; p.in_offset = Q.dqi.offset;
+  p.q = dqi.q; p.in_scale = dqi.scale; p.in_offset = dqi.offset;
   p.weights = reinterpret_cast<const int8_t*>(base);
   p.w_row_sum = reinterpret_cast<const int32_t*>(base + wbytes);
   p.w_scale = reinterpret_cast<const float*>(base + wbytes + 4ull * oc);
   p.bias = g.bias >= 0 ? reinterpret_cast<const float*>(base + wbytes + 8ull * oc) : nullptr;
   p.output = static_cast<float*>(out_ptr);
-  L->kind = dw ? Launch::kDwConvHybrid : Launch::kConvHybrid;
   L->kernel = cpu ? (dw ? "dwconv_hybrid_host" : "conv_hybrid_host")
                   : (dw ? bh_dwconv2d_hybrid_kernel(&p) : bh_conv2d_hybrid_kernel(&p));
   const double outs = static_cast<double>(g.batch) * g.out_h * g.out_w * oc;
@@ -1136,8 +1086,7 @@ absl::Status HipModelExecutor::LowerEltwise(const HipModel& model, int oi, void*
   const bool i8 = in.type == DataType::kInt8;
   void* b_ptr = nullptr;
   RETURN_STATUS_IF(DevicePtr(model, op.inputs[1], sg, &b_ptr));
-  bh_eltwise_params& p = L->elt;
-  p = bh_eltwise_params{};
+  bh_eltwise_params& p = L->Set<Launch::kEltwise>();
   p.in_signed = i8 ? 1 : 0;
   std::copy_n(s.a, 4, p.shape_a); std::copy_n(s.b, 4, p.shape_b); std::copy_n(s.o, 4, p.shape_o);
   p.a_off = -Zp(in); p.b_off = -Zp(b); p.o_off = Zp(out);
@@ -1163,7 +1112,6 @@ absl::Status HipModelExecutor::LowerEltwise(const HipModel& model, int oi, void*
     p.o_mult = ap.mo; p.o_shift = ap.so;
   }
   p.a = in_ptr; p.b = b_ptr; p.out = out_ptr;
-  L->kind = Launch::kEltwise;
   L->kernel = p.kind != BH_ELT_SQDIFF                 ? "eltwise_kernel"
               : device_flag_ == DeviceFlag::kCPU ? "eltwise_sqdiff_host"
                                                  : "eltwise_sqdiff_kernel";
@@ -1181,14 +1129,12 @@ absl::Status HipModelExecutor::LowerPool(const HipModel& model, int oi, void* in
   const TflTensor& in = d.tensors[op.inputs[0]];
   const TflTensor& out = d.tensors[op.outputs[0]];
   const bool i8 = in.type == DataType::kInt8;
-  bh_pool_params& p = L->pool;
-  p = bh_pool_params{};
+  bh_pool_params& p = L->Set<Launch::kPool>();
   p.kind = op.builtin == kTflAveragePool2D ? BH_POOL_AVG : BH_POOL_MAX;
   p.in_signed = i8 ? 1 : 0;
   SetGeometry(g, &p);
   ActivationRangeQuantized(g.act, Scale(out), Zp(out), i8, &p.act_min, &p.act_max);
   p.input = in_ptr; p.output = out_ptr;
-  L->kind = Launch::kPool;
   L->kernel = "pool_kernel";
   L->alg_bytes = static_cast<double>(in.num_elements() + out.num_elements());
   return absl::OkStatus();
@@ -1206,8 +1152,7 @@ absl::Status HipModelExecutor::LowerMean(const HipModel& model, int oi, void* in
   L->alg_bytes = static_cast<double>(meta_[op.inputs[0]]->bytes + meta_[op.outputs[0]]->bytes);
   if (g.rows) {
     // the last axis of an 8-bit tensor: one wave per row (mean_rows_kernel / CpuMeanRows)
-    bh_mean_rows_params& q = L->mrows;
-    q = bh_mean_rows_params{};
+    bh_mean_rows_params& q = L->Set<Launch::kMeanRows>();
     q.rows = g.outer;
     q.depth = static_cast<int>(g.reduce);
     q.type = in.type == DataType::kInt8 ? 1 : 2;
@@ -1218,12 +1163,10 @@ absl::Status HipModelExecutor::LowerMean(const HipModel& model, int oi, void* in
     q.out_zp = Zp(out);
     q.input = in_ptr; q.output = out_ptr;
     if (bh_mean_rows_check(&q) != 0) return absl::InternalError(std::string("MEAN: ") + bh_last_error());
-    L->kind = Launch::kMeanRows;
     L->kernel = device_flag_ == DeviceFlag::kGPU ? bh_mean_rows_kernel(&q) : "mean_rows_host";
     return absl::OkStatus();
   }
-  CpuMeanParams& p = L->mean;
-  p = CpuMeanParams{};
+  bh_mean_params& p = L->Set<Launch::kMean>();
   p.outer = g.outer; p.reduce = g.reduce; p.inner = g.inner;
   p.type = in.type == DataType::kFloat32 ? 0 : (in.type == DataType::kInt8 ? 1 : 2);
   if (p.type) {
@@ -1238,7 +1181,6 @@ absl::Status HipModelExecutor::LowerMean(const HipModel& model, int oi, void* in
     p.shift = shift;
   }
   p.input = in_ptr; p.output = out_ptr;
-  L->kind = Launch::kMean;
   L->kernel = device_flag_ == DeviceFlag::kGPU ? "mean_kernel" : "mean_host";
   L->alg_bytes = static_cast<double>(meta_[op.inputs[0]]->bytes + meta_[op.outputs[0]]->bytes);
   return absl::OkStatus();
@@ -1248,14 +1190,12 @@ absl::Status HipModelExecutor::LowerArgMinMax(const HipModel& model, int oi, voi
   const TflModel& d = model.desc();
   const TflOperator& op = d.ops[oi];
   const DataType type = d.tensors[op.inputs[0]].type;
-  bh_argminmax_params& p = L->argmm;
-  p = bh_argminmax_params{};
+  bh_argminmax_params& p = L->Set<Launch::kArgMinMax>();
   if (!ArgMinMaxArgs(d, op, &p.outer, &p.axis_len, &p.inner, &p.out_bytes))
     return absl::InternalError("unsupported ARG_MAX / ARG_MIN");
   p.in_type = type == DataType::kFloat32 ? BH_ARG_F32 : (type == DataType::kInt8 ? BH_ARG_I8 : BH_ARG_U8);
   p.is_min = op.builtin == kTflArgMin ? 1 : 0;
   p.input = in_ptr; p.output = out_ptr;
-  L->kind = Launch::kArgMinMax;
   L->kernel = device_flag_ == DeviceFlag::kCPU ? "argminmax_host" : bh_argminmax_kernel(&p);
   L->alg_bytes = static_cast<double>(meta_[op.inputs[0]]->bytes + meta_[op.outputs[0]]->bytes);
   return absl::OkStatus();
@@ -1266,7 +1206,7 @@ absl::Status HipModelExecutor::LowerDetectionHost(const HipModel& model, int oi,
                                                   Launch* L) {
   const TflModel& d = model.desc();
   const TflOperator& op = d.ops[oi];
-  CpuDetectionParams& p = L->det;
+  CpuDetectionParams& p = L->Set<Launch::kDetectionPost>();
   if (!DetectionSupported(d, op, &p)) return absl::InternalError("unsupported custom op " + op.custom_code);
   void* scores = nullptr;
   void* anchors = nullptr;
@@ -1281,7 +1221,6 @@ absl::Status HipModelExecutor::LowerDetectionHost(const HipModel& model, int oi,
   p.out_classes = static_cast<float*>(outs[1]);
   p.out_scores = static_cast<float*>(outs[2]);
   p.out_num = static_cast<float*>(outs[3]);
-  L->kind = Launch::kDetectionPost;
   L->kernel = "detection_postprocess_host";
   return absl::OkStatus();
 }
@@ -1323,18 +1262,16 @@ absl::Status HipModelExecutor::Lower(const HipModel& model, int oi, PreparedSubg
       case kTflCustom:
         return cpu ? LowerDetectionHost(model, oi, in_ptr, sg, &L) : LowerDetectionGpu(model, oi, sg, &L);
       case kTflReshape: case kTflSqueeze:  // same bytes, new dims
-        L.kind = Launch::kCopy;
+        L.Set<Launch::kCopy>({out_ptr, in_ptr, meta_[op.outputs[0]]->bytes});
         L.kernel = "copy";
-        L.src = in_ptr;
-        L.dst = out_ptr;
-        L.bytes = meta_[op.outputs[0]]->bytes;
-        L.alg_bytes = 2.0 * L.bytes;
-        emit = L.src != L.dst;  // aliased slot: nothing to move
+        L.alg_bytes = 2.0 * meta_[op.outputs[0]]->bytes;
+        emit = in_ptr != out_ptr;  // aliased slot: nothing to move
         return absl::OkStatus();
       default: return LowerGlue(model, oi, in_ptr, out_ptr, ckey, sg, &L);
     }
   };
   RETURN_STATUS_IF(IsFloatOp(d, op) ? LowerFloat(model, oi, in_ptr, out_ptr, ckey, sg, &L, &emit) : lower());
+  if (emit && L.kind() == Launch::kNone) return absl::InternalError("op " + std::to_string(oi) + " lowered to no launch");
   if (emit) sg->launches.push_back(L);
   return absl::OkStatus();
 }

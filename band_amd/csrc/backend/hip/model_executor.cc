@@ -610,85 +610,162 @@ std::shared_ptr<interface::ITensorView> HipModelExecutor::GetTensorView(const Su
   return std::make_shared<HipTensorView>(m, nullptr);
 }
 
+namespace {
+
+// One row per Launch::Kind, in enum order: the launcher a kGPU executor calls
+// with the launch's payload and the host twin a kCPU executor calls.  A null
+// entry is a kind that worker never lowers to.
+struct KindCalls {
+  Launch::Kind kind;
+  int (*device)(const Launch&, bh_stream_t);
+  void (*host)(const Launch&, CpuPool&);
+};
+
+// the parameter block a launcher (const P*, ...) or a host twin (const P&, ...) takes
+template <class F>
+struct BlockOf;
+template <class R, class P, class... A>
+struct BlockOf<R (*)(const P*, A...)> {
+  using type = P;
+};
+template <class R, class P, class... A>
+struct BlockOf<R (*)(const P&, A...)> {
+  using type = P;
+};
+// Fn(&payload, stream) / Fn(payload[, pool]) on the payload of Fn's block type
+template <auto Fn>
+int Dev(const Launch& l, bh_stream_t s) {
+  return Fn(&l.as<typename BlockOf<decltype(Fn)>::type>(), s);
+}
+template <auto Fn>
+void Host(const Launch& l, CpuPool& pool) {
+  const auto& p = l.as<typename BlockOf<decltype(Fn)>::type>();
+  if constexpr (std::is_invocable_v<decltype(Fn), decltype(p), CpuPool&>) Fn(p, pool);
+  else Fn(p);
+}
+
+constexpr KindCalls kCalls[] = {
+    {Launch::kConv, Dev<bh_conv2d_i8>, Host<CpuConv>},
+    {Launch::kDwConv, Dev<bh_dwconv2d_i8>, Host<CpuDwConv>},
+    {Launch::kFc, Dev<bh_fc_i8>, Host<CpuFc>},
+    {Launch::kEltwise, Dev<bh_eltwise_i8>, Host<CpuEltwise>},
+    {Launch::kPool, Dev<bh_pool_i8>, Host<CpuPool2D>},
+    // a kernel copy, not a blit: graphs replayed under rocprofv3's kernel
+    // trace crash on blit (memcpy) nodes
+    {Launch::kCopy,
+     [](const Launch& l, bh_stream_t s) {
+       const CopyArgs& c = l.as<CopyArgs>();
+       return c.src != c.dst ? bh_copy_d2d(c.dst, c.src, c.bytes, s) : 0;
+     },
+     [](const Launch& l, CpuPool&) {
+       const CopyArgs& c = l.as<CopyArgs>();
+       if (c.src != c.dst) std::memmove(c.dst, c.src, c.bytes);
+     }},
+    {Launch::kIrb, Dev<bh_irb_i8>, nullptr},
+    {Launch::kChain, Dev<bh_chain_i8>, nullptr},
+    {Launch::kLutU8,
+     [](const Launch& l, bh_stream_t s) {
+       const LutArgs& a = l.as<LutArgs>();
+       return bh_lut_u8(a.src, a.dst, a.count, a.table, s);
+     },
+     [](const Launch& l, CpuPool& pool) {
+       const LutArgs& a = l.as<LutArgs>();
+       CpuLutU8(a.src, a.dst, a.count, static_cast<const uint8_t*>(a.table), pool);
+     }},
+    {Launch::kLutF32,
+     [](const Launch& l, bh_stream_t s) {
+       const LutArgs& a = l.as<LutArgs>();
+       return bh_lut_f32(a.src, a.dst, a.count, static_cast<const float*>(a.table), s);
+     },
+     [](const Launch& l, CpuPool& pool) {
+       const LutArgs& a = l.as<LutArgs>();
+       CpuLutF32(a.src, static_cast<float*>(a.dst), a.count, static_cast<const float*>(a.table), pool);
+     }},
+    {Launch::kQuantF32,
+     [](const Launch& l, bh_stream_t s) {
+       const QuantF32Args& a = l.as<QuantF32Args>();
+       return bh_quantize_f32(a.src, a.dst, a.count, a.scale, a.zp, a.is_signed, s);
+     },
+     [](const Launch& l, CpuPool& pool) {
+       const QuantF32Args& a = l.as<QuantF32Args>();
+       CpuQuantizeF32(a.src, a.dst, a.count, a.scale, a.zp, a.is_signed, pool);
+     }},
+    {Launch::kConcat, Dev<bh_concat>, Host<CpuConcat>},
+    {Launch::kPad, Dev<bh_pad>, Host<CpuPad>},
+    {Launch::kResizeNearest, Dev<bh_resize_nearest>, Host<CpuResizeNearest>},
+    {Launch::kResizeBilinear, Dev<bh_resize_bilinear_i8>, Host<CpuResizeBilinear>},
+    {Launch::kSoftmax, Dev<bh_softmax_i8>, Host<CpuSoftmax>},
+    {Launch::kZeroInsert, Dev<bh_zero_insert>, Host<CpuZeroInsert>},
+    {Launch::kConvF32, Dev<bh_conv2d_f32>, Host<CpuConvF32>},
+    {Launch::kFcF32, Dev<bh_fc_f32>, Host<CpuFcF32>},
+    {Launch::kEltwiseF32, Dev<bh_eltwise_f32>, Host<CpuEltwiseF32>},
+    {Launch::kPoolF32, Dev<bh_pool_f32>, Host<CpuPoolF32>},
+    {Launch::kUnaryF32,
+     [](const Launch& l, bh_stream_t s) {
+       const UnaryF32Args& a = l.as<UnaryF32Args>();
+       return bh_unary_f32(a.kind, a.src, a.dst, a.count, a.lo, a.hi, s);
+     },
+     [](const Launch& l, CpuPool&) {
+       const UnaryF32Args& a = l.as<UnaryF32Args>();
+       CpuUnaryF32(a.kind, a.src, a.dst, a.count, a.lo, a.hi);
+     }},
+    {Launch::kSoftmaxF32,
+     [](const Launch& l, bh_stream_t s) {
+       const SoftmaxF32Args& a = l.as<SoftmaxF32Args>();
+       return bh_softmax_f32(a.src, a.dst, a.rows, a.depth, a.beta, s);
+     },
+     [](const Launch& l, CpuPool&) {
+       const SoftmaxF32Args& a = l.as<SoftmaxF32Args>();
+       CpuSoftmaxF32(a.src, a.dst, a.rows, a.depth, a.beta);
+     }},
+    {Launch::kResizeBilinearU8, Dev<bh_resize_bilinear_u8>, Host<CpuResizeBilinearU8>},
+    {Launch::kDetectionPost, nullptr, Host<CpuDetectionPostprocess>},
+    {Launch::kMean, Dev<bh_mean>, Host<CpuMean>},
+    {Launch::kMeanRows, Dev<bh_mean_rows>, Host<CpuMeanRows>},
+    {Launch::kConvGroup,
+     [](const Launch& l, bh_stream_t s) { return bh_conv_group_i8(&l.as<ConvGroupArgs>().cgroup, s); }, nullptr},
+    {Launch::kDetectionGpu, Dev<bh_detection_postprocess>, nullptr},
+    {Launch::kArgMinMax, Dev<bh_argminmax>, Host<CpuArgMinMax>},
+    {Launch::kResizeArgMinMax, Dev<bh_resize_bilinear_argminmax_i8>, nullptr},
+    {Launch::kReindex, Dev<bh_reindex>, Host<CpuReindex>},
+    {Launch::kConvGrouped, Dev<bh_conv2d_grouped_i8>,
+     [](const Launch& l, CpuPool& pool) {
+       const bh_conv_grouped_params& g = l.as<bh_conv_grouped_params>();
+       CpuConvGrouped(g.conv, g.groups, pool);
+     }},
+    {Launch::kBatchMatMul, Dev<bh_batch_matmul_i8>, Host<CpuBatchMatMul>},
+    {Launch::kBatchMatMulF32, Dev<bh_batch_matmul_f32>, Host<CpuBatchMatMulF32>},
+    {Launch::kLayerNorm, [](const Launch& l, bh_stream_t s) { return bh_layernorm_i8(l.as<LayerNormArgs>().p.get(), s); },
+     nullptr},
+    {Launch::kAttention, Dev<bh_attention_i8>, nullptr},
+    {Launch::kDynQuantRows, Dev<bh_dynquant_rows>, Host<CpuDynQuantRows>},
+    {Launch::kFcHybrid, Dev<bh_fc_hybrid>, Host<CpuFcHybrid>},
+    {Launch::kDynQuantItems, Dev<bh_dynquant_items>, Host<CpuDynQuantItems>},
+    {Launch::kConvHybrid, Dev<bh_conv2d_hybrid>, Host<CpuConvHybrid>},
+    {Launch::kDwConvHybrid, Dev<bh_dwconv2d_hybrid>, Host<CpuDwConvHybrid>},
+    {Launch::kLayerNormF32, Dev<bh_layernorm_f32>, nullptr},
+};
+
+constexpr bool CallRowsInOrder() {
+  for (int k = 0; k < Launch::kNumKinds; ++k)
+    if (kCalls[k].kind != k) return false;
+  return true;
+}
+constexpr bool EveryKindRuns() {
+  for (const KindCalls& c : kCalls)
+    if (!c.device && !c.host) return false;
+  return true;
+}
+static_assert(sizeof(kCalls) / sizeof(kCalls[0]) == Launch::kNumKinds, "one row of kCalls per Launch::Kind");
+static_assert(CallRowsInOrder(), "row i of kCalls names kind i");
+static_assert(EveryKindRuns(), "every kind has a device call or a host call");
+
+}  // namespace
+
 absl::Status HipModelExecutor::EnqueueLaunch(const Launch& l) {
-  int rc = 0;
-  switch (l.kind) {
-    case Launch::kConv: rc = bh_conv2d_i8(&l.conv, stream_); break;
-    case Launch::kConvGrouped: {
-      const bh_conv_grouped_params gp{l.conv, l.conv_groups};
-      rc = bh_conv2d_grouped_i8(&gp, stream_);
-      break;
-    }
-    case Launch::kDwConv: rc = bh_dwconv2d_i8(&l.dw, stream_); break;
-    case Launch::kFc: rc = bh_fc_i8(&l.fc, stream_); break;
-    case Launch::kEltwise: rc = bh_eltwise_i8(&l.elt, stream_); break;
-    case Launch::kPool: rc = bh_pool_i8(&l.pool, stream_); break;
-    case Launch::kIrb: rc = bh_irb_i8(&l.irb, stream_); break;
-    case Launch::kChain: rc = bh_chain_i8(&l.chain, stream_); break;
-    case Launch::kConvGroup: rc = bh_conv_group_i8(&l.cgroup, stream_); break;
-    case Launch::kCopy: {
-      // a kernel copy, not a blit: graphs replayed under rocprofv3's kernel
-      // trace crash on blit (memcpy) nodes
-      if (l.src != l.dst) rc = bh_copy_d2d(l.dst, l.src, l.bytes, stream_);
-      break;
-    }
-    case Launch::kLutU8: rc = bh_lut_u8(l.src, l.dst, l.count, l.table, stream_); break;
-    case Launch::kLutF32:
-      rc = bh_lut_f32(l.src, l.dst, l.count, static_cast<const float*>(l.table), stream_);
-      break;
-    case Launch::kQuantF32:
-      rc = bh_quantize_f32(static_cast<const float*>(l.src), l.dst, l.count, l.q_scale, l.q_zp, l.q_signed, stream_);
-      break;
-    case Launch::kConcat: rc = bh_concat(&l.concat, stream_); break;
-    case Launch::kPad: rc = bh_pad(&l.pad, stream_); break;
-    case Launch::kResizeNearest: rc = bh_resize_nearest(&l.rnear, stream_); break;
-    case Launch::kResizeBilinear: rc = bh_resize_bilinear_i8(&l.rbil, stream_); break;
-    case Launch::kResizeBilinearU8: rc = bh_resize_bilinear_u8(&l.rbil8, stream_); break;
-    case Launch::kSoftmax: rc = bh_softmax_i8(&l.softmax, stream_); break;
-    case Launch::kZeroInsert: rc = bh_zero_insert(&l.zi, stream_); break;
-    case Launch::kConvF32: rc = bh_conv2d_f32(&l.convf, stream_); break;
-    case Launch::kFcF32: rc = bh_fc_f32(&l.fcf, stream_); break;
-    case Launch::kEltwiseF32: rc = bh_eltwise_f32(&l.eltf, stream_); break;
-    case Launch::kPoolF32: rc = bh_pool_f32(&l.poolf, stream_); break;
-    case Launch::kUnaryF32:
-      rc = bh_unary_f32(l.unary_kind, static_cast<const float*>(l.src), static_cast<float*>(l.dst), l.count, l.lo,
-                        l.hi, stream_);
-      break;
-    case Launch::kSoftmaxF32:
-      rc = bh_softmax_f32(static_cast<const float*>(l.src), static_cast<float*>(l.dst), l.count, l.depth, l.beta,
-                          stream_);
-      break;
-    case Launch::kDetectionPost: return absl::InternalError(std::string(l.kernel) + " is a CPU-worker op");
-    case Launch::kDetectionGpu: rc = bh_detection_postprocess(&l.detg, stream_); break;
-    case Launch::kArgMinMax: rc = bh_argminmax(&l.argmm, stream_); break;
-    case Launch::kResizeArgMinMax: rc = bh_resize_bilinear_argminmax_i8(&l.rzarg, stream_); break;
-    case Launch::kReindex: rc = bh_reindex(&l.reindex, stream_); break;
-    case Launch::kBatchMatMul: rc = bh_batch_matmul_i8(&l.bmm, stream_); break;
-    case Launch::kBatchMatMulF32: rc = bh_batch_matmul_f32(&l.bmm, stream_); break;
-    case Launch::kMeanRows: rc = bh_mean_rows(&l.mrows, stream_); break;
-    case Launch::kLayerNorm: rc = bh_layernorm_i8(&l.ln, stream_); break;
-    case Launch::kLayerNormF32: rc = bh_layernorm_f32(&l.lnf, stream_); break;
-    case Launch::kAttention: rc = bh_attention_i8(&l.attn, stream_); break;
-    case Launch::kDynQuantRows: rc = bh_dynquant_rows(&l.dq, stream_); break;
-    case Launch::kFcHybrid: rc = bh_fc_hybrid(&l.fch, stream_); break;
-    case Launch::kDynQuantItems: rc = bh_dynquant_items(&l.dqi, stream_); break;
-    case Launch::kConvHybrid: rc = bh_conv2d_hybrid(&l.convh, stream_); break;
-    case Launch::kDwConvHybrid: rc = bh_dwconv2d_hybrid(&l.convh, stream_); break;
-    case Launch::kMean: {
-      bh_mean_params q{};
-      q.outer = l.mean.outer;
-      q.reduce = l.mean.reduce;
-      q.inner = l.mean.inner;
-      q.type = l.mean.type;
-      q.multiplier = l.mean.multiplier;
-      q.shift = l.mean.shift;
-      q.bias = l.mean.bias;
-      q.input = l.mean.input;
-      q.output = l.mean.output;
-      rc = bh_mean(&q, stream_);
-      break;
-    }
-  }
+  const auto device = l.kind() < Launch::kNumKinds ? kCalls[l.kind()].device : nullptr;
+  if (!device) return absl::InternalError(std::string(l.kernel) + " is a CPU-worker op");
+  const int rc = device(l, stream_);
   return rc ? HipErr(rc, l.kernel) : absl::OkStatus();
 }
 
@@ -838,54 +915,9 @@ absl::Status HipModelExecutor::ExecuteOnHost(PreparedSubgraph* sg) {
     cpu_pool_ = std::make_shared<CpuPool>(num_threads_ > 0 ? num_threads_ : 1, PinnableCpus(thread_affinity_mask_));
   CpuPool& pool = *cpu_pool_;
   for (const Launch& l : sg->launches) {
-    switch (l.kind) {
-      case Launch::kConv: CpuConv(l.conv, pool); break;
-      case Launch::kConvGrouped: CpuConvGrouped(l.conv, l.conv_groups, pool); break;
-      case Launch::kDwConv: CpuDwConv(l.dw, pool); break;
-      case Launch::kFc: CpuFc(l.fc, pool); break;
-      case Launch::kEltwise: CpuEltwise(l.elt, pool); break;
-      case Launch::kPool: CpuPool2D(l.pool, pool); break;
-      case Launch::kCopy:
-        if (l.src != l.dst) std::memmove(l.dst, l.src, l.bytes);
-        break;
-      case Launch::kLutU8: CpuLutU8(l.src, l.dst, l.count, static_cast<const uint8_t*>(l.table), pool); break;
-      case Launch::kLutF32:
-        CpuLutF32(l.src, static_cast<float*>(l.dst), l.count, static_cast<const float*>(l.table), pool);
-        break;
-      case Launch::kQuantF32:
-        CpuQuantizeF32(static_cast<const float*>(l.src), l.dst, l.count, l.q_scale, l.q_zp, l.q_signed, pool);
-        break;
-      case Launch::kConcat: CpuConcat(l.concat); break;
-      case Launch::kPad: CpuPad(l.pad); break;
-      case Launch::kResizeNearest: CpuResizeNearest(l.rnear); break;
-      case Launch::kResizeBilinear: CpuResizeBilinear(l.rbil); break;
-      case Launch::kResizeBilinearU8: CpuResizeBilinearU8(l.rbil8); break;
-      case Launch::kSoftmax: CpuSoftmax(l.softmax); break;
-      case Launch::kZeroInsert: CpuZeroInsert(l.zi); break;
-      case Launch::kConvF32: CpuConvF32(l.convf, pool); break;
-      case Launch::kFcF32: CpuFcF32(l.fcf, pool); break;
-      case Launch::kEltwiseF32: CpuEltwiseF32(l.eltf); break;
-      case Launch::kPoolF32: CpuPoolF32(l.poolf); break;
-      case Launch::kUnaryF32:
-        CpuUnaryF32(l.unary_kind, static_cast<const float*>(l.src), static_cast<float*>(l.dst), l.count, l.lo, l.hi);
-        break;
-      case Launch::kSoftmaxF32:
-        CpuSoftmaxF32(static_cast<const float*>(l.src), static_cast<float*>(l.dst), l.count, l.depth, l.beta);
-        break;
-      case Launch::kDetectionPost: CpuDetectionPostprocess(l.det, pool); break;
-      case Launch::kMean: CpuMean(l.mean, pool); break;
-      case Launch::kMeanRows: CpuMeanRows(l.mrows, pool); break;
-      case Launch::kArgMinMax: CpuArgMinMax(l.argmm, pool); break;
-      case Launch::kReindex: CpuReindex(l.reindex); break;
-      case Launch::kBatchMatMul: CpuBatchMatMul(l.bmm, pool); break;
-      case Launch::kBatchMatMulF32: CpuBatchMatMulF32(l.bmm, pool); break;
-      case Launch::kDynQuantRows: CpuDynQuantRows(l.dq, pool); break;
-      case Launch::kFcHybrid: CpuFcHybrid(l.fch, pool); break;
-      case Launch::kDynQuantItems: CpuDynQuantItems(l.dqi, pool); break;
-      case Launch::kConvHybrid: CpuConvHybrid(l.convh, pool); break;
-      case Launch::kDwConvHybrid: CpuDwConvHybrid(l.convh, pool); break;
-      default: return absl::InternalError(std::string("no host implementation of ") + l.kernel);
-    }
+    const auto host = l.kind() < Launch::kNumKinds ? kCalls[l.kind()].host : nullptr;
+    if (!host) return absl::InternalError(std::string("no host implementation of ") + l.kernel);
+    host(l, pool);
   }
   for (int t : sg->outputs) sync(t, false);
   for (int t : sg->extra_d2h) sync(t, false);

@@ -32,94 +32,13 @@
 #include "backend/hip/model.h"
 #include "backend/hip/tensor.h"
 #include "backend/hip/job_batching.h"
+#include "backend/hip/launch.h"
 #include "backend/hip/lower_args.h"
 #include "band/interface/model_executor.h"
 #include "band_hip_kernels.h"
 
 namespace band {
 namespace hip {
-
-struct Launch {
-  enum Kind {
-    kConv, kDwConv, kFc, kEltwise, kPool, kCopy, kIrb, kChain,
-    kLutU8, kLutF32, kQuantF32, kConcat, kPad, kResizeNearest, kResizeBilinear, kSoftmax, kZeroInsert,
-    kConvF32, kFcF32, kEltwiseF32, kPoolF32, kUnaryF32, kSoftmaxF32,  // float32 graphs
-    kResizeBilinearU8,
-    kDetectionPost,  // CPU-only TFLite_Detection_PostProcess
-    kMean,           // MEAN: float32 over a run of axes, 8-bit over H, W
-    kMeanRows,       // MEAN of an 8-bit tensor over its last axis (`mrows`)
-    kConvGroup,      // independent small convs in one dispatch (GroupConvs)
-    kDetectionGpu,   // TFLite_Detection_PostProcess on the device (BAND_HIP_GPU_DETECTION=1)
-    kArgMinMax,      // ARG_MAX / ARG_MIN
-    kResizeArgMinMax, // RESIZE_BILINEAR int8 -> ARG_MAX / ARG_MIN over channels, one launch (FuseGlue; kGPU)
-    kReindex,         // one output of TRANSPOSE / STRIDED_SLICE / SLICE / SPLIT / SPLIT_V / SPACE_TO_DEPTH / DEPTH_TO_SPACE
-    kConvGrouped,     // grouped CONV_2D: `conv` with the total channel counts + conv_groups (never chained / grouped / blocked)
-    kBatchMatMul,     // BATCH_MATMUL int8 (BatchMatMulArgs -> `bmm`; never chained / grouped / blocked, no epilogue folds)
-    kBatchMatMulF32,  // BATCH_MATMUL float32
-    kLayerNorm,       // the ten ops of an int8 LayerNorm as one launch (FuseLayerNorm; kGPU)
-    kAttention,       // BATCH_MATMUL -> SOFTMAX -> BATCH_MATMUL (int8) as one launch (FuseAttention; kGPU, opt-in)
-    kDynQuantRows,    // hybrid FULLY_CONNECTED, first launch: the input's rows quantised into the subgraph's scratch (`dq`)
-    kFcHybrid,        // hybrid FULLY_CONNECTED, second launch: int8 product, float epilogue (`fch`)
-    kDynQuantItems,   // hybrid CONV_2D / DEPTHWISE_CONV_2D, first launch(es): each batch item quantised into the subgraph's scratch (`dqi`)
-    kConvHybrid,      // hybrid CONV_2D: int8 implicit GEMM, float epilogue (`convh`)
-    kDwConvHybrid,    // hybrid DEPTHWISE_CONV_2D (`convh`)
-    kLayerNormF32     // the ten ops of a float32 LayerNorm as one launch, with the row quantisation of the hybrid
-                      // FULLY_CONNECTEDs that read it (`lnf`; FuseLayerNormF32 / FoldLayerNormQuant; kGPU, opt-in)
-  } kind;
-  int op_index = -1;
-  int out_tensor = -1;  // tensor this launch materialises (after epilogue fusions)
-  bh_conv_params conv{};
-  int conv_groups = 1;  // kConvGrouped
-  bh_dwconv_params dw{};
-  bh_fc_params fc{};
-  bh_eltwise_params elt{};
-  bh_pool_params pool{};
-  bh_irb_params irb{};
-  bh_chain_params chain{};
-  // kConvGroup: the member convs (program order) and the planned group
-  std::vector<bh_conv_params> members;
-  bh_conv_group cgroup{};
-  bh_concat_params concat{};
-  bh_pad_params pad{};
-  bh_resize_nearest_params rnear{};
-  bh_resize_bilinear_params rbil{};
-  bh_resize_bilinear_u8_params rbil8{};
-  bh_softmax_params softmax{};
-  bh_zero_insert_params zi{};
-  bh_conv_f32_params convf{};
-  bh_fc_f32_params fcf{};
-  bh_eltwise_f32_params eltf{};
-  bh_pool_f32_params poolf{};
-  int unary_kind = 0;
-  float lo = 0.f, hi = 0.f, beta = 1.f;
-  int depth = 0;
-  CpuDetectionParams det{};
-  bh_detection_params detg{};  // kDetectionGpu
-  CpuMeanParams mean{};
-  bh_mean_rows_params mrows{};
-  bh_layernorm_params ln{};
-  bh_layernorm_f32_params lnf{};
-  bh_argminmax_params argmm{};
-  bh_resize_argminmax_params rzarg{};
-  bh_reindex_params reindex{};
-  bh_batch_matmul_params bmm{};
-  bh_attention_params attn{};
-  bh_dynquant_params dq{};
-  bh_fc_hybrid_params fch{};
-  bh_dynquant_items_params dqi{};
-  bh_conv_hybrid_params convh{};
-  const void* table = nullptr;  // kLutU8 / kLutF32: 256-entry device table
-  long count = 0;               // kLut* / kQuantF32: elements
-  float q_scale = 0.f;          // kQuantF32
-  int32_t q_zp = 0;
-  int q_signed = 0;
-  void* dst = nullptr;
-  const void* src = nullptr;
-  size_t bytes = 0;
-  double alg_bytes = 0;  // algorithmic HBM bytes per launch (roofline numerator)
-  double alg_ops = 0;    // algorithmic int ops (2 per MAC)
-  const char* kernel = "";
-};
 
 struct LnMatch;  // fusion_transformer.cc
 
