@@ -7,6 +7,7 @@ import ctypes
 import numpy as np
 
 from oracle import runner as orc
+from tests.guarded_output import GuardedOutput
 
 RELU6_SCALE = 6.0 / 255.0
 
@@ -96,7 +97,11 @@ class ChainCase:
         return y, f
 
     # --- GPU: one fused launch -------------------------------------------
-    def params(self, lib, px_blocks, keep, waves=4, persist=0, tile=0, deep=0, c_split=0, stage=0):
+    def params(self, lib, px_blocks, keep, waves=4, persist=0, tile=0, deep=0, c_split=0, stage=0, expect=None,
+               dense=0):
+        """expect: the launch's reference (y_ref, f_ref), from which the guarded
+        outputs are poisoned (tests/guarded_output.py); dense: bh_chain_params.dense"""
+        y_exp, f_exp = expect if expect is not None else (None, None)
         from band_amd import _abi
         from band_amd.device import DeviceBuffer
 
@@ -170,13 +175,13 @@ class ChainCase:
         px = self.b * self.oh * self.ow
         self._y = self._f = None
         if self.store_pw1:
-            self._y = DB(px * self.cout)
+            self._y = GuardedOutput(px * self.cout, y_exp)
             keep.append(self._y)
             c.pw1.output = self._y.value
         if self.ce2:
             c.has_pw2 = 1
             c.pw2 = conv("pw2", self.wf, self.ce2, self.cout, y_zp, self.wf_s, self.y_s, self.f_s, self.bf, self.f_zp, 3)
-            self._f = DB(px * self.ce2)
+            self._f = GuardedOutput(px * self.ce2, f_exp)
             keep.append(self._f)
             c.pw2.output = self._f.value
         c.px_blocks = px_blocks
@@ -186,6 +191,7 @@ class ChainCase:
         c.deep = deep
         c.c_split = c_split
         c.stage = stage
+        c.dense = dense
         if tile or stage:
             nb = lib.bh_chain_tile_blob_bytes(ctypes.byref(c))
             if nb:
@@ -195,10 +201,10 @@ class ChainCase:
                 c.tile_blob = blob.value
         return c
 
-    def gpu(self, lib, px_blocks, waves=4, persist=0, tile=0, deep=0, c_split=0, stage=0):
+    def gpu(self, lib, px_blocks, waves=4, persist=0, tile=0, deep=0, c_split=0, stage=0, expect=None, dense=0):
         from band_amd import _abi
         keep = []
-        c = self.params(lib, px_blocks, keep, waves, persist, tile, deep, c_split, stage)
+        c = self.params(lib, px_blocks, keep, waves, persist, tile, deep, c_split, stage, expect, dense)
         assert lib.bh_chain_lds_bytes(ctypes.byref(c)) > 0, "chain unsupported"
         _abi.check(lib.bh_chain_i8(ctypes.byref(c), None), "bh_chain_i8")
         y = self._y.download(np.int8, (self.b, self.oh, self.ow, self.cout)) if self._y else None

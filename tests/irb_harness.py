@@ -7,6 +7,7 @@ import ctypes
 import numpy as np
 
 from oracle import runner as orc
+from tests.guarded_output import GuardedOutput
 
 RELU6_SCALE = 6.0 / 255.0
 
@@ -94,7 +95,9 @@ class IrbCase:
         return orc.add(p, x, a_zp=self.p_zp, b_zp=self.x_zp, out_zp=self.o_zp, params=prm, amin=lo, amax=hi)
 
     # --- GPU: one fused launch -------------------------------------------
-    def params(self, lib, tile, keep):
+    def params(self, lib, tile, keep, expect=None):
+        """the block's C-ABI params; the output is guarded and poisoned
+        (tests/guarded_output.py) from `expect`, the launch's reference"""
         from band_amd import _abi
         from band_amd.device import DeviceBuffer
 
@@ -163,8 +166,7 @@ class IrbCase:
                 q.requant_fast &= int(self.fast)
         q.input = dev(self.x)
         self.out_shape = (self.b, oh, ow, self.cout)
-        from band_amd.device import DeviceBuffer as DB
-        out = DB(int(np.prod(self.out_shape)))
+        out = GuardedOutput(int(np.prod(self.out_shape)), expect)
         keep.append(out)
         q.output = out.value
         self._out = out
@@ -174,10 +176,10 @@ class IrbCase:
         keep = []
         return lib.bh_irb_lds_bytes(ctypes.byref(self.params(lib, tile, keep))) > 0
 
-    def gpu(self, lib, tile):
+    def gpu(self, lib, tile, expect=None):
         from band_amd import _abi
         keep = []
-        q = self.params(lib, tile, keep)
+        q = self.params(lib, tile, keep, expect)
         assert lib.bh_irb_lds_bytes(ctypes.byref(q)) > 0, "tile %d unsupported" % tile
         _abi.check(lib.bh_irb_i8(ctypes.byref(q), None), "bh_irb_i8")
         return self._out.download(np.int8, self.out_shape)

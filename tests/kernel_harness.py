@@ -7,6 +7,7 @@ import ctypes
 import numpy as np
 
 from oracle import runner as orc
+from tests.guarded_output import GuardedOutput
 
 
 def rand_q(rng, shape, dtype):
@@ -79,9 +80,9 @@ class ConvCase:
             return orc.dwconv2d(self.x, self.w, self.bias, dm=self.dm, **kw)
         return orc.conv2d(self.x, self.w, self.bias, **kw)
 
-    def gpu(self, lib, stream=None):
+    def gpu(self, lib, stream=None, expect=None):
         keep = []
-        p = self.params(lib, keep)
+        p = self.params(lib, keep, expect=expect)
         fn = lib.bh_dwconv2d_i8 if self.depthwise else lib.bh_conv2d_i8
         from band_amd import _abi
         _abi.check(fn(ctypes.byref(p), stream), "bh_dwconv2d_i8" if self.depthwise else "bh_conv2d_i8")
@@ -89,16 +90,18 @@ class ConvCase:
         del keep
         return out
 
-    def params(self, lib, keep, dx=None, dy=None):
+    def params(self, lib, keep, dx=None, dy=None, expect=None):
         """C-ABI params on device copies of the case (buffers appended to
-        `keep`); dx / dy override the activation buffers (timing chains)."""
+        `keep`); dx / dy override the activation buffers (timing chains).
+        The case's own output is guarded and poisoned (tests/guarded_output.py)
+        from `expect`, the reference of the launch about to be made."""
         from band_amd import _abi
         from band_amd.device import DeviceBuffer
         out_shape = (self.b, self.oh, self.ow, self.oc)
         if dx is None:
             dx = DeviceBuffer.from_array(self.x)
         if dy is None:
-            dy = DeviceBuffer(int(np.prod(out_shape)))
+            dy = GuardedOutput(int(np.prod(out_shape)), expect)
         self._dy = dy
         dmult = DeviceBuffer.from_array(self.mult.astype(np.int32))
         dshift = DeviceBuffer.from_array(self.shift.astype(np.int32))

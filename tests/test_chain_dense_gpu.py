@@ -16,6 +16,23 @@ phases, one depthwise channel group and one 1x1 channel tile per load round:
   * second 1x1 of 6, 9 tiles, a partial last tile (ce2 136) and none (ce2 0);
     its K held in 1, 2 or 5 fragments (cout <= 64, 96, 160);
   * residual together with a stored first output; two-step requantisation.
+
+Interior blocks (INTERIOR): phase A asks, per block of 16 raster-consecutive
+pixels, whether every 3x3 tap of every pixel lies inside the image, and then
+runs an instantiation of its own that feeds the loaded dwords to the MFMA with
+no zero-point select.  Such a block lies within one output row and off both
+of its ends, so it needs out_w >= 18: none of the shapes above has one
+(dense_blocks() below restates the rule from the case's geometry;
+tests/test_chain_dense_blocks_cpu.py pins the counts).  The INTERIOR shapes are
+the smallest that have interior blocks beside edge, ragged and - at batch 2 -
+image-spanning ones, at stride 1 and 2 and dilation 2, with 1 and 3 channel
+groups, a residual together with a stored first output, no second 1x1, both
+requantisation forms, and the depthwise input's zero point at -128 and inside.
+
+Narrow 1x1 layers (NARROW): the form admits any out_c % 4 == 0 and every case
+above has a multiple of 8.  out_c of 4, 12 and 20 for the first 1x1 and 20
+for the second: a single partial channel tile, two tiles with a partial last
+one, pixel rows of 1, 3 and 5 four-byte units in the copy-out.
 """
 import ctypes
 
@@ -45,31 +62,106 @@ CASES = [
 ]
 
 
-def _run(lib, c, dense):
+# shapes with interior blocks (b, h, w, stride, dilation: non-empty / interior
+# blocks under the harness's SAME padding): 1x3x33 7 / 1, 1x6x35 14 / 4,
+# 2x5x21 14 / 2 (one per image), 1x5x67 stride 2 7 / 1, 1x7x37 dilation 2 17 / 3
+INTERIOR = [
+    _case(1, 3, 33, 16, 1, 16, True, 32, store_pw1=True, e_zp=-128),    # one group; residual + stored
+    _case(1, 6, 35, 48, 1, 24, False, 0, fast=False, e_zp=7),           # three groups, no second 1x1, two-step
+    _case(2, 5, 21, 48, 1, 8, True, 48, e_zp=-128),                     # blocks span images
+    _case(1, 5, 67, 16, 2, 24, False, 40, fast=False, e_zp=-128),       # stride 2: the borrow is off for column 1
+    _case(1, 7, 37, 48, 1, 16, True, 32, store_pw1=True, dil=2, e_zp=-19),  # the borrow reaches 2 / 4 lanes
+]
+
+NARROW = [
+    _case(1, 5, 7, 16, 1, 4, True, 20),                                 # y of 4, f of 20 channels
+    _case(1, 5, 7, 32, 1, 12, False, 0),                                # y of 12, no second 1x1
+    _case(1, 5, 7, 16, 1, 20, True, 32, store_pw1=True),                # two tiles, the last of 4
+    _case(1, 5, 7, 48, 1, 12, False, 20, store_pw1=True, fast=False),
+]
+
+
+def make_case(args):
+    """the ChainCase of a CASES / INTERIOR / NARROW entry; e_zp, where given,
+    replaces the drawn zero point of the depthwise input"""
+    args = dict(args)
+    e_zp = args.pop("e_zp", None)
+    rng = np.random.default_rng(1 + sum(int(v) for v in args.values()))
+    c = ChainCase(rng, **args)
+    if e_zp is not None:
+        c.e_zp = e_zp
+    return c
+
+
+def dense_blocks(c):
+    """The form's interior rule restated from the case's geometry alone: one
+    flag per non-empty block of 16 raster-consecutive output pixels, true
+    where every pixel exists (m < P) and all nine taps of every pixel - input
+    row oy * stride + s * dil - pad_h, column ox * stride + g * dil - pad_w,
+    s, g in 0 .. 2 - lie inside the h x w image."""
+    P = c.b * c.oh * c.ow
+    m = np.arange((P + 15) // 16 * 16)
+    valid = m < P
+    ox, oy = m % c.ow, m // c.ow % c.oh
+    inside = valid.copy()
+    for k in range(3):
+        y = oy * c.stride + k * c.dil - c.pad[0]
+        x = ox * c.stride + k * c.dil - c.pad[1]
+        inside &= (y >= 0) & (y < c.h) & (x >= 0) & (x < c.w)
+    return inside.reshape(-1, 16).all(axis=1)
+
+
+def _run(lib, c, dense, expect, eligible=False):
     from band_amd import _abi
     keep = []
-    q = c.params(lib, 4, keep, 4)
-    q.dense = dense
+    q = c.params(lib, 4, keep, 4, expect=expect, dense=dense)
     assert lib.bh_chain_lds_bytes(ctypes.byref(q)) > 0, "form not admitted (dense %d)" % dense
+    if eligible and c.fast:  # the single-step requantisation is what such a case is there for
+        assert q.dw.requant_fast and q.pw1.requant_fast and (not c.ce2 or q.pw2.requant_fast), "not eligible"
     _abi.check(lib.bh_chain_i8(ctypes.byref(q), None), "bh_chain_i8")
     y = c._y.download(np.int8, (c.b, c.oh, c.ow, c.cout)) if c._y else None
     f = c._f.download(np.int8, (c.b, c.oh, c.ow, c.ce2)) if c._f else None
     return y, f
 
 
-@pytest.mark.parametrize("args", CASES, ids=lambda a: "b%dx%dx%dce%ds%dd%dco%dce2_%d%s" % (
-    a["b"], a["h"], a["w"], a["ce"], a["stride"], a.get("dil", 1), a["cout"], a["ce2"], "r" if a["residual"] else ""))
-def test_chain_dense(gpu_lib, args):
-    rng = np.random.default_rng(1 + sum(int(v) for v in args.values()))
-    c = ChainCase(rng, **args)
+def _both_forms(lib, c, eligible=False):
+    """dense, then plain, against the oracle (computed once); eligible: a case
+    with `fast` on must get the single-step requantisation in every stage"""
     y_ref, f_ref = c.oracle()
     for dense in (1, 0):
-        y, f = _run(gpu_lib, c, dense)
+        y, f = _run(lib, c, dense, (y_ref, f_ref), eligible)
         tag = "dense form" if dense else "plain form"
         if c.store_pw1:
             np.testing.assert_array_equal(y, y_ref, err_msg="first 1x1, " + tag)
         if c.ce2:
             np.testing.assert_array_equal(f, f_ref, err_msg="second 1x1, " + tag)
+
+
+def _id(a):
+    return "b%dx%dx%dce%ds%dd%dco%dce2_%d%s%s" % (
+        a["b"], a["h"], a["w"], a["ce"], a["stride"], a.get("dil", 1), a["cout"], a["ce2"], "r" if a["residual"] else "",
+        "" if a.get("fast", True) else "two")
+
+
+@pytest.mark.parametrize("args", INTERIOR, ids=_id)
+def test_chain_dense_interior(gpu_lib, args):
+    """cases with blocks on both sides of phase A's interior ballot"""
+    c = make_case(args)
+    interior = dense_blocks(c)
+    assert interior.any(), "no interior block"
+    assert not interior.all(), "no edge or ragged block"
+    _both_forms(gpu_lib, c, eligible=True)
+
+
+@pytest.mark.parametrize("args", NARROW, ids=_id)
+def test_chain_dense_narrow(gpu_lib, args):
+    _both_forms(gpu_lib, make_case(args))
+
+
+@pytest.mark.parametrize("args", CASES, ids=lambda a: "b%dx%dx%dce%ds%dd%dco%dce2_%d%s" % (
+    a["b"], a["h"], a["w"], a["ce"], a["stride"], a.get("dil", 1), a["cout"], a["ce2"], "r" if a["residual"] else ""))
+def test_chain_dense(gpu_lib, args):
+    _both_forms(gpu_lib, make_case(args))
 
 
 def test_dense_form_gate(gpu_lib):
@@ -83,8 +175,7 @@ def test_dense_form_gate(gpu_lib):
         args = dict(px_blocks=4, waves=4, persist=0, tile=0, deep=0, c_split=0, stage=0)
         args.update(kw)
         q = c.params(gpu_lib, args["px_blocks"], keep, args["waves"], args["persist"], args["tile"], args["deep"],
-                     args["c_split"], args["stage"])
-        q.dense = dense
+                     args["c_split"], args["stage"], dense=dense)
         assert (gpu_lib.bh_chain_lds_bytes(ctypes.byref(q)) > 0) == ok, (kw, dense)
 
 

@@ -26,7 +26,7 @@ pytestmark = pytest.mark.gpu
 
 def _check(c, lib, px, waves=4, persist=0, tile=0, deep=0, c_split=0, stage=0):
     y_ref, f_ref = c.oracle()
-    y, f = c.gpu(lib, px, waves, persist, tile, deep, c_split, stage)
+    y, f = c.gpu(lib, px, waves, persist, tile, deep, c_split, stage, expect=(y_ref, f_ref))
     if c.store_pw1:
         np.testing.assert_array_equal(y, y_ref, err_msg="first conv, px_blocks %d" % px)
     if c.ce2:
@@ -410,3 +410,21 @@ def test_chain_tune_file_replay(gpu_lib, tmp_path):
     assert any(ln.startswith(b"ch12:") for ln in files[0].splitlines()), files[0][:400]
     assert kernels[1] == kernels[0]
     assert files[1] == files[0]
+
+
+def test_chain_harness_bites(gpu_lib):
+    """ChainCase's two outputs before any launch: every byte differs from the
+    reference it was poisoned from, 0xa5 throughout without one, and all four
+    guards stand"""
+    c = ChainCase(np.random.default_rng(32), 2, 5, 7, 16, 1, 12, True, 48)
+    y_ref, f_ref = c.oracle()
+    keep = []
+    c.params(gpu_lib, 4, keep, expect=(y_ref, f_ref))
+    for buf, ref in ((c._y, y_ref), (c._f, f_ref)):
+        got = buf.download(np.int8, ref.shape)
+        assert (got != ref).all()
+        np.testing.assert_array_equal(got.view(np.uint8), ref.view(np.uint8) ^ 0x80)
+    c.params(gpu_lib, 4, keep)
+    for buf, ref in ((c._y, y_ref), (c._f, f_ref)):
+        assert (buf.download(np.uint8, ref.shape) == 0xa5).all()
+        assert buf.value % 16 == 0

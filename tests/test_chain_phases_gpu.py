@@ -49,7 +49,7 @@ def _run_forms(lib, args, must_run=()):
         q = c.params(lib, px, keep, waves, 0, 0, deep, split)
         if lib.bh_chain_lds_bytes(ctypes.byref(q)) == 0:
             continue
-        y, f = c.gpu(lib, px, waves, 0, 0, deep, split)
+        y, f = c.gpu(lib, px, waves, 0, 0, deep, split, expect=(y_ref, f_ref))
         tag = "px %d waves %d deep %d split %d" % (px, waves, deep, split)
         if c.store_pw1:
             np.testing.assert_array_equal(y, y_ref, err_msg="first 1x1, " + tag)

@@ -9,6 +9,22 @@ from tests.irb_harness import MNV2_BLOCKS, IrbCase
 pytestmark = pytest.mark.gpu
 
 
+def test_irb_harness_bites(gpu_lib):
+    """IrbCase's output before any launch: every byte differs from the
+    reference it was poisoned from, 0xa5 throughout without one, and both
+    guards stand"""
+    c = IrbCase(np.random.default_rng(33), 2, 5, 7, 8, 48, 8, 1)
+    ref = c.oracle()
+    keep = []
+    c.params(gpu_lib, 1, keep, expect=ref)
+    got = c._out.download(np.int8, c.out_shape)
+    assert (got != ref).all()
+    np.testing.assert_array_equal(got.view(np.uint8), ref.view(np.uint8) ^ 0x80)
+    c.params(gpu_lib, 1, keep)
+    assert (c._out.download(np.uint8, c.out_shape) == 0xa5).all()
+    assert c._out.value % 16 == 0
+
+
 @pytest.mark.parametrize("h,cin,t,cout,s", MNV2_BLOCKS)
 def test_irb_mnv2_blocks(gpu_lib, h, cin, t, cout, s):
     rng = np.random.default_rng(h * 1000 + cin * 10 + cout + s)
@@ -18,9 +34,9 @@ def test_irb_mnv2_blocks(gpu_lib, h, cin, t, cout, s):
         # tile 1 must always fit; larger tiles may exceed the 160 KB LDS budget
         if tile > 1 and not c.supported(gpu_lib, tile):
             continue
-        np.testing.assert_array_equal(c.gpu(gpu_lib, tile), ref, err_msg="tile %d" % tile)
+        np.testing.assert_array_equal(c.gpu(gpu_lib, tile, expect=ref), ref, err_msg="tile %d" % tile)
     c.fast = False  # TFLite's two-step requantisation in every stage
-    np.testing.assert_array_equal(c.gpu(gpu_lib, 1), ref, err_msg="two-step requant")
+    np.testing.assert_array_equal(c.gpu(gpu_lib, 1, expect=ref), ref, err_msg="two-step requant")
 
 
 @pytest.mark.parametrize("args", [
@@ -36,4 +52,4 @@ def test_irb_general(gpu_lib, args):
     c = IrbCase(rng, **args)
     ref = c.oracle()
     for tile in (1, 2, 5):
-        np.testing.assert_array_equal(c.gpu(gpu_lib, tile), ref, err_msg="tile %d" % tile)
+        np.testing.assert_array_equal(c.gpu(gpu_lib, tile, expect=ref), ref, err_msg="tile %d" % tile)

@@ -29,7 +29,7 @@ def launch(lib, c, name, what=""):
     for fast in (None, False):
         c.requant_fast = fast
         keep = []
-        p = c.params(lib, keep)
+        p = c.params(lib, keep, expect=ref)
         namer = lib.bh_dwconv2d_i8_kernel if c.depthwise else lib.bh_conv2d_i8_kernel
         got_name = namer(ctypes.byref(p)).decode()
         assert got_name == name, "%s: routed to %s, wanted %s" % (what, got_name, name)
@@ -109,11 +109,12 @@ def test_conv_group_directed(gpu_lib, family):
     deep, shallow = dh.epilogues(family, I8, 192), dh.epilogues(family, I8, 16)
     for i in range(len(shallow)):
         convs = [dh.conv_layer(deep[i % len(deep)], ic=192, seed=i), dh.conv_layer(shallow[i], seed=i)]
+        refs = [cc.oracle() for cc in convs]
         for fast in (None, False):
             keep, params = [], []
-            for cc in convs:
+            for cc, ref in zip(convs, refs):
                 cc.requant_fast = fast
-                params.append(cc.params(gpu_lib, keep))
+                params.append(cc.params(gpu_lib, keep, expect=ref))
                 cc._dy_keep = cc._dy
                 assert gpu_lib.bh_conv_group_ok(ctypes.byref(params[-1])) == 1
                 if fast is None:
@@ -127,7 +128,7 @@ def test_conv_group_directed(gpu_lib, family):
             _abi.check(gpu_lib.bh_conv_group_i8(ctypes.byref(g), None), "bh_conv_group_i8")
             for j, cc in enumerate(convs):
                 got = cc._dy_keep.download(cc.dtype, (cc.b, cc.oh, cc.ow, cc.oc))
-                np.testing.assert_array_equal(got, cc.oracle(), err_msg="%s member %d fast %s" % (cc.epi.name, j, fast))
+                np.testing.assert_array_equal(got, refs[j], err_msg="%s member %d fast %s" % (cc.epi.name, j, fast))
             del keep, dt
             if family == "two":
                 break
@@ -445,7 +446,7 @@ def run_residual(lib, c, name, what=""):
             for fast in (None, False):
                 c.requant_fast = fast
                 keep = []
-                p = c.params(lib, keep)
+                p = c.params(lib, keep, expect=ref)
                 dr = DeviceBuffer.from_array(r)
                 keep.append(dr)
                 p.residual = dr.value

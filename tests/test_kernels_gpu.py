@@ -25,11 +25,37 @@ def kernel_name(lib, c):
     return name
 
 
+@pytest.mark.parametrize("dtype", [np.int8, np.uint8])
+def test_conv_harness_bites(gpu_lib, dtype):
+    """ConvCase's output before any launch: every byte differs from the
+    reference it was poisoned from (an unwritten byte cannot compare equal),
+    0xa5 throughout without one, and both guards stand"""
+    c = ConvCase(np.random.default_rng(31), 2, 5, 7, 16, 12, 1, 1, dtype=dtype)
+    ref = c.oracle()
+    keep = []
+    c.params(gpu_lib, keep, expect=ref)
+    got = c._dy.download(dtype, ref.shape)
+    assert (got != ref).all()
+    np.testing.assert_array_equal(got.view(np.uint8), ref.view(np.uint8) ^ 0x80)
+    c.params(gpu_lib, keep)
+    assert (c._dy.download(np.uint8, ref.shape) == 0xa5).all()
+    assert c._dy.value % 16 == 0
+    # a changed guard byte (put there by a host copy) is reported with its side
+    raw = c._dy.buf.download(np.uint8, (ref.size + 128,))
+    for at, side in ((63, "in front of"), (64 + ref.size, "behind")):
+        bad = raw.copy()
+        bad[at] = 0
+        c._dy.buf.upload(bad)
+        with pytest.raises(AssertionError, match=side):
+            c._dy.download(dtype, ref.shape)
+
+
 @pytest.mark.parametrize("spatial,ic,oc", MNV2_POINTWISE)
 def test_conv1x1_mnv2_shapes_int8(gpu_lib, spatial, ic, oc):
     rng = np.random.default_rng(1000 + spatial * 7 + ic + oc)
     c = ConvCase(rng, 1, spatial, spatial, ic, oc, 1, 1, act=3)
-    np.testing.assert_array_equal(c.gpu(gpu_lib), c.oracle())
+    ref = c.oracle()
+    np.testing.assert_array_equal(c.gpu(gpu_lib, expect=ref), ref)
 
 
 # batched 1x1 layers (job batching): K <= 320 and M = b*h*w >= 2048 output
@@ -47,9 +73,9 @@ def test_conv1x1_rows_batched(gpu_lib, b, spatial, ic, oc, dtype):
     c = ConvCase(rng, b, spatial, spatial, ic, oc, 1, 1, dtype=dtype, act=3)
     ref = c.oracle()
     assert kernel_name(gpu_lib, c) == "conv_xs_kernel"
-    np.testing.assert_array_equal(c.gpu(gpu_lib), ref)
+    np.testing.assert_array_equal(c.gpu(gpu_lib, expect=ref), ref)
     c.requant_fast = False  # the two-step requantisation path
-    np.testing.assert_array_equal(c.gpu(gpu_lib), ref)
+    np.testing.assert_array_equal(c.gpu(gpu_lib, expect=ref), ref)
 
 
 # the LDS-staged GEMM (conv_gemm_kernel, forced with BH_CONV_GEMM = 2) beside
@@ -71,7 +97,7 @@ def test_conv1x1_gemm_vs_mfma(gpu_lib, b, spatial, ic, oc):
         assert kernel_name(gpu_lib, c) == names[hint], "hint %d" % hint
         for fast in (None, False):
             c.requant_fast = fast
-            np.testing.assert_array_equal(c.gpu(gpu_lib), ref, err_msg="hint %d fast %s" % (hint, fast))
+            np.testing.assert_array_equal(c.gpu(gpu_lib, expect=ref), ref, err_msg="hint %d fast %s" % (hint, fast))
 
 
 # conv_gemm_big_kernel at the sizes it is routed to (M in the tens of
@@ -93,7 +119,7 @@ def test_conv1x1_gemm_big_routed(gpu_lib, b, spatial, ic, oc):
         c.kernel_hint = hint
         for fast in (None, False):
             c.requant_fast = fast
-            np.testing.assert_array_equal(c.gpu(gpu_lib), ref, err_msg="hint %d fast %s" % (hint, fast))
+            np.testing.assert_array_equal(c.gpu(gpu_lib, expect=ref), ref, err_msg="hint %d fast %s" % (hint, fast))
 
 
 # the big GEMM's folded residual ADD and 8-bit output table, applied per byte
@@ -117,7 +143,7 @@ def test_conv1x1_gemm_big_residual_table(gpu_lib, b, spatial, ch):
     outs = {}
     for hint in (3, 1):
         keep = []
-        p = c.params(gpu_lib, keep)
+        p = c.params(gpu_lib, keep, expect=ref)
         dr = DeviceBuffer.from_array(r)
         dt = DeviceBuffer.from_array(table)
         keep += [dr, dt]
@@ -159,7 +185,7 @@ def test_conv_stem(gpu_lib, b, h, w, oc, stride, same, dtype):
         assert kernel_name(gpu_lib, c) == stem_form(hint, oc, b * c.oh * c.ow), "hint %d" % hint
         for fast in (None, False):
             c.requant_fast = fast
-            np.testing.assert_array_equal(c.gpu(gpu_lib), ref, err_msg="hint %d fast %s" % (hint, fast))
+            np.testing.assert_array_equal(c.gpu(gpu_lib, expect=ref), ref, err_msg="hint %d fast %s" % (hint, fast))
 
 
 def stem_form(hint, oc, m):
@@ -177,14 +203,16 @@ def stem_form(hint, oc, m):
 def test_conv_first_layer_3x3_s2_int8(gpu_lib):
     rng = np.random.default_rng(7)
     c = ConvCase(rng, 1, 224, 224, 3, 32, 3, 3, stride=(2, 2), act=3)
-    np.testing.assert_array_equal(c.gpu(gpu_lib), c.oracle())
+    ref = c.oracle()
+    np.testing.assert_array_equal(c.gpu(gpu_lib, expect=ref), ref)
 
 
 @pytest.mark.parametrize("spatial,ic,oc", MNV2_POINTWISE[::4])
 def test_conv1x1_uint8_per_tensor(gpu_lib, spatial, ic, oc):
     rng = np.random.default_rng(2000 + spatial + ic + oc)
     c = ConvCase(rng, 1, spatial, spatial, ic, oc, 1, 1, dtype=np.uint8, act=3)
-    np.testing.assert_array_equal(c.gpu(gpu_lib), c.oracle())
+    ref = c.oracle()
+    np.testing.assert_array_equal(c.gpu(gpu_lib, expect=ref), ref)
 
 
 @pytest.mark.parametrize("args", [
@@ -204,14 +232,16 @@ def test_conv1x1_uint8_per_tensor(gpu_lib, spatial, ic, oc):
 def test_conv_general(gpu_lib, args):
     rng = np.random.default_rng(zlib.crc32(repr(sorted(args.items())).encode()))
     c = ConvCase(rng, **args)
-    np.testing.assert_array_equal(c.gpu(gpu_lib), c.oracle())
+    ref = c.oracle()
+    np.testing.assert_array_equal(c.gpu(gpu_lib, expect=ref), ref)
 
 
 @pytest.mark.parametrize("spatial,ch,stride", MNV2_DEPTHWISE)
 def test_dwconv_mnv2_shapes(gpu_lib, spatial, ch, stride):
     rng = np.random.default_rng(3000 + spatial + ch + stride)
     c = ConvCase(rng, 1, spatial, spatial, ch, ch, 3, 3, stride=(stride, stride), depthwise=True)
-    np.testing.assert_array_equal(c.gpu(gpu_lib), c.oracle())
+    ref = c.oracle()
+    np.testing.assert_array_equal(c.gpu(gpu_lib, expect=ref), ref)
 
 
 # the dot4 kernel (tap table) and the per-tap kernel against the oracle:
@@ -246,10 +276,10 @@ def test_dwconv_taps_vs_per_tap(gpu_lib, b, h, w, ch, stride, dil, dtype):
         assert kernel_name(gpu_lib, c) == names[hint], "hint %d" % hint
         for fast in (None, False):
             c.requant_fast = fast
-            np.testing.assert_array_equal(c.gpu(gpu_lib), ref, err_msg="hint %d requant_fast %s" % (hint, fast))
+            np.testing.assert_array_equal(c.gpu(gpu_lib, expect=ref), ref, err_msg="hint %d requant_fast %s" % (hint, fast))
     c.kernel_hint, c.taps = 0, False
     assert kernel_name(gpu_lib, c) == "dwconv3x3_kernel"
-    np.testing.assert_array_equal(c.gpu(gpu_lib), ref)
+    np.testing.assert_array_equal(c.gpu(gpu_lib, expect=ref), ref)
 
 
 # the MFMA form (block-diagonal filter fragments) on every MobileNetV2
@@ -265,9 +295,9 @@ def test_dwconv_mfma_mnv2_layers(gpu_lib, h, ch, stride, dtype):
     c = ConvCase(rng, b, h, h, ch, ch, 3, 3, stride=(stride, stride), depthwise=True, dtype=dtype, kernel_hint=3)
     ref = c.oracle()
     assert kernel_name(gpu_lib, c) == "dwconv3x3_mfma_kernel"  # every C here is a multiple of 16
-    np.testing.assert_array_equal(c.gpu(gpu_lib), ref)
+    np.testing.assert_array_equal(c.gpu(gpu_lib, expect=ref), ref)
     c.requant_fast = False
-    np.testing.assert_array_equal(c.gpu(gpu_lib), ref)
+    np.testing.assert_array_equal(c.gpu(gpu_lib, expect=ref), ref)
 
 
 @pytest.mark.parametrize("args", [
@@ -281,7 +311,8 @@ def test_dwconv_general(gpu_lib, args):
     args["depthwise"] = True
     rng = np.random.default_rng(zlib.crc32(repr(sorted(args.items())).encode()))
     c = ConvCase(rng, **args)
-    np.testing.assert_array_equal(c.gpu(gpu_lib), c.oracle())
+    ref = c.oracle()
+    np.testing.assert_array_equal(c.gpu(gpu_lib, expect=ref), ref)
 
 
 def _elt(gpu_lib, a, b, kind, dtype, rng, sub=False):
@@ -434,14 +465,15 @@ def test_conv_group(gpu_lib, cases, is1x1):
     from band_amd import _abi
     from band_amd.device import DeviceBuffer
     rng = np.random.default_rng(7100 + len(cases) + is1x1)
-    convs, keep, params = [], [], []
+    convs, keep, params, refs = [], [], [], []
     for c in cases:
         b, sp, ic, oc = c[:4]
         dtype = c[4] if len(c) > 4 else np.int8
         k = c[5] if len(c) > 5 else 1
         cc = ConvCase(rng, b, sp, sp, ic, oc, k, k, dtype=dtype, act=3)
         convs.append(cc)
-        params.append(cc.params(gpu_lib, keep))
+        refs.append(cc.oracle())
+        params.append(cc.params(gpu_lib, keep, expect=refs[-1]))
         cc._dy_keep = cc._dy
     for cc, p in zip(convs, params):
         assert gpu_lib.bh_conv_group_ok(ctypes.byref(p)) == 1
@@ -457,7 +489,7 @@ def test_conv_group(gpu_lib, cases, is1x1):
     _abi.check(gpu_lib.bh_conv_group_i8(ctypes.byref(g), None), "bh_conv_group_i8")
     for i, cc in enumerate(convs):
         got = cc._dy_keep.download(cc.dtype, (cc.b, cc.oh, cc.ow, cc.oc))
-        np.testing.assert_array_equal(got, cc.oracle(), err_msg="member %d" % i)
+        np.testing.assert_array_equal(got, refs[i], err_msg="member %d" % i)
     del keep, dt
 
 
