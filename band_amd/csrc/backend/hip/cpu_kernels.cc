@@ -103,6 +103,13 @@ inline int32_t Requant(int32_t x, int32_t m, int32_t shift) {
 }
 inline int32_t RequantLt1(int32_t x, int32_t m, int32_t left_shift) { return Rdbypot(Srdhm(x, m), -left_shift); }
 inline int32_t Clamp(int32_t v, int32_t lo, int32_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// the residual ADD folded into a CONV_2D epilogue (add.cc for 8-bit operands):
+// y = the layer's requantised value, r = the residual value
+inline int32_t ResidualAdd(const bh_conv_params& p, int32_t y, int32_t r) {
+  const int32_t sy = RequantLt1((y + p.add_y_off) * (1 << p.add_left_shift), p.add_y_mult, p.add_y_shift);
+  const int32_t sr = RequantLt1((r + p.add_r_off) * (1 << p.add_left_shift), p.add_r_mult, p.add_r_shift);
+  return Clamp(RequantLt1(sy + sr, p.add_o_mult, p.add_o_shift) + p.add_o_off, p.add_act_min, p.add_act_max);
+}
 
 // int8 x int8 dot product (vectorised per target by the compiler)
 __attribute__((target_clones("arch=skylake-avx512", "avx2", "default"))) int32_t Dot(const int8_t* a, const int8_t* b, int n) {
@@ -133,70 +140,8 @@ inline int32_t Load8(const uint8_t* p, long i, bool is_signed) {
 }
 }  // namespace
 
-// ---- CONV_2D: packed [n_pad][k_pad] int8-domain filters, folded bias ---------
-
-void CpuConv(const bh_conv_params& p, CpuPool& pool) {
-  const long M = static_cast<long>(p.batch) * p.out_h * p.out_w;
-  const int K = p.k_h * p.k_w * p.in_c;
-  const uint8_t* in = static_cast<const uint8_t*>(p.input);
-  const int8_t* W = p.weights;
-  uint8_t* out = static_cast<uint8_t*>(p.output);
-  const uint8_t* res = static_cast<const uint8_t*>(p.residual);
-  const uint8_t* tab = static_cast<const uint8_t*>(p.out_table);
-  const uint8_t xorb = static_cast<uint8_t>(p.in_xor);
-  const int8_t padv = static_cast<int8_t>(p.in_zp);
-  pool.ParallelFor(M, [&](long m0, long m1) {
-    std::vector<int8_t> row(static_cast<size_t>(K));
-    std::vector<int32_t> acc(static_cast<size_t>(p.out_c) + 4);
-    for (long m = m0; m < m1; ++m) {
-      const int ox = static_cast<int>(m % p.out_w);
-      const long t = m / p.out_w;
-      const int oy = static_cast<int>(t % p.out_h);
-      const int n = static_cast<int>(t / p.out_h);
-      const int y0 = oy * p.stride_h - p.pad_h, x0 = ox * p.stride_w - p.pad_w;
-      // im2col row in the int8 domain; out-of-image taps hold the input zp
-      int k = 0;
-      for (int fy = 0; fy < p.k_h; ++fy) {
-        const int y = y0 + fy * p.dil_h;
-        for (int fx = 0; fx < p.k_w; ++fx) {
-          const int x = x0 + fx * p.dil_w;
-          if (y < 0 || y >= p.in_h || x < 0 || x >= p.in_w) {
-            std::memset(&row[k], static_cast<uint8_t>(padv), p.in_c);
-          } else {
-            const uint8_t* src = in + ((static_cast<long>(n) * p.in_h + y) * p.in_w + x) * p.in_c;
-            for (int c = 0; c < p.in_c; ++c) row[k + c] = static_cast<int8_t>(src[c] ^ xorb);
-          }
-          k += p.in_c;
-        }
-      }
-      int32_t rowsum = 0;
-      if (p.w_zp != 0)
-        for (int i = 0; i < K; ++i) rowsum += row[i];
-      int c = 0;
-      for (; c + 4 <= p.out_c; c += 4) {
-        const int8_t* w = W + static_cast<long>(c) * p.k_pad;
-        Dot4(row.data(), w, w + p.k_pad, w + 2 * p.k_pad, w + 3 * p.k_pad, K, &acc[c]);
-      }
-      for (; c < p.out_c; ++c) acc[c] = Dot(row.data(), W + static_cast<long>(c) * p.k_pad, K);
-      uint8_t* o = out + m * p.out_c;
-      for (c = 0; c < p.out_c; ++c) {
-        int32_t a = acc[c] + p.bias_eff[c];
-        if (p.w_zp != 0) a -= p.w_zp * rowsum;
-        int32_t v = Clamp(Requant(a, p.mult[c], p.shift[c]) + p.out_zp, p.act_min, p.act_max);
-        if (res) {
-          const int32_t q = Load8(res, m * p.out_c + c, p.in_xor == 0);
-          const int32_t sy = RequantLt1((v + p.add_y_off) * (1 << p.add_left_shift), p.add_y_mult, p.add_y_shift);
-          const int32_t sr = RequantLt1((q + p.add_r_off) * (1 << p.add_left_shift), p.add_r_mult, p.add_r_shift);
-          v = Clamp(RequantLt1(sy + sr, p.add_o_mult, p.add_o_shift) + p.add_o_off, p.add_act_min, p.add_act_max);
-        }
-        const uint8_t byte = static_cast<uint8_t>(v);
-        o[c] = tab ? tab[byte] : byte;
-      }
-    }
-  });
-}
-
-// ---- grouped CONV_2D: CpuConv per group (rows of K_g, the group's slice) ------
+// ---- CONV_2D, dense and grouped: packed [n_pad][k_pad] int8-domain filters
+// (K = the group's k_h * k_w * in_c / groups), folded bias ---------------------
 
 void CpuConvGrouped(const bh_conv_params& p, int groups, CpuPool& pool) {
   const long M = static_cast<long>(p.batch) * p.out_h * p.out_w;
@@ -211,6 +156,7 @@ void CpuConvGrouped(const bh_conv_params& p, int groups, CpuPool& pool) {
   const int8_t padv = static_cast<int8_t>(p.in_zp);
   pool.ParallelFor(M, [&](long m0, long m1) {
     std::vector<int8_t> row(static_cast<size_t>(K));
+    std::vector<int32_t> acc(static_cast<size_t>(ocg));
     for (long m = m0; m < m1; ++m) {
       const int ox = static_cast<int>(m % p.out_w);
       const long t = m / p.out_w;
@@ -219,7 +165,8 @@ void CpuConvGrouped(const bh_conv_params& p, int groups, CpuPool& pool) {
       const int y0 = oy * p.stride_h - p.pad_h, x0 = ox * p.stride_w - p.pad_w;
       uint8_t* o = out + m * p.out_c;
       for (int g = 0; g < groups; ++g) {
-        // im2col row of the group's channel slice; out-of-image taps hold the input zp
+        // im2col row of the group's channel slice in the int8 domain;
+        // out-of-image taps hold the input zp
         int k = 0;
         for (int fy = 0; fy < p.k_h; ++fy) {
           const int y = y0 + fy * p.dil_h;
@@ -237,16 +184,20 @@ void CpuConvGrouped(const bh_conv_params& p, int groups, CpuPool& pool) {
         int32_t rowsum = 0;
         if (p.w_zp != 0)
           for (int i = 0; i < K; ++i) rowsum += row[i];
-        for (int c = g * ocg; c < (g + 1) * ocg; ++c) {
-          int32_t a = Dot(row.data(), W + static_cast<long>(c) * p.k_pad, K) + p.bias_eff[c];
+        // the group's channels, four filter rows per pass over the im2col row
+        const int8_t* Wg = W + static_cast<long>(g) * ocg * p.k_pad;
+        int j = 0;
+        for (; j + 4 <= ocg; j += 4) {
+          const int8_t* w = Wg + static_cast<long>(j) * p.k_pad;
+          Dot4(row.data(), w, w + p.k_pad, w + 2 * p.k_pad, w + 3 * p.k_pad, K, &acc[j]);
+        }
+        for (; j < ocg; ++j) acc[j] = Dot(row.data(), Wg + static_cast<long>(j) * p.k_pad, K);
+        for (j = 0; j < ocg; ++j) {
+          const int c = g * ocg + j;
+          int32_t a = acc[j] + p.bias_eff[c];
           if (p.w_zp != 0) a -= p.w_zp * rowsum;
           int32_t v = Clamp(Requant(a, p.mult[c], p.shift[c]) + p.out_zp, p.act_min, p.act_max);
-          if (res) {
-            const int32_t q = Load8(res, m * p.out_c + c, p.in_xor == 0);
-            const int32_t sy = RequantLt1((v + p.add_y_off) * (1 << p.add_left_shift), p.add_y_mult, p.add_y_shift);
-            const int32_t sr = RequantLt1((q + p.add_r_off) * (1 << p.add_left_shift), p.add_r_mult, p.add_r_shift);
-            v = Clamp(RequantLt1(sy + sr, p.add_o_mult, p.add_o_shift) + p.add_o_off, p.add_act_min, p.add_act_max);
-          }
+          if (res) v = ResidualAdd(p, v, Load8(res, m * p.out_c + c, p.in_xor == 0));
           const uint8_t byte = static_cast<uint8_t>(v);
           o[c] = tab ? tab[byte] : byte;
         }
@@ -254,6 +205,8 @@ void CpuConvGrouped(const bh_conv_params& p, int groups, CpuPool& pool) {
     }
   });
 }
+
+void CpuConv(const bh_conv_params& p, CpuPool& pool) { CpuConvGrouped(p, 1, pool); }
 
 // ---- DEPTHWISE_CONV_2D: [kh][kw][out_c] int8-domain filters, raw bias -------
 

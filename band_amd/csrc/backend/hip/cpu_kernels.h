@@ -48,9 +48,10 @@ class CpuPool {
 };
 
 // the launch kinds of launch.h with their host implementations
-void CpuConv(const bh_conv_params& p, CpuPool& pool);
-// grouped CONV_2D: p with the total channel counts, filters packed with K = K_g
+// CONV_2D: p with the total channel counts, filters packed with K = K_g (the
+// group's slice); CpuConv is the one-group call
 void CpuConvGrouped(const bh_conv_params& p, int groups, CpuPool& pool);
+void CpuConv(const bh_conv_params& p, CpuPool& pool);
 void CpuDwConv(const bh_dwconv_params& p, CpuPool& pool);
 void CpuFc(const bh_fc_params& p, CpuPool& pool);
 void CpuEltwise(const bh_eltwise_params& p, CpuPool& pool);

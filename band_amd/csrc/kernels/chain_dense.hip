@@ -27,6 +27,7 @@
 
 #include "chain_dw.hpp"
 #include "common.hpp"
+#include "residual_add.hpp"
 
 namespace bh {
 
@@ -229,13 +230,7 @@ __global__ __launch_bounds__(256, WPE) void chain_dense_kernel(bh_chain_params c
   // residual ADD: both operands' rescalings as 256-entry tables (chain_kernel)
   const int* add_tab = (const int*)(smem + L.off_add);
   if (cp.pw1.residual) {
-    const bh_conv_params& a = cp.pw1;
-    int* tab = (int*)(smem + L.off_add);
-    for (int i = threadIdx.x; i < 512; i += 256) {
-      const int q = (i & 255) - 128;
-      tab[i] = i < 256 ? requant_lt1((q + a.add_y_off) * (1 << a.add_left_shift), a.add_y_mult, a.add_y_shift)
-                       : requant_lt1((q + a.add_r_off) * (1 << a.add_left_shift), a.add_r_mult, a.add_r_shift);
-    }
+    residual_tab_build((int*)(smem + L.off_add), cp.pw1, threadIdx.x, 256);
     __syncthreads();  // the only workgroup barrier
   }
   if (mw >= P) return;  // an empty block of the last workgroup
@@ -254,6 +249,7 @@ __global__ __launch_bounds__(256, WPE) void chain_dense_kernel(bh_chain_params c
     const int KS1 = a.k_pad >> 6;
     const unsigned char* xrow = dl + r16 * L.S1 + g * 16;
     const uint8_t* res = (const uint8_t*)a.residual;
+    const ResidualAdd A = residual_of(a);
     const DenseConv ac = dense_conv(a, r16, g);
     for (int t = 0; t < T1; ++t) {
       // rounds of two K-steps, each a load round of its own: the SIMD's other
@@ -282,12 +278,7 @@ __global__ __launch_bounds__(256, WPE) void chain_dense_kernel(bh_chain_params c
           for (int r = 0; r < 4; ++r)  // rows past P: a valid address, the value never stored
             rq[r] = (int32_t)(int8_t)res[(uint32_t)(min(mw + orow + r, P - 1) * N1 + n)];
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int32_t sy = add_tab[v[r] + 128];
-            const int32_t sr = add_tab[256 + rq[r] + 128];
-            v[r] = clamp_i32(requant_lt1(sy + sr, a.add_o_mult, a.add_o_shift) + a.add_o_off, a.add_act_min,
-                             a.add_act_max);
-          }
+          for (int r = 0; r < 4; ++r) v[r] = residual_add_tab(add_tab, A, v[r], rq[r]);
         }
         stage4(pl, L.S2, orow, n, v);
       }

@@ -30,6 +30,7 @@
 #include "chain_blob.hpp"
 #include "chain_dw.hpp"
 #include "common.hpp"
+#include "residual_add.hpp"
 
 namespace bh {
 
@@ -182,13 +183,7 @@ __global__ __launch_bounds__(NW * 64) void chain_stage_kernel(bh_chain_params cp
   // residual ADD: add.cc rescales each 8-bit operand on its own, so both
   // rescalings are 256-entry tables (built while the burst is in flight)
   int* add_tab = (int*)(smem + G.off_add);
-  if (a.residual) {
-    for (int i = tid; i < 512; i += NW * 64) {
-      const int q = (i & 255) - 128;
-      add_tab[i] = i < 256 ? requant_lt1((q + a.add_y_off) * (1 << a.add_left_shift), a.add_y_mult, a.add_y_shift)
-                           : requant_lt1((q + a.add_r_off) * (1 << a.add_left_shift), a.add_r_mult, a.add_r_shift);
-    }
-  }
+  if (a.residual) residual_tab_build(add_tab, a, tid, NW * 64);
 
   // ---- phase A: depthwise 3x3 (global taps) -> dl -------------------------
   if (LW == 0 || wave < NA) chain_dw_mfma<FAST, 2, NA / RB>(cp.dw, dv, m, m < P, lane, r16, g, wsub, dl, G.S1, orow);
@@ -205,6 +200,7 @@ __global__ __launch_bounds__(NW * 64) void chain_stage_kernel(bh_chain_params cp
     const int* s1 = m1 + N1;
     const unsigned char* xrow = dl + (pb * 16 + r16) * G.S1 + g * 16;
     const bool out1 = a.output != nullptr && blockIdx.y == 0;  // slice 0 stores the block output
+    const ResidualAdd A = residual_of(a);
     auto epi = [&](int nch, v4i acc) {
       if (nch >= N1) return;
       const ChanQ q = chan_q(m1[nch], s1[nch], a.out_zp);
@@ -215,9 +211,7 @@ __global__ __launch_bounds__(NW * 64) void chain_stage_kernel(bh_chain_params cp
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int32_t rq = (int32_t)(int8_t)resl[(orow + r) * N1 + nch];  // rows past `rows`: never stored
-          v[r] = clamp_i32(requant_lt1(add_tab[v[r] + 128] + add_tab[256 + rq + 128], a.add_o_mult, a.add_o_shift) +
-                               a.add_o_off,
-                           a.add_act_min, a.add_act_max);
+          v[r] = residual_add_tab(add_tab, A, v[r], rq);
         }
       }
       if (out1) stage4(o1, N1, orow, nch, v);

@@ -9,6 +9,7 @@
 // byte of the window is loaded at once (one memory round trip) and the dot
 // products are v_dot4_i32_i8.
 #include "common.hpp"
+#include "residual_add.hpp"
 #include "stem_window.hpp"
 
 namespace bh {
@@ -75,10 +76,7 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(bh_conv_params p, int 
     if (p.w_zp != 0) acc -= p.w_zp * rowsum;
     int32_t v = clamp_i32(requant(acc, p.mult[oc], p.shift[oc]) + p.out_zp, p.act_min, p.act_max);
     if (res) {
-      const int32_t q = p.in_xor == 0 ? (int32_t)(int8_t)res[obase + oc] : (int32_t)res[obase + oc];
-      const int32_t sy = requant_lt1((v + p.add_y_off) * (1 << p.add_left_shift), p.add_y_mult, p.add_y_shift);
-      const int32_t sr = requant_lt1((q + p.add_r_off) * (1 << p.add_left_shift), p.add_r_mult, p.add_r_shift);
-      v = clamp_i32(requant_lt1(sy + sr, p.add_o_mult, p.add_o_shift) + p.add_o_off, p.add_act_min, p.add_act_max);
+      v = residual_add(residual_of(p), v, residual_byte(res[obase + oc], 0, p.in_xor == 0));
     }
     const uint32_t byte = p.out_table ? ((const uint8_t*)p.out_table)[(uint8_t)v] : ((uint32_t)v & 0xffu);
     packed[c >> 2] |= byte << (8 * (c & 3));

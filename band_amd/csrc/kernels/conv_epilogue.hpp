@@ -5,6 +5,7 @@
 #pragma once
 
 #include "common.hpp"
+#include "residual_add.hpp"
 
 namespace bh {
 
@@ -119,6 +120,7 @@ __device__ __forceinline__ void conv_store4(const bh_conv_params& p, v4i acc, in
         if (nb + r < N) rq |= (uint32_t)res[o + r] << (8 * r);
     }
   }
+  const ResidualAdd A = residual_of(p);
   uint32_t packed = 0;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -126,13 +128,7 @@ __device__ __forceinline__ void conv_store4(const bh_conv_params& p, v4i acc, in
     if (p.w_zp != 0) a -= p.w_zp * rsum;
     int32_t v = p.requant_fast ? requant_out<true>(a, c.q[r], p.out_zp, p.act_min, p.act_max)
                                : requant_out<false>(a, c.q[r], p.out_zp, p.act_min, p.act_max);
-    if (res) {
-      const uint32_t qb = (rq >> (8 * r)) & 0xffu;
-      const int32_t q = res_signed ? (int32_t)(int8_t)qb : (int32_t)qb;
-      const int32_t sy = requant_lt1((v + p.add_y_off) * (1 << p.add_left_shift), p.add_y_mult, p.add_y_shift);
-      const int32_t sr = requant_lt1((q + p.add_r_off) * (1 << p.add_left_shift), p.add_r_mult, p.add_r_shift);
-      v = clamp_i32(requant_lt1(sy + sr, p.add_o_mult, p.add_o_shift) + p.add_o_off, p.add_act_min, p.add_act_max);
-    }
+    if (res) v = residual_add(A, v, residual_byte(rq, r, res_signed));
     const uint32_t byte = tab ? tab[(uint8_t)v] : ((uint32_t)v & 0xffu);
     packed |= byte << (8 * r);
   }

@@ -39,6 +39,7 @@
 //     pixel block consecutive, so a pixel block is fetched from HBM once per
 //     XCD and re-read by its N-blocks from that XCD's L2.
 #include "common.hpp"
+#include "residual_add.hpp"
 
 namespace bh {
 
@@ -57,10 +58,7 @@ __device__ __forceinline__ uint8_t big_post(const bh_conv_params& p, uint8_t y, 
                                             bool r_signed, const uint8_t* tab, bool res) {
   int32_t v = y_signed ? (int32_t)(int8_t)y : (int32_t)y;
   if (res) {
-    const int32_t q = r_signed ? (int32_t)(int8_t)r : (int32_t)r;
-    const int32_t sy = requant_lt1((v + p.add_y_off) * (1 << p.add_left_shift), p.add_y_mult, p.add_y_shift);
-    const int32_t sr = requant_lt1((q + p.add_r_off) * (1 << p.add_left_shift), p.add_r_mult, p.add_r_shift);
-    v = clamp_i32(requant_lt1(sy + sr, p.add_o_mult, p.add_o_shift) + p.add_o_off, p.add_act_min, p.add_act_max);
+    v = residual_add(residual_of(p), v, residual_byte(r, 0, r_signed));
   }
   return tab ? tab[(uint8_t)v] : (uint8_t)v;
 }

@@ -22,6 +22,7 @@
 // Workgroup ids are remapped so that the chunks of one pixel block run on
 // one XCD (its L2 then serves the block's input rows to every chunk).
 #include "common.hpp"
+#include "residual_add.hpp"
 
 namespace bh {
 
@@ -63,6 +64,23 @@ __device__ __forceinline__ int rowsum16b(v4i a, int s) {
 }
 
 // ChanQ / chan_q / requant_out: common.hpp
+
+// The tail of both kernels' tile epilogue: the lane's four requantised
+// values (channels nb..nb+3 of one pixel, output offset o) through the folded
+// residual ADD and the byte table to the packed dword.
+__device__ __forceinline__ uint32_t finish4(const ResidualAdd& A, int32_t v[4], const uint8_t* res, long o,
+                                            bool res_signed, const uint8_t* tab) {
+  if (res) {
+    const uint32_t rq = *(const uint32_t*)(res + o);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = residual_add(A, v[r], residual_byte(rq, r, res_signed));
+  }
+  if (tab) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = tab[(uint8_t)v[r]];
+  }
+  return pack4_bytes(v);
+}
 
 template <int RB, int NT, int VEC, bool FAST>
 __global__ __launch_bounds__(256) void conv_rows_kernel(bh_conv_params p, int M, int K, int N, int mblocks,
@@ -135,7 +153,8 @@ __global__ __launch_bounds__(256) void conv_rows_kernel(bh_conv_params p, int M,
 
   uint8_t* out = (uint8_t*)p.output;
   const uint8_t* res = (const uint8_t*)p.residual;
-  const bool res_signed = p.in_xor == 0;
+  const bool res_signed = p.in_xor == 0;  // the residual shares the activation type
+  const ResidualAdd A = residual_of(p);
   const uint8_t* tab = (const uint8_t*)p.out_table;
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
@@ -162,28 +181,7 @@ __global__ __launch_bounds__(256) void conv_rows_kernel(bh_conv_params p, int M,
         if (wzp) a -= p.w_zp * rs[b];
         v[r] = requant_out<FAST>(a, q[r], p.out_zp, p.act_min, p.act_max);
       }
-      if (res) {
-        const uint32_t rq = *(const uint32_t*)(res + o);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const uint32_t qb = (rq >> (8 * r)) & 0xffu;
-          const int32_t qv = res_signed ? (int32_t)(int8_t)qb : (int32_t)qb;
-          const int32_t sy =
-              requant_lt1((v[r] + p.add_y_off) * (1 << p.add_left_shift), p.add_y_mult, p.add_y_shift);
-          const int32_t sr = requant_lt1((qv + p.add_r_off) * (1 << p.add_left_shift), p.add_r_mult, p.add_r_shift);
-          v[r] = clamp_i32(requant_lt1(sy + sr, p.add_o_mult, p.add_o_shift) + p.add_o_off, p.add_act_min,
-                           p.add_act_max);
-        }
-      }
-      if (tab) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = tab[(uint8_t)v[r]];
-      }
-      // bytes 0 of v0..v3 -> one dword (v_perm_b32: selector bytes 0-3 pick
-      // from the second operand, 4-7 from the first)
-      const uint32_t lo = __builtin_amdgcn_perm((uint32_t)v[1], (uint32_t)v[0], 0x0c0c0400u);
-      const uint32_t hi = __builtin_amdgcn_perm((uint32_t)v[3], (uint32_t)v[2], 0x04000c0cu);
-      *(uint32_t*)(out + o) = lo | hi;
+      *(uint32_t*)(out + o) = finish4(A, v, res, o, res_signed, tab);
     }
   }
 }
@@ -241,7 +239,8 @@ __global__ __launch_bounds__(256) void conv_xs_kernel(bh_conv_params p, int M, i
 
   uint8_t* out = (uint8_t*)p.output;
   const uint8_t* res = (const uint8_t*)p.residual;
-  const bool res_signed = p.in_xor == 0;
+  const bool res_signed = p.in_xor == 0;  // the residual shares the activation type
+  const ResidualAdd A = residual_of(p);
   const uint8_t* tab = (const uint8_t*)p.out_table;
   // operands of one channel tile: filter fragments + folded bias,
   // multipliers, shifts of this lane's 4 channels (zero past N)
@@ -302,26 +301,7 @@ __global__ __launch_bounds__(256) void conv_xs_kernel(bh_conv_params p, int M, i
         if (wzp) a -= p.w_zp * rs[b];
         v[r] = requant_out<FAST>(a, q[r], p.out_zp, p.act_min, p.act_max);
       }
-      if (res) {
-        const uint32_t rq = *(const uint32_t*)(res + o);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const uint32_t qb = (rq >> (8 * r)) & 0xffu;
-          const int32_t qv = res_signed ? (int32_t)(int8_t)qb : (int32_t)qb;
-          const int32_t sy =
-              requant_lt1((v[r] + p.add_y_off) * (1 << p.add_left_shift), p.add_y_mult, p.add_y_shift);
-          const int32_t sr = requant_lt1((qv + p.add_r_off) * (1 << p.add_left_shift), p.add_r_mult, p.add_r_shift);
-          v[r] = clamp_i32(requant_lt1(sy + sr, p.add_o_mult, p.add_o_shift) + p.add_o_off, p.add_act_min,
-                           p.add_act_max);
-        }
-      }
-      if (tab) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = tab[(uint8_t)v[r]];
-      }
-      const uint32_t lo = __builtin_amdgcn_perm((uint32_t)v[1], (uint32_t)v[0], 0x0c0c0400u);
-      const uint32_t hi = __builtin_amdgcn_perm((uint32_t)v[3], (uint32_t)v[2], 0x04000c0cu);
-      *(uint32_t*)(out + o) = lo | hi;
+      *(uint32_t*)(out + o) = finish4(A, v, res, o, res_signed, tab);
     }
   }
 }

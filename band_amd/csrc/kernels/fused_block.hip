@@ -22,6 +22,7 @@
 // to the waves, so no wave runs a long serial chain (at batch 1 a block has
 // few workgroups; latency, not FLOPs, is the cost).
 #include "common.hpp"
+#include "residual_add.hpp"
 
 namespace bh {
 
@@ -399,11 +400,7 @@ __global__ __launch_bounds__(NW * 64) void irb_kernel(bh_irb_params p, int kspli
         int32_t v = accl[pi * G.np3 + col] + pjt[col];
         v = requant_clamp(v, pjt[p.out_c + col], pjt[2 * p.out_c + col], p.p_zp, p.p_act_min, p.p_act_max,
                           p.requant_fast & 4);
-        if (p.has_residual) {
-          const int32_t sp = requant_lt1((v + p.add_p_off) * (1 << p.add_left_shift), p.add_p_mult, p.add_p_shift);
-          const int32_t sx = requant_lt1((q[j] + p.add_x_off) * (1 << p.add_left_shift), p.add_x_mult, p.add_x_shift);
-          v = clamp_i32(requant_lt1(sp + sx, p.add_o_mult, p.add_o_shift) + p.add_o_off, p.add_act_min, p.add_act_max);
-        }
+        if (p.has_residual) v = residual_add(residual_of(p), v, q[j]);
         out[o[j]] = (int8_t)v;
       }
     }

@@ -37,112 +37,9 @@
 
 #include "chain_dw.hpp"
 #include "common.hpp"
+#include "residual_add.hpp"
 
 namespace bh {
-
-__device__ __forceinline__ uint32_t pack4(const int32_t v[4]) {
-  // bytes 0 of v0..v3 -> one dword (v_perm_b32 selectors as in conv_xs_kernel)
-  const uint32_t lo = __builtin_amdgcn_perm((uint32_t)v[1], (uint32_t)v[0], 0x0c0c0400u);
-  const uint32_t hi = __builtin_amdgcn_perm((uint32_t)v[3], (uint32_t)v[2], 0x04000c0cu);
-  return lo | hi;
-}
-
-// One 16-channel tile t of the 1x1 layer `c` for this lane's pixel row:
-// `xrow` = the row's K bytes in LDS at this lane's 16-byte K offset.  The
-// accumulator starts at the folded bias of the lane's 4 channels.  Four
-// K-steps' weight fragments (global, L1/L2-resident) and pixel fragments
-// (LDS) are issued before their MFMAs.
-__device__ __forceinline__ v4i gemm_tile(const bh_conv_params& c, const unsigned char* xrow, int t, int KS, int r16,
-                                         int g) {
-  const int8_t* wrow = c.weights + (long)(t * 16 + r16) * c.k_pad + g * 16;
-  const int nb = t * 16 + 4 * g;
-  const int nl = nb < c.out_c ? nb : 0;
-  v4i acc = *(const v4i*)(c.bias_eff + nl);
-  int k = 0;
-  for (; k + 8 <= KS; k += 8) {
-    v4i w[8], x[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      w[u] = *(const v4i*)(wrow + (k + u) * 64);
-      x[u] = *(const v4i*)(xrow + (k + u) * 64);
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(w[u], x[u], acc, 0, 0, 0);
-  }
-  for (; k + 4 <= KS; k += 4) {
-    v4i w[4], x[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      w[u] = *(const v4i*)(wrow + (k + u) * 64);
-      x[u] = *(const v4i*)(xrow + (k + u) * 64);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(w[u], x[u], acc, 0, 0, 0);
-  }
-  for (; k < KS; ++k) {
-    const v4i w = *(const v4i*)(wrow + k * 64);
-    const v4i x = *(const v4i*)(xrow + k * 64);
-    acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(w, x, acc, 0, 0, 0);
-  }
-  return acc;
-}
-
-template <bool FAST>
-__device__ __forceinline__ void requant4(const bh_conv_params& c, int nb, v4i acc, int32_t v[4]) {
-  const v4i vm = *(const v4i*)(c.mult + nb);
-  const v4i vs = *(const v4i*)(c.shift + nb);
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-    v[r] = requant_out<FAST>(acc[r], chan_q(vm[r], vs[r], c.out_zp), c.out_zp, c.act_min, c.act_max);
-}
-
-// x-stationary 1x1 GEMM for K <= 64 * KMAX: this lane's KS pixel fragments
-// are read from LDS once; the wave then walks its channel tiles t0, t0 +
-// tstep, ... two at a time, with both tiles' weight fragments and epilogue
-// operands (folded bias, multipliers, shifts) issued before their MFMAs, so
-// each pair costs one memory round trip.  epi(t, nb, acc, mult4, shift4)
-// finishes a tile (nb = the lane's first channel; may be >= out_c).
-template <int KMAX, typename Epi>
-__device__ __forceinline__ void gemm_xs(const bh_conv_params& c, const unsigned char* xrow, int KS, int t0, int tstep,
-                                        int r16, int g, Epi&& epi) {
-  v4i x[KMAX];
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k) x[k] = k < KS ? *(const v4i*)(xrow + k * 64) : (v4i){0, 0, 0, 0};
-  const int T = (c.out_c + 15) >> 4;
-  for (int t = t0; t < T; t += 2 * tstep) {
-    const int tb = t + tstep < T ? t + tstep : t;
-    const int8_t* ra = c.weights + (long)(t * 16 + r16) * c.k_pad + g * 16;
-    const int8_t* rb = c.weights + (long)(tb * 16 + r16) * c.k_pad + g * 16;
-    v4i wa[KMAX], wb[KMAX];
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-      if (k < KS) {
-        wa[k] = *(const v4i*)(ra + k * 64);
-        wb[k] = *(const v4i*)(rb + k * 64);
-      }
-    const int na = t * 16 + 4 * g, nb = tb * 16 + 4 * g;
-    const int la = na < c.out_c ? na : 0, lb = nb < c.out_c ? nb : 0;
-    v4i acca = *(const v4i*)(c.bias_eff + la);
-    v4i accb = *(const v4i*)(c.bias_eff + lb);
-    const v4i ma = *(const v4i*)(c.mult + la), sa = *(const v4i*)(c.shift + la);
-    const v4i mb = *(const v4i*)(c.mult + lb), sb = *(const v4i*)(c.shift + lb);
-#pragma unroll
-    for (int k = 0; k < KMAX; ++k)
-      if (k < KS) {
-        acca = __builtin_amdgcn_mfma_i32_16x16x64_i8(wa[k], x[k], acca, 0, 0, 0);
-        accb = __builtin_amdgcn_mfma_i32_16x16x64_i8(wb[k], x[k], accb, 0, 0, 0);
-      }
-    epi(t, na, acca, ma, sa);
-    if (tb != t) epi(tb, nb, accb, mb, sb);
-  }
-}
-
-template <bool FAST>
-__device__ __forceinline__ void requant4m(const bh_conv_params& c, v4i acc, v4i vm, v4i vs, int32_t v[4]) {
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-    v[r] = requant_out<FAST>(acc[r], chan_q(vm[r], vs[r], c.out_zp), c.out_zp, c.act_min, c.act_max);
-}
 
 constexpr int kXsMax = 5;  // x-stationary GEMMs up to K = 320
 
@@ -367,14 +264,7 @@ __global__ __launch_bounds__(NW * 64) void chain_kernel(bh_chain_params cp, int 
   // (MultiplyByQuantizedMultiplierSmallerThanOneExp of (q + offset) << 20),
   // so both rescalings are 256-entry tables, built once per workgroup
   int* add_tab = (int*)(smem + off_add);  // [0, 256): first conv's output, [256, 512): residual
-  if (cp.pw1.residual) {
-    const bh_conv_params& a = cp.pw1;
-    for (int i = threadIdx.x; i < 512; i += NW * 64) {
-      const int q = (i & 255) - 128;
-      add_tab[i] = i < 256 ? requant_lt1((q + a.add_y_off) * (1 << a.add_left_shift), a.add_y_mult, a.add_y_shift)
-                           : requant_lt1((q + a.add_r_off) * (1 << a.add_left_shift), a.add_r_mult, a.add_r_shift);
-    }
-  }
+  if (cp.pw1.residual) residual_tab_build(add_tab, cp.pw1, threadIdx.x, NW * 64);
   const int prow = pb * 16 + r16;     // this lane's operand row
   const int orow = pb * 16 + 4 * g;   // first of this lane's 4 result rows
   // diagnostics (tools/tile_probe.py --raster): shader-clock stamps at the
@@ -422,6 +312,7 @@ __global__ __launch_bounds__(NW * 64) void chain_kernel(bh_chain_params cp, int 
     const int KS1 = a.k_pad >> 6;
     const unsigned char* xrow = dl + prow * S1 + g * 16;
     const uint8_t* res = (const uint8_t*)a.residual;
+    const ResidualAdd A = residual_of(a);
     const bool out1 = a.output != nullptr && (!SPLIT || blockIdx.y == 0);  // split: slice 0 stores it
     auto epi = [&](int t, int n, v4i acc, int mu, int sh) {
       if (n >= N1) return;
@@ -437,12 +328,7 @@ __global__ __launch_bounds__(NW * 64) void chain_kernel(bh_chain_params cp, int 
           rq[r] = mr < P ? (int32_t)(int8_t)res[(long)mr * N1 + n] : 0;
         }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int32_t sy = add_tab[v[r] + 128];
-          const int32_t sr = add_tab[256 + rq[r] + 128];
-          v[r] = clamp_i32(requant_lt1(sy + sr, a.add_o_mult, a.add_o_shift) + a.add_o_off, a.add_act_min,
-                           a.add_act_max);
-        }
+        for (int r = 0; r < 4; ++r) v[r] = residual_add_tab(add_tab, A, v[r], rq[r]);
       }
       if (out1) stage4(o1, N1, orow, n, v);
       if (cp.has_pw2) stage4(pl, S2, orow, n, v);
@@ -462,9 +348,7 @@ __global__ __launch_bounds__(NW * 64) void chain_kernel(bh_chain_params cp, int 
             for (int r = 0; r < 4; ++r) {
               const int mr = m0 + rb + r;
               const int32_t rq = mr < P ? (int32_t)(int8_t)res[(long)mr * N1 + n] : 0;
-              v[r] = clamp_i32(requant_lt1(add_tab[v[r] + 128] + add_tab[256 + rq + 128], a.add_o_mult, a.add_o_shift) +
-                                   a.add_o_off,
-                               a.add_act_min, a.add_act_max);
+              v[r] = residual_add_tab(add_tab, A, v[r], rq);
             }
           }
           if (out1) stage4(o1, N1, rb, n, v);
@@ -759,7 +643,7 @@ __global__ __launch_bounds__(256) void chain_persist_kernel(bh_chain_params cp, 
 #pragma unroll
           for (int r = 0; r < 4; ++r)
             v[r] = requant_out<FAST>(acc[r], chan_q(mm4[r], ss4[r], d.out_zp), d.out_zp, d.act_min, d.act_max);
-          *(uint32_t*)(dl + (pb * 16 + r16) * L.S1 + co) = pack4(v);
+          *(uint32_t*)(dl + (pb * 16 + r16) * L.S1 + co) = pack4_bytes(v);
         }
       }
     }
@@ -803,6 +687,9 @@ __global__ __launch_bounds__(256) void chain_persist_kernel(bh_chain_params cp, 
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = requant_out<FAST>(acc[pb][r], q[r], a.out_zp, a.act_min, a.act_max);
           if (res) {
+            // residual_add() spelled out: through the helper this kernel's
+            // phase A compiles to 11 more branches per pixel block and the
+            // form runs 1.5-4 % slower (profiles/r19a_epilogue_bench.txt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int32_t qv = sbyte(rq[pb], r);
@@ -814,7 +701,7 @@ __global__ __launch_bounds__(256) void chain_persist_kernel(bh_chain_params cp, 
                                a.add_act_max);
             }
           }
-          const uint32_t pk = pack4(v);
+          const uint32_t pk = pack4_bytes(v);
           const int row = pb * 16 + r16;
           if (out1) *(uint32_t*)(o1 + row * N1 + nb) = pk;
           if (cp.has_pw2) *(uint32_t*)(pl + row * L.S2 + nb) = pk;
@@ -855,7 +742,7 @@ __global__ __launch_bounds__(256) void chain_persist_kernel(bh_chain_params cp, 
           int32_t v[4];
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = requant_out<FAST>(acc[pb][r], q[r], b.out_zp, b.act_min, b.act_max);
-          *(uint32_t*)(dl + (pb * 16 + r16) * N2 + nb) = pack4(v);
+          *(uint32_t*)(dl + (pb * 16 + r16) * N2 + nb) = pack4_bytes(v);
         }
       }
       __syncthreads();

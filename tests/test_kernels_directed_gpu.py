@@ -429,20 +429,25 @@ RESIDUAL_SETS = [  # (y scale, residual scale, out scale), (y_zp is the conv's, 
 
 def run_residual(lib, c, name, what=""):
     """conv -> ADD -> table against the oracle's three ops, every (y, r) pair:
-    residual[pixel, c] = c - 128, with and without a permutation out_table,
-    both requantisation paths"""
+    residual[pixel, c] = the c-th value of the layer's type, with and without
+    a permutation out_table, both requantisation paths.  A uint8 layer takes
+    the sets' zero points moved by 128, its residual read unsigned."""
     from band_amd import _abi
     from band_amd.device import DeviceBuffer
+    dtype = np.dtype(c.dtype)
+    lo = dh.type_range(dtype)[0]
     y = c.oracle()
+    assert y.dtype == dtype
     assert all(len(np.unique(y[0, :, :, ch])) == 256 for ch in (0, 1, 255)), "y does not sweep"
-    r = np.ascontiguousarray(np.broadcast_to((np.arange(256) - 128).astype(I8), y.shape))
+    r = np.ascontiguousarray(np.broadcast_to((np.arange(256) + lo).astype(dtype), y.shape))
     table = np.random.default_rng(5).permutation(256).astype(U8)
-    for (ys, rs, os_), (r_zp, o_zp), act in RESIDUAL_SETS:
+    for (ys, rs, os_), zps, act in RESIDUAL_SETS:
+        r_zp, o_zp = (z + lo + 128 for z in zps)
         prm = orc.add_params(ys, rs, os_)
-        amin, amax = orc.act_range(act, os_, o_zp, True)
+        amin, amax = orc.act_range(act, os_, o_zp, dtype == I8)
         z = orc.add(y, r, a_zp=c.out_zp, b_zp=r_zp, out_zp=o_zp, params=prm, amin=amin, amax=amax)
         for with_table in (False, True):
-            ref = table[z.view(U8)].view(I8) if with_table else z
+            ref = table[z.view(U8)].view(dtype) if with_table else z
             for fast in (None, False):
                 c.requant_fast = fast
                 keep = []
@@ -464,7 +469,7 @@ def run_residual(lib, c, name, what=""):
                 assert got_name == name, "%s: routed to %s, wanted %s" % (what, got_name, name)
                 assert p.requant_fast == (1 if fast is None else 0)
                 _abi.check(lib.bh_conv2d_i8(ctypes.byref(p), None), "bh_conv2d_i8")
-                got = c._dy.download(I8, y.shape)
+                got = c._dy.download(dtype, y.shape)
                 del keep
                 np.testing.assert_array_equal(got, ref, err_msg="%s %s scales %r table %s fast %s" % (
                     what, name, (ys, rs, os_), with_table, fast))
@@ -475,6 +480,17 @@ def run_residual(lib, c, name, what=""):
     (0, 1, 3, 4, "conv_direct_kernel")])
 def test_conv_residual_every_pair(gpu_lib, hint, sweeps, k, ic, name):
     c = dh.conv_layer(passthrough_epi(k=k * k * ic), ic=ic, k=k, sweeps=sweeps, kernel_hint=hint)
+    run_residual(gpu_lib, c, name)
+
+
+@pytest.mark.parametrize("hint,sweeps,k,ic,name", [
+    (1, 1, 1, 16, "conv_mfma_kernel"), (0, 9, 1, 16, "conv_xs_kernel"), (7, 1, 1, 16, "conv_rows_kernel"),
+    (0, 1, 3, 4, "conv_direct_kernel")])
+def test_conv_residual_every_pair_uint8(gpu_lib, hint, sweeps, k, ic, name):
+    """the unsigned branch of the folded ADD (in_xor != 0: conv_store4, conv_xs,
+    conv_rows, conv_direct): y and the residual as uint8, same layer.
+    conv_gemm_big_kernel has no such run: its route admits int8 activations only."""
+    c = dh.conv_layer(passthrough_epi(dtype=U8, k=k * k * ic), ic=ic, k=k, sweeps=sweeps, kernel_hint=hint)
     run_residual(gpu_lib, c, name)
 
 
