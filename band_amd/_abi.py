@@ -174,7 +174,16 @@ REINDEX_MAX_RANK = 6
 class ReindexParams(ctypes.Structure):
     _fields_ = [("elem_bytes", c_int), ("rank", c_int), ("out_dims", c_int * REINDEX_MAX_RANK),
                 ("in_stride", ctypes.c_int64 * REINDEX_MAX_RANK), ("in_offset", ctypes.c_int64),
-                ("input", c_void_p), ("output", c_void_p)]
+                ("input", c_void_p), ("output", c_void_p),
+                # GATHER as a map (null indices: a plain map)
+                ("indices", c_void_p), ("index_bytes", c_int), ("index_range", ctypes.c_int64)]
+
+
+class GatherParams(ctypes.Structure):
+    """bh_gather_params: params [outer][axis_size][inner], n_idx int32 / int64 indices on the device"""
+    _fields_ = [("elem_bytes", c_int), ("index_bytes", c_int)] + [
+        (n, ctypes.c_int64) for n in ("outer", "axis_size", "n_idx", "inner")] + [
+        (n, c_void_p) for n in ("params", "indices", "output")]
 
 
 BMM_AUTO, BMM_BYTES, BMM_NT1, BMM_NT4 = 0, 1, 2, 4
@@ -354,6 +363,9 @@ KERNEL_SYMBOLS = {
     "bh_reindex_as": (c_int, [ctypes.POINTER(ReindexParams), c_int, c_void_p]),
     "bh_reindex_kernel": (ctypes.c_char_p, [ctypes.POINTER(ReindexParams)]),
     "bh_reindex_canonical": (c_int, [ctypes.POINTER(ReindexParams), ctypes.POINTER(ReindexParams)]),
+    "bh_gather": (c_int, [ctypes.POINTER(GatherParams), c_void_p]),
+    "bh_gather_kernel": (ctypes.c_char_p, [ctypes.POINTER(GatherParams)]),
+    "bh_gather_check": (c_int, [ctypes.POINTER(GatherParams)]),
     "bh_batch_matmul_i8": (c_int, [ctypes.POINTER(BatchMatMulParams), c_void_p]),
     "bh_batch_matmul_i8_kernel": (ctypes.c_char_p, [ctypes.POINTER(BatchMatMulParams)]),
     "bh_batch_matmul_f32": (c_int, [ctypes.POINTER(BatchMatMulParams), c_void_p]),

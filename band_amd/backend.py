@@ -81,6 +81,7 @@ _abi.BACKEND_SYMBOLS.update({
                                             ctypes.POINTER(ctypes.c_double)]),
     "bhx_time_subgraph": (c_int, _KEY + [c_int, ctypes.POINTER(ctypes.c_double)]),
     "bhx_cpu_reindex": (c_int, [ctypes.POINTER(_abi.ReindexParams)]),
+    "bhx_cpu_gather": (c_int, [ctypes.POINTER(_abi.GatherParams)]),
     "bhx_launch_kernels": (c_int, _KEY + [ctypes.POINTER(ctypes.c_char_p), c_int, ctypes.POINTER(c_int)]),
     "bhx_job_batch_launch_kernels": (c_int, _KEY + [c_int, ctypes.POINTER(ctypes.c_char_p), c_int,
                                                     ctypes.POINTER(c_int)]),

@@ -454,6 +454,14 @@ int bhx_cpu_reindex(const void* reindex_params) {
   return 0;
 }
 
+int bhx_cpu_gather(const void* gather_params) {
+  if (!gather_params) return Fail("null argument");
+  const auto* p = static_cast<const bh_gather_params*>(gather_params);
+  if (bh_gather_check(p) != 0 || !band::hip::CpuGather(*p))
+    return Fail((std::string("CpuGather: ") + bh_last_error()).c_str());
+  return 0;
+}
+
 int bhx_launch_kernels(bhx_executor* e, int mid, int wid, uint64_t mask, const char** out, int cap, int* n) {
   auto* h = e ? dynamic_cast<band::hip::HipModelExecutor*>(e->exec.get()) : nullptr;
   if (!h) return Fail("not a HIP executor");

@@ -3,6 +3,7 @@
 #include "backend/hip/affinity.h"
 
 #include "backend/hip/quant.h"
+#include "band_hip_gather_shared.h"
 
 #include <pthread.h>
 
@@ -870,6 +871,10 @@ void CpuArgMinMax(const bh_argminmax_params& p, CpuPool& pool) {
 }
 
 bool CpuReindex(const bh_reindex_params& p) {
+  if (p.indices) {  // GATHER as a map
+    bh_gather_params g;
+    return !bh_reindex_as_gather(&p, &g) && CpuGather(g);
+  }
   bh_reindex_params c;
   if (!p.input || !p.output || bh_reindex_canonical(&p, &c) != 0) return false;
   const int64_t eb = c.elem_bytes;
@@ -895,6 +900,21 @@ bool CpuReindex(const bh_reindex_params& p) {
       if (++idx[d] < c.out_dims[d]) break;
       off -= c.in_stride[d] * eb * c.out_dims[d];
       idx[d] = 0;
+    }
+  }
+  return true;
+}
+
+bool CpuGather(const bh_gather_params& p) {
+  if (bh_gather_refusal(&p)) return false;
+  const size_t row = static_cast<size_t>(p.inner) * p.elem_bytes;
+  const char* in = static_cast<const char*>(p.params);
+  char* out = static_cast<char*>(p.output);
+  for (int64_t o = 0; o < p.outer; ++o) {
+    for (int64_t j = 0; j < p.n_idx; ++j, out += row) {
+      const int64_t idx = bh_gather_row(p.indices, p.index_bytes, j, static_cast<int32_t>(p.axis_size));
+      if (idx >= 0) std::memcpy(out, in + static_cast<size_t>(o * p.axis_size + idx) * row, row);
+      else std::memset(out, 0, row);
     }
   }
   return true;

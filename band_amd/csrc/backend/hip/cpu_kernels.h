@@ -112,8 +112,14 @@ void CpuArgMinMax(const bh_argminmax_params& p, CpuPool& pool);
 // SPACE_TO_DEPTH, DEPTH_TO_SPACE): bh_reindex's host twin over the same
 // canonical map (bh_reindex_canonical) - rows are copied whole where the
 // innermost stride is 1, element by element otherwise.  False for a map the
-// launcher would refuse.
+// launcher would refuse.  A map with indices (GATHER) goes to CpuGather.
 bool CpuReindex(const bh_reindex_params& p);
+
+// GATHER: bh_gather's host twin - one memcpy per output row, the index range-
+// checked by the function the kernel uses (bh_gather_row); a row whose index
+// lies outside [0, axis_size) is zero bytes.  False for what the launcher
+// would refuse (bh_gather_refusal, band_hip_gather_shared.h).
+bool CpuGather(const bh_gather_params& p);
 
 // BATCH_MATMUL (bh_batch_matmul_params, validated by the caller): the host
 // twins of bh_batch_matmul_i8 - sum_k (a - z_l)(b - z_r) unfolded, TFLite's

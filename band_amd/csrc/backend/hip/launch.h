@@ -101,7 +101,7 @@ class Launch {
     kDetectionGpu,   // TFLite_Detection_PostProcess on the device (BAND_HIP_GPU_DETECTION=1)
     kArgMinMax,      // ARG_MAX / ARG_MIN
     kResizeArgMinMax, // RESIZE_BILINEAR int8 -> ARG_MAX / ARG_MIN over channels, one launch (FuseGlue; kGPU)
-    kReindex,         // one output of TRANSPOSE / STRIDED_SLICE / SLICE / SPLIT / SPLIT_V / SPACE_TO_DEPTH / DEPTH_TO_SPACE
+    kReindex,         // one output of TRANSPOSE / STRIDED_SLICE / SLICE / SPLIT / SPLIT_V / SPACE_TO_DEPTH / DEPTH_TO_SPACE / UNPACK / TILE, or a GATHER (a map with indices)
     kConvGrouped,     // grouped CONV_2D: the dense block with the total channel counts + groups (never chained / grouped / blocked)
     kBatchMatMul,     // BATCH_MATMUL int8 (BatchMatMulArgs; never chained / grouped / blocked, no epilogue folds)
     kBatchMatMulF32,  // BATCH_MATMUL float32

@@ -333,6 +333,21 @@ absl::Status HipModelExecutor::LowerGlue(const HipModel& model, int oi, void* in
       L->kernel = "concat_kernel";
       return absl::OkStatus();
     }
+    case kTflPack: {
+      // np.stack is a concatenation of the inputs' remainders past the axis
+      bh_concat_params& p = L->Set<Launch::kConcat>();
+      const char* why = "";
+      if (!PackArgs(d, op, &p, &why)) return Refused(op, why);
+      p.output = out_ptr;
+      for (int k = 0; k < p.n_inputs; ++k) {
+        void* xp = nullptr;
+        RETURN_STATUS_IF(DevicePtr(model, op.inputs[k], sg, &xp));
+        p.input[k] = xp;
+      }
+      L->alg_bytes = 2.0 * out_bytes;
+      L->kernel = "concat_kernel";
+      return absl::OkStatus();
+    }
     case kTflPad:
     case kTflPadV2:
     case kTflMirrorPad: {
@@ -742,8 +757,9 @@ absl::Status HipModelExecutor::LowerDetectionGpu(const HipModel& model, int oi, 
 }
 
 // TRANSPOSE / STRIDED_SLICE / SLICE / SPLIT / SPLIT_V / SPACE_TO_DEPTH /
-// DEPTH_TO_SPACE: each output is one map (ReindexArgs) and one launch - a
-// SPLIT with n outputs is n launches, each writing its own dense tensor.
+// DEPTH_TO_SPACE / UNPACK / TILE: each output is one map (ReindexArgs) and one
+// launch - a SPLIT or an UNPACK with n outputs is n launches, each writing its
+// own dense tensor.
 absl::Status HipModelExecutor::LowerReindex(const HipModel& model, int oi, PreparedSubgraph* sg) {
   const TflModel& d = model.desc();
   const TflOperator& op = d.ops[oi];
@@ -777,6 +793,66 @@ absl::Status HipModelExecutor::LowerReindex(const HipModel& model, int oi, Prepa
     }
     sg->launches.push_back(L);
   }
+  return absl::OkStatus();
+}
+
+// GATHER: one kReindex launch whose map carries the index tensor - [outer]
+// [n_idx][inner] over GatherArgs' counts - so bh_reindex / CpuReindex hand it
+// to bh_gather / CpuGather.  A constant params (an embedding table) and a
+// constant indices tensor are uploaded once per (model, GPU), as a filter is;
+// a runtime indices tensor is read from its arena slot (a model input lands
+// there like any other).  With outer == 1 and the constant indices 0 ..
+// axis_size - 1 the output is params byte for byte: a copy, as LowerReindex
+// makes of the identity.  The launch joins no fusion pattern (the head
+// TRANSPOSE matchers ask for a TRANSPOSE op).
+absl::Status HipModelExecutor::LowerGather(const HipModel& model, int oi, PreparedSubgraph* sg) {
+  const TflModel& d = model.desc();
+  const TflOperator& op = d.ops[oi];
+  Launch L;
+  L.op_index = oi;
+  L.out_tensor = op.outputs[0];
+  bh_gather_params p;
+  const char* why = "";
+  if (!GatherArgs(d, op, &p, &why)) return Refused(op, why);
+  void* params = nullptr;
+  void* indices = nullptr;
+  void* out_ptr = nullptr;
+  RETURN_STATUS_IF(DevicePtr(model, op.inputs[0], sg, &params));
+  RETURN_STATUS_IF(DevicePtr(model, op.inputs[1], sg, &indices));
+  RETURN_STATUS_IF(DevicePtr(model, op.outputs[0], sg, &out_ptr));
+  p.params = params;
+  p.indices = indices;
+  p.output = out_ptr;
+  if (bh_gather_check(&p) != 0) return absl::InternalError(std::string("GATHER: ") + bh_last_error());
+  const size_t bytes = meta_[op.outputs[0]]->bytes;
+  std::vector<int64_t> idx;
+  bool identity = p.outer == 1 && p.n_idx == p.axis_size && ConstInts(d.tensors[op.inputs[1]], &idx);
+  for (size_t i = 0; identity && i < idx.size(); ++i) identity = idx[i] == static_cast<int64_t>(i);
+  if (identity) {
+    if (params == out_ptr) return absl::OkStatus();
+    L.Set<Launch::kCopy>({out_ptr, params, bytes});
+    L.kernel = "copy";
+    L.alg_bytes = 2.0 * bytes;
+  } else {
+    // (bh_gather_check: every count fits an int)
+    bh_reindex_params& r = L.Set<Launch::kReindex>();
+    r.elem_bytes = p.elem_bytes;
+    r.rank = 3;
+    r.out_dims[0] = static_cast<int>(p.outer);
+    r.out_dims[1] = static_cast<int>(p.n_idx);
+    r.out_dims[2] = static_cast<int>(p.inner);
+    r.in_stride[0] = p.axis_size * p.inner;
+    r.in_stride[1] = p.inner;
+    r.in_stride[2] = 1;
+    r.input = params;
+    r.output = out_ptr;
+    r.indices = indices;
+    r.index_bytes = p.index_bytes;
+    r.index_range = p.axis_size;
+    L.kernel = device_flag_ == DeviceFlag::kCPU ? "gather_host" : bh_reindex_kernel(&r);
+    L.alg_bytes = 2.0 * bytes + static_cast<double>(p.n_idx * p.index_bytes);
+  }
+  sg->launches.push_back(L);
   return absl::OkStatus();
 }
 
@@ -1239,6 +1315,7 @@ absl::Status HipModelExecutor::Lower(const HipModel& model, int oi, PreparedSubg
     return absl::OkStatus();
   }
   if (IsReindexOp(op.builtin)) return LowerReindex(model, oi, sg);
+  if (op.builtin == kTflGather) return LowerGather(model, oi, sg);
   void* in_ptr = nullptr;
   void* out_ptr = nullptr;
   RETURN_STATUS_IF(DevicePtr(model, op.inputs[0], sg, &in_ptr));

@@ -2,6 +2,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <limits>
 #include <set>
 
 namespace band {
@@ -547,7 +548,7 @@ bool ReindexArgs(const TflModel& m, const TflOperator& op, int oi, bh_reindex_pa
   const int b = op.builtin;
   const int xin = b == kTflSplit ? 1 : 0;
   const size_t need = b == kTflStridedSlice ? 4 : (b == kTflSlice || b == kTflSplitV) ? 3
-                      : (b == kTflTranspose || b == kTflSplit)                       ? 2
+                      : (b == kTflTranspose || b == kTflSplit || b == kTflTile)      ? 2
                                                                                      : 1;
   if (!IsReindexOp(b) || op.inputs.size() < need || oi < 0 || oi >= static_cast<int>(op.outputs.size()) ||
       op.outputs[oi] < 0)
@@ -676,6 +677,43 @@ bool ReindexArgs(const TflModel& m, const TflOperator& op, int oi, bh_reindex_pa
     off = first * istr[axis];
     lead = axis != 0;
     expect = ext;
+  } else if (b == kTflUnpack) {
+    if (r < 1) return no("UNPACK of a scalar");
+    int64_t axis = op.options.valid() ? op.options.Int(1, 0) : 0;
+    if (axis < 0) axis += r;
+    if (axis < 0 || axis >= r) return no("UNPACK axis out of range");
+    const int64_t parts = static_cast<int64_t>(op.outputs.size());
+    if (in.shape[axis] != parts || (op.options.valid() && op.options.Int(0, 0) != 0 && op.options.Int(0, 0) != parts))
+      return no("UNPACK num differs from the axis extent or the number of outputs");
+    for (int d = 0; d < r; ++d) {
+      if (d == axis) continue;
+      ext.push_back(in.shape[d]);
+      str.push_back(istr[d]);
+    }
+    off = oi * istr[axis];
+    lead = axis != 0;
+    expect = ext;
+  } else if (b == kTflTile) {
+    std::vector<int64_t> mult;
+    if (!ints(1, &mult)) return no("TILE multiples must be a constant int32 / int64 tensor");
+    if (static_cast<int>(mult.size()) != r) return no("TILE multiples length differs from the rank");
+    for (int d = 0; d < r; ++d) {
+      const int64_t n = in.shape[d], k = mult[d];
+      if (k < 1 || k * n > std::numeric_limits<int>::max()) return no("TILE multiples must be positive");
+      expect.push_back(n * k);
+      // [k][n] with strides [0][s]; past axis 0 a multiple of 1 and a unit dim leave no map dim
+      if (k > 1) {
+        ext.push_back(k);
+        str.push_back(0);
+      }
+      if (n > 1 || (d == 0 && k == 1)) {
+        ext.push_back(n);
+        str.push_back(istr[d]);
+      }
+    }
+    if (ext.size() > BH_REINDEX_MAX_RANK)
+      return no("TILE map exceeds rank 6 after unit dims and multiples of 1 are dropped");
+    lead = r > 0 && mult[0] == 1;
   } else {  // SPACE_TO_DEPTH / DEPTH_TO_SPACE
     const bool d2s = b == kTflDepthToSpace;
     if (r != 4 || out.shape.size() != 4)
@@ -712,6 +750,117 @@ bool ReindexArgs(const TflModel& m, const TflOperator& op, int oi, bh_reindex_pa
   }
   map->in_offset = off;
   if (whole_batch) *whole_batch = whole0;
+  return true;
+}
+
+bool GatherArgs(const TflModel& m, const TflOperator& op, bh_gather_params* p, const char** why, bool* batch_ok) {
+  auto no = [&](const char* w) {
+    if (why) *why = w;
+    return false;
+  };
+  if (op.builtin != kTflGather || op.inputs.size() < 2 || op.inputs[0] < 0 || op.inputs[1] < 0 || op.outputs.empty() ||
+      op.outputs[0] < 0)
+    return no("GATHER needs params, indices and an output");
+  const TflTensor& in = m.tensors[op.inputs[0]];
+  const TflTensor& ix = m.tensors[op.inputs[1]];
+  const TflTensor& out = m.tensors[op.outputs[0]];
+  if (in.type != DataType::kInt8 && in.type != DataType::kUInt8 && in.type != DataType::kFloat32 &&
+      in.type != DataType::kInt32)
+    return no("GATHER params must be int8, uint8, float32 or int32");
+  if (out.type != in.type) return no("GATHER output type differs from params'");
+  if (ix.type != DataType::kInt32 && ix.type != DataType::kInt64) return no("GATHER indices must be int32 or int64");
+  if (op.options.valid() && op.options.Int(1, 0) != 0) return no("GATHER batch_dims != 0");
+  if (IsQ8(in.type) && (in.scale != out.scale || in.zero_point != out.zero_point))
+    return no("GATHER output quantization differs from params' (GATHER never requantises)");
+  const int r = static_cast<int>(in.shape.size());
+  if (r < 1 || r > 6) return no("GATHER params rank must be 1-6");
+  int axis = op.options.valid() ? op.options.Int(0, 0) : 0;
+  if (axis < 0) axis += r;
+  if (axis < 0 || axis >= r) return no("GATHER axis out of range");
+  std::vector<int> expect(in.shape.begin(), in.shape.begin() + axis);
+  expect.insert(expect.end(), ix.shape.begin(), ix.shape.end());
+  expect.insert(expect.end(), in.shape.begin() + axis + 1, in.shape.end());
+  if (out.shape != expect)
+    return no("GATHER output shape differs from params.shape[:axis] + indices.shape + params.shape[axis + 1:]");
+  if (expect.size() > 6) return no("GATHER output rank > 6");
+  bh_gather_params g{};
+  g.elem_bytes = static_cast<int>(GetDataTypeBytes(in.type));
+  g.index_bytes = ix.type == DataType::kInt64 ? 8 : 4;
+  g.outer = g.inner = 1;
+  for (int d = 0; d < axis; ++d) g.outer *= in.shape[d];
+  for (int d = axis + 1; d < r; ++d) g.inner *= in.shape[d];
+  g.axis_size = in.shape[axis];
+  g.n_idx = static_cast<int64_t>(ix.num_elements());
+  if (g.outer < 1 || g.axis_size < 1 || g.n_idx < 1 || g.inner < 1) return no("GATHER of an empty tensor");
+  constexpr int64_t kMax = std::numeric_limits<int32_t>::max();
+  if (g.outer > kMax || g.n_idx > kMax || g.inner > kMax || g.outer * g.n_idx > kMax ||
+      g.outer * g.n_idx * g.inner > kMax / g.elem_bytes)
+    return no("GATHER output of more than 2^31 - 1 bytes");
+  if (ix.is_const()) {
+    std::vector<int64_t> v;
+    if (!ConstInts(ix, &v)) return no("GATHER constant indices are truncated");
+    for (int64_t i : v)
+      if (i < 0 || i >= g.axis_size) return no("GATHER constant index outside [0, axis_size)");
+  }
+  if (p) *p = g;
+  if (batch_ok) {
+    const char* w = nullptr;
+    if (in.is_const()) {
+      if (ix.is_const()) w = "constant params and constant indices: the output does not follow the batch axis";
+      else if (axis != 0) w = "constant params gathered along an axis other than 0";
+    } else {
+      if (!ix.is_const()) w = "runtime indices into an activation params";
+      else if (axis == 0) w = "an activation params gathered along the batch axis";
+    }
+    *batch_ok = w == nullptr;
+    if (w && why) *why = w;
+  }
+  return true;
+}
+
+bool PackArgs(const TflModel& m, const TflOperator& op, bh_concat_params* p, const char** why, int* axis_out) {
+  auto no = [&](const char* w) {
+    if (why) *why = w;
+    return false;
+  };
+  if (op.builtin != kTflPack || op.inputs.empty() || op.outputs.empty() || op.outputs[0] < 0)
+    return no("PACK needs inputs and an output");
+  if (op.inputs.size() > BH_CONCAT_MAX_INPUTS) return no("PACK of more than 16 inputs");
+  if (op.options.valid() && op.options.Int(0, 0) != 0 && op.options.Int(0, 0) != static_cast<int>(op.inputs.size()))
+    return no("PACK values_count differs from the number of inputs");
+  for (int t : op.inputs)
+    if (t < 0) return no("PACK needs inputs and an output");
+  const TflTensor& x0 = m.tensors[op.inputs[0]];
+  const TflTensor& out = m.tensors[op.outputs[0]];
+  if (out.type != DataType::kInt8 && out.type != DataType::kUInt8 && out.type != DataType::kFloat32 &&
+      out.type != DataType::kInt32)
+    return no("PACK element type must be int8, uint8, float32 or int32");
+  const int r = static_cast<int>(x0.shape.size());
+  int axis = op.options.valid() ? op.options.Int(1, 0) : 0;
+  if (axis < 0) axis += r + 1;
+  if (axis < 0 || axis > r) return no("PACK axis out of range");
+  for (int t : op.inputs) {
+    const TflTensor& x = m.tensors[t];
+    if (x.type != out.type || x.shape != x0.shape) return no("PACK inputs must share one shape and the output's type");
+    if (IsQ8(out.type) && (x.scale != out.scale || x.zero_point != out.zero_point))
+      return no("PACK inputs must share the output's quantization (pack.cc)");
+  }
+  std::vector<int> expect = x0.shape;
+  expect.insert(expect.begin() + axis, static_cast<int>(op.inputs.size()));
+  if (out.shape != expect) return no("PACK output shape is not the stacked shape");
+  long outer = 1, row = static_cast<long>(GetDataTypeBytes(out.type));
+  for (int d = 0; d < axis; ++d) outer *= x0.shape[d];
+  for (int d = axis; d < r; ++d) row *= x0.shape[d];
+  if (outer < 1 || row < 1) return no("PACK of empty tensors");
+  if (outer * row * static_cast<long>(op.inputs.size()) >= std::numeric_limits<int32_t>::max())
+    return no("PACK output of 2^31 - 1 or more bytes");
+  if (p) {
+    *p = bh_concat_params{};
+    p->n_inputs = static_cast<int>(op.inputs.size());
+    p->outer = outer;
+    for (int k = 0; k < p->n_inputs; ++k) p->row[k] = row;
+  }
+  if (axis_out) *axis_out = axis;
   return true;
 }
 

@@ -176,10 +176,11 @@ bool ArgMinMaxArgs(const TflModel& m, const TflOperator& op, long* outer, long* 
                    int* out_bytes, int* axis_out = nullptr, const char** why = nullptr);
 
 // The re-indexing ops: TRANSPOSE, STRIDED_SLICE, SLICE, SPLIT, SPLIT_V,
-// SPACE_TO_DEPTH, DEPTH_TO_SPACE
+// SPACE_TO_DEPTH, DEPTH_TO_SPACE, UNPACK, TILE
 inline bool IsReindexOp(int builtin) {
   return builtin == kTflTranspose || builtin == kTflStridedSlice || builtin == kTflSlice || builtin == kTflSplit ||
-         builtin == kTflSplitV || builtin == kTflSpaceToDepth || builtin == kTflDepthToSpace;
+         builtin == kTflSplitV || builtin == kTflSpaceToDepth || builtin == kTflDepthToSpace ||
+         builtin == kTflUnpack || builtin == kTflTile;
 }
 // the values of a constant int32 / int64 tensor
 bool ConstInts(const TflTensor& t, std::vector<int64_t>* v);
@@ -192,7 +193,11 @@ bool ConstInts(const TflTensor& t, std::vector<int64_t>* v);
 // clamping, negative strides; a begin_mask / end_mask bit makes the bound None,
 // a shrink_axis_mask bit makes the axis the index x[b]); np.split;
 // DEPTH_TO_SPACE out[n, h bs + by, w bs + bx, c] = in[n, h, w, (by bs + bx) C' + c]
-// and SPACE_TO_DEPTH its inverse.  Starts and strides come from the constants
+// and SPACE_TO_DEPTH its inverse; UNPACK output k is np.moveaxis(x, axis, 0)[k]
+// (the SPLIT map with the axis dropped); np.tile(x, multiples) with constant
+// multiples - input dim d with multiple m > 1 becomes the two map dims [m][d]
+// with input strides [0][s], unit dims and multiples of 1 past axis 0 leave no
+// map dim, and what is left must fit rank 6.  Starts and strides come from the constants
 // and the input's shape, extents from the OUTPUT tensor's shape, which must be
 // what the constants resolve to - except that an output may take the whole of
 // input axis 0 from element 0 at stride 1 whatever end / size say (a job-batch
@@ -201,6 +206,32 @@ bool ConstInts(const TflTensor& t, std::vector<int64_t>* v);
 // what was refused.
 bool ReindexArgs(const TflModel& m, const TflOperator& op, int oi, bh_reindex_params* map,
                  const char** why = nullptr, bool* whole_batch = nullptr);
+
+// GATHER (gather.cc, batch_dims 0): params viewed as [outer][axis_size][inner]
+// (GatherOptions.axis, negatives resolved), the indices flattened to n_idx -
+// p's counts, elem_bytes and index_bytes (pointers stay null); p may be null
+// (a pure check).  params is int8 / uint8 / float32 / int32 of rank 1-6, a
+// constant or an activation; indices int32 / int64, a constant or a runtime
+// tensor.  Refused with a reason: batch_dims != 0, 8-bit params whose output
+// quantisation differs (GATHER never requantises), an output shape other than
+// params.shape[:axis] + indices.shape + params.shape[axis + 1:] or of rank > 6,
+// more than 2^31 - 1 output bytes, a constant index outside [0, axis_size).
+// *batch_ok: a job-batch variant (axis 0 of every non-constant tensor scaled)
+// computes each job's own rows - constant params gathered along axis 0 by
+// runtime indices (the embedding), or an activation params gathered along an
+// axis >= 1 by constant indices; when the op is accepted and *batch_ok is
+// false, *why names what keeps it from batching.
+bool GatherArgs(const TflModel& m, const TflOperator& op, bh_gather_params* p, const char** why = nullptr,
+                bool* batch_ok = nullptr);
+
+// PACK (pack.cc; np.stack): the bh_concat launch of its inputs - outer the
+// product of the dims before the axis, row[k] the bytes of one input's
+// remainder (pointers stay null); p may be null.  Refused with a reason: more
+// than BH_CONCAT_MAX_INPUTS inputs, inputs that differ in shape or type,
+// 8-bit inputs without the output's quantisation, an output that is not the
+// stacked shape.  *axis: the resolved axis (0: the batch axis).
+bool PackArgs(const TflModel& m, const TflOperator& op, bh_concat_params* p, const char** why = nullptr,
+              int* axis = nullptr);
 
 // TFLite_Detection_PostProcess in the form the host kernel and the device
 // kernels (kernels/detection.hip) implement.  batch: the images of a

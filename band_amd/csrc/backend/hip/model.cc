@@ -91,9 +91,23 @@ absl::Status HipModel::CloneWithJobBatch(int batch, std::unique_ptr<HipModel>* o
                                          : "job batching: BATCH_MATMUL operand does not broadcast along the batch axis");
       }
     }
+    if (op.builtin == kTflGather) {
+      // the embedding (constant params, axis 0, runtime indices) or an
+      // activation gathered along an inner axis by constant indices
+      bool batch_ok = false;
+      const char* why = "";
+      if (ex::GatherArgs(desc_, op, nullptr, &why, &batch_ok) && !batch_ok)
+        return absl::InternalError(std::string("job batching: GATHER with ") + why);
+    }
+    if (op.builtin == kTflPack) {
+      int axis = -1;
+      if (ex::PackArgs(desc_, op, nullptr, nullptr, &axis) && axis == 0)
+        return absl::InternalError("job batching: PACK on the batch axis");
+    }
     if (ex::IsReindexOp(op.builtin)) {
       // a map may touch axis 0 only as the full range: no TRANSPOSE with
-      // perm[0] != 0, no SPLIT / SPLIT_V on axis 0, no slice of part of it
+      // perm[0] != 0, no SPLIT / SPLIT_V / UNPACK on axis 0, no slice of part
+      // of it, no TILE that repeats it
       for (int k = 0; k < static_cast<int>(op.outputs.size()); ++k) {
         bh_reindex_params map;
         bool whole_batch = false;

@@ -222,7 +222,9 @@ bool HipModelExecutor::GpuSupports(const TflModel& m, const TflOperator& op, std
     case kTflSplit:
     case kTflSplitV:
     case kTflSpaceToDepth:
-    case kTflDepthToSpace: {
+    case kTflDepthToSpace:
+    case kTflUnpack:
+    case kTflTile: {
       bh_reindex_params map;
       const char* w = "";
       for (int k = 0; k < static_cast<int>(op.outputs.size()); ++k)
@@ -232,6 +234,14 @@ bool HipModelExecutor::GpuSupports(const TflModel& m, const TflOperator& op, std
     case kTflBatchMatMul: {
       const char* w = "";
       return BatchMatMulArgs(m, op, nullptr, &w) ? true : no(w);
+    }
+    case kTflGather: {
+      const char* w = "";
+      return GatherArgs(m, op, nullptr, &w) ? true : no(w);
+    }
+    case kTflPack: {
+      const char* w = "";
+      return PackArgs(m, op, nullptr, &w) ? true : no(w);
     }
     case kTflSoftmax:
       if (!IsQ8(in.type) || out.type != in.type || !HasQ(in) || !HasQ(out) || in.shape.empty())

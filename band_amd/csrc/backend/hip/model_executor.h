@@ -284,6 +284,8 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   // that is the identity lowers as RESHAPE does (a kCopy, dropped when both
   // sides share a slot)
   absl::Status LowerReindex(const HipModel& model, int op_index, PreparedSubgraph* sg);
+  // GATHER (GatherArgs): one kReindex launch whose map carries the indices; constant params / indices are uploaded once
+  absl::Status LowerGather(const HipModel& model, int op_index, PreparedSubgraph* sg);
   // BATCH_MATMUL int8 / float32 (BatchMatMulArgs): one kBatchMatMul / kBatchMatMulF32 launch
   absl::Status LowerBatchMatMul(const HipModel& model, int op_index, void* lhs_ptr, void* out_ptr,
                                 PreparedSubgraph* sg, Launch* L);

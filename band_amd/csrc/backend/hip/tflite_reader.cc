@@ -56,6 +56,10 @@ const char* TflBuiltinName(int c) {
     case kTflSplitV: return "SPLIT_V";
     case kTflBatchMatMul: return "BATCH_MATMUL";
     case kTflGelu: return "GELU";
+    case kTflGather: return "GATHER";
+    case kTflTile: return "TILE";
+    case kTflPack: return "PACK";
+    case kTflUnpack: return "UNPACK";
     default: return "UNKNOWN";
   }
 }

@@ -38,6 +38,9 @@ enum TflBuiltin : int {
   kTflBatchMatMul = 126,
   // GeluOptions: slot 0 approximate (bool)
   kTflGelu = 150,
+  // GatherOptions: slots 0-1 axis, batch_dims; PackOptions: slots 0-1
+  // values_count, axis; UnpackOptions: slots 0-1 num, axis; TILE has no fields
+  kTflGather = 36, kTflTile = 69, kTflPack = 83, kTflUnpack = 88,
 };
 
 const char* TflBuiltinName(int code);

@@ -36,8 +36,13 @@
 // Index math is 32-bit FastDiv (common.hpp), so a map of more than 2^31 - 1
 // elements is refused.  No scratch, atomics or host step: all three capture
 // into a hipGraph.
+//
+// A map that carries an index tensor (bh_reindex_params.indices: GATHER, whose
+// indices are data on the device) is not resolved here: the launcher hands it
+// to bh_gather (gather.hip).
 #include <limits.h>
 
+#include "band_hip_gather_shared.h"
 #include "common.hpp"
 
 namespace bh {
@@ -148,6 +153,7 @@ __global__ __launch_bounds__(256) void reindex_gather_kernel(RxMap m, int dword_
 
 // ---- host --------------------------------------------------------------------
 static const char* rx_canonical(const bh_reindex_params& p, bh_reindex_params* c) {
+  if (p.indices) return "bh_reindex: a map with indices has no canonical form";
   if (p.rank < 0) return "bh_reindex: invalid parameters";
   if (p.rank > kRxRank) return "bh_reindex: rank > 6";
   if (p.elem_bytes != 1 && p.elem_bytes != 4) return "bh_reindex: elem_bytes must be 1 or 4";
@@ -226,6 +232,10 @@ extern "C" int bh_reindex_canonical(const bh_reindex_params* p, bh_reindex_param
 }
 
 extern "C" const char* bh_reindex_kernel(const bh_reindex_params* p) {
+  if (p && p->indices) {  // GATHER as a map: gather.hip's kernel
+    bh_gather_params g;
+    return bh_reindex_as_gather(p, &g) ? "" : bh_gather_kernel(&g);
+  }
   bh_reindex_params c;
   if (!p || bh::rx_canonical(*p, &c)) return "";
   int jpos = -1;
@@ -240,6 +250,14 @@ extern "C" int bh_reindex(const bh_reindex_params* pp, bh_stream_t s) { return b
 
 extern "C" int bh_reindex_as(const bh_reindex_params* pp, int gather, bh_stream_t s) {
   using namespace bh;
+  if (pp && pp->indices && !gather) {
+    bh_gather_params g;
+    if (const char* e = bh_reindex_as_gather(pp, &g)) {
+      bh_set_last_error(e);
+      return BH_EINVAL;
+    }
+    return bh_gather(&g, s);
+  }
   bh_reindex_params c;
   const char* err = pp ? rx_canonical(*pp, &c) : "bh_reindex: invalid parameters";
   if (!err && (!c.input || !c.output || (uintptr_t)c.input % c.elem_bytes || (uintptr_t)c.output % c.elem_bytes))

@@ -35,6 +35,10 @@ OPTION_FIELDS = {
     27: [(0, "b")],                                                             # Reducer (MEAN keep_dims)
     76: [],                                                                     # SquaredDifference
     116: [(0, "b")],                                                            # Gelu (approximate)
+    23: [(0, "i"), (1, "i")],                                                   # Gather (axis, batch_dims)
+    51: [],                                                                     # Tile
+    59: [(0, "i"), (1, "i")],                                                   # Pack (values_count, axis)
+    64: [(0, "i"), (1, "i")],                                                   # Unpack (num, axis)
 }
 
 

@@ -30,7 +30,8 @@ OPC = dict(ADD=0, AVERAGE_POOL_2D=1, CONCATENATION=2, CONV_2D=3, DEPTHWISE_CONV_
            TRANSPOSE_CONV=67, ARG_MAX=56, ARG_MIN=79,
            DEPTH_TO_SPACE=5, SPACE_TO_DEPTH=26, TRANSPOSE=39, STRIDED_SLICE=45, SPLIT=49, SLICE=65, SPLIT_V=102,
            BATCH_MATMUL=126,
-           MEAN=40, RSQRT=76, SQUARED_DIFFERENCE=99, GELU=150)
+           MEAN=40, RSQRT=76, SQUARED_DIFFERENCE=99, GELU=150,
+           GATHER=36, TILE=69, PACK=83, UNPACK=88)
 # BuiltinOptions union indices
 OPT = dict(Conv2DOptions=1, DepthwiseConv2DOptions=2, Pool2DOptions=5, FullyConnectedOptions=8,
            SoftmaxOptions=9, ConcatenationOptions=10, AddOptions=11, ReshapeOptions=17,
@@ -42,7 +43,9 @@ OPT = dict(Conv2DOptions=1, DepthwiseConv2DOptions=2, Pool2DOptions=5, FullyConn
            # written from memory of schema.fbs; the C++ reader never keys on the union number
            BatchMatMulOptions=101,
            # ... and so are these three
-           ReducerOptions=27, SquaredDifferenceOptions=76, GeluOptions=116)
+           ReducerOptions=27, SquaredDifferenceOptions=76, GeluOptions=116,
+           # ... and these four
+           GatherOptions=23, TileOptions=51, PackOptions=59, UnpackOptions=64)
 
 
 # ---------------------------------------------------------------------------
@@ -324,9 +327,11 @@ def _bmm_shape(sa, sb, adj_x, adj_y):
 
 class _ReindexOps:
     """The re-indexing ops of QGraph and FGraph: TRANSPOSE, STRIDED_SLICE,
-    SLICE, SPLIT, SPLIT_V, SPACE_TO_DEPTH, DEPTH_TO_SPACE.  They draw nothing
-    from the RNG; an output inherits the input's quantisation (the ops copy
-    bytes).  Index arguments are constant int32 tensors."""
+    SLICE, SPLIT, SPLIT_V, SPACE_TO_DEPTH, DEPTH_TO_SPACE, UNPACK, TILE, and
+    GATHER and PACK beside them.  They draw nothing from the RNG; an output
+    inherits the input's quantisation (the ops copy bytes).  Index arguments
+    are constant int32 tensors, except GATHER's indices, which may be a tensor
+    of the graph."""
 
     def _re_out(self, x, shape):
         shape = [int(v) for v in shape]
@@ -402,6 +407,47 @@ class _ReindexOps:
         self.mb.op("DEPTH_TO_SPACE", [x], [y], OPT["DepthToSpaceOptions"], Table().set(0, "i", block_size))
         return y
 
+    def gather(self, params, indices, axis=0, batch_dims=0, index_dtype=np.int32):
+        """np.take(params, indices, axis).  `indices` is a tensor of the graph (an
+        int32 / int64 input) or a list / array, which becomes a constant of
+        index_dtype; the output inherits params' quantisation"""
+        shp = self.meta[params][0]
+        if isinstance(indices, (list, tuple, np.ndarray)):
+            v = np.asarray(indices, index_dtype)
+            ishape = list(v.shape)
+            indices = self.mb.tensor(self._name("indices"), ishape, index_dtype, data=v)
+        else:
+            ishape = self.meta[indices][0]
+        ax = axis + len(shp) if axis < 0 else axis
+        y = self._re_out(params, list(shp[:ax]) + list(ishape) + list(shp[ax + 1:]))
+        self.mb.op("GATHER", [params, indices], [y], OPT["GatherOptions"],
+                   Table().set(0, "i", axis).set(1, "i", batch_dims))
+        return y
+
+    def pack(self, xs, axis=0):
+        """np.stack(xs, axis); the inputs share one shape and, 8-bit, one quantisation"""
+        shp = list(self.meta[xs[0]][0])
+        ax = axis + len(shp) + 1 if axis < 0 else axis
+        y = self._re_out(xs[0], shp[:ax] + [len(xs)] + shp[ax:])
+        self.mb.op("PACK", list(xs), [y], OPT["PackOptions"], Table().set(0, "i", len(xs)).set(1, "i", axis))
+        return y
+
+    def unpack(self, x, axis=0):
+        """[np.moveaxis(x, axis, 0)[k] for k in range(x.shape[axis])]: a list of outputs"""
+        shp = list(self.meta[x][0])
+        ax = axis + len(shp) if axis < 0 else axis
+        ys = [self._re_out(x, shp[:ax] + shp[ax + 1:]) for _ in range(shp[ax])]
+        self.mb.op("UNPACK", [x], ys, OPT["UnpackOptions"], Table().set(0, "i", shp[ax]).set(1, "i", axis))
+        return ys
+
+    def tile(self, x, multiples):
+        """np.tile(x, multiples), one multiple per dim"""
+        shp = self.meta[x][0]
+        mt = self._re_ints("multiples", list(multiples))
+        y = self._re_out(x, [n * m for n, m in zip(shp, multiples)])
+        self.mb.op("TILE", [x, mt], [y], OPT["TileOptions"], Table())
+        return y
+
 
 # ---------------------------------------------------------------------------
 # quantised graph construction with synthetic (seeded) weights
@@ -436,7 +482,13 @@ class QGraph(_ReindexOps):
         self.meta[t] = (list(shape), scale, zp)
         return t
 
-    def input(self, shape, scale=0.0078125, zp=None):
+    def input(self, shape, scale=0.0078125, zp=None, dtype=None):
+        """a model input; dtype np.int32 / np.int64: an index tensor (token ids) without quantisation"""
+        if dtype is not None:
+            t = self.mb.tensor(self._name("input"), list(shape), dtype)
+            self.meta[t] = (list(shape), None, None)
+            self.mb.inputs.append(t)
+            return t
         zp = (0 if self.dtype == np.int8 else 128) if zp is None else zp
         t = self.act_tensor(shape, scale, zp, "input")
         self.mb.inputs.append(t)
@@ -902,8 +954,13 @@ class FGraph(_ReindexOps):
         self.mb.op("DEQUANTIZE", [c], [y], OPT["DequantizeOptions"], Table())
         return y
 
-    def input(self, shape, scale=None, zp=None):
-        t = self._act(shape, "input")
+    def input(self, shape, scale=None, zp=None, dtype=None):
+        """a float32 model input; dtype np.int32 / np.int64: an index tensor (token ids)"""
+        if dtype is not None:
+            t = self.mb.tensor(self._name("input"), list(shape), dtype)
+            self.meta[t] = (list(shape), None, None)
+        else:
+            t = self._act(shape, "input")
         self.mb.inputs.append(t)
         return t
 
@@ -1328,6 +1385,40 @@ def vit_tiny(dtype=np.int8, seed=7, size=224, dim=192, heads=3, blocks=2, batch=
     for _ in range(blocks):
         y = _encoder(g, y, heads, 4 * dim, layer_norm, mlp) if (layer_norm or mlp) else _attention(g, y, heads)
     g.output(y)
+    return g.build()
+
+
+def text_encoder(dtype=np.int8, seed=9, tokens=128, dim=192, heads=3, hidden=768, blocks=2, vocab=1000, classes=2,
+                 batch=1, hybrid=None):
+    """A BERT-style classifier on token ids [batch, tokens] int32: GATHER of a
+    constant [vocab, dim] embedding table (axis 0), ADD of a constant
+    [1, tokens, dim] position embedding, LayerNorm, `blocks` pre-norm encoder
+    blocks (encoder_block's), STRIDED_SLICE of token 0 and a FULLY_CONNECTED to
+    `classes`.  dtype float32 (or float16) builds the fp16-constant float
+    model, or with `hybrid` ("symmetric" | "asymmetric") the dynamic-range one;
+    the table is then a float32 constant either way (GATHER reads it as it is
+    stored).  Keep vocab > 99: the benchmark tool fills int32 inputs with
+    0 .. 99."""
+    assert hybrid is None or np.dtype(dtype) == np.dtype(np.float32), "hybrid is a form of the float32 model"
+    quant = np.dtype(dtype) not in (np.dtype(np.float32), np.dtype(np.float16))
+    if quant:
+        g = QGraph(dtype, seed, "text_encoder_%s" % np.dtype(dtype).name)
+    else:
+        g = FGraph(seed, "text_encoder_f32" + ("_hybrid" if hybrid else ""), hybrid=hybrid)
+    ids = g.input([batch, tokens], dtype=np.int32)
+    table = g.rng.normal(0.0, 1.0, (vocab, dim))
+    if quant:
+        tab = g.const(table, "embedding")
+    else:
+        tab = g.mb.tensor(g._name("embedding"), [vocab, dim], np.float32, data=table.astype(np.float32))
+        g.meta[tab] = ([vocab, dim], None, None)
+    y = g.gather(tab, ids, axis=0)
+    y = g.add(y, g.const(g.rng.normal(0.0, 0.5, (1, tokens, dim)), "position"))
+    y = g.layer_norm(y)
+    for _ in range(blocks):
+        y = _encoder(g, y, heads, hidden)
+    y = g.strided_slice(y, [0, 0, 0], [0, 1, 0], [1, 1, 1], begin_mask=0b101, end_mask=0b101, shrink_axis_mask=0b010)
+    g.output(g.fully_connected(y, classes))
     return g.build()
 
 

@@ -182,6 +182,9 @@ int bhx_time_subgraph(bhx_executor* e, int model_id, int worker_id, uint64_t uni
  * `reindex_params` is a bh_reindex_params (band_hip_kernels.h).  Tests compare
  * it with numpy without building a model around every map. */
 int bhx_cpu_reindex(const void* reindex_params);
+/* CpuGather, the host twin of bh_gather, over host pointers: `gather_params`
+ * is a bh_gather_params (band_hip_kernels.h) */
+int bhx_cpu_gather(const void* gather_params);
 /* kernel symbols (static storage) of a prepared subgraph's launches in program
  * order, up to cap; *n = the count.  Works on kCPU executors too. */
 int bhx_launch_kernels(bhx_executor* e, int model_id, int worker_id, uint64_t unit_mask, const char** out, int cap,

@@ -38,7 +38,9 @@
  *   bh_argminmax      <- ARG_MAX / ARG_MIN  (reference_ops::ArgMinMax: first extreme, strict compare)
  *   bh_resize_bilinear_argminmax_i8 <- RESIZE_BILINEAR int8 -> ARG_MAX / ARG_MIN over channels, fused
  *   bh_reindex        <- TRANSPOSE, STRIDED_SLICE, SLICE, SPLIT, SPLIT_V, SPACE_TO_DEPTH,
- *                        DEPTH_TO_SPACE (one launch per output; numpy's indexing semantics)
+ *                        DEPTH_TO_SPACE, UNPACK, TILE (one launch per output; numpy's indexing
+ *                        semantics; PACK runs through bh_concat)
+ *   bh_gather         <- GATHER (np.take along one axis; the indices may be a runtime tensor)
  *   bh_batch_matmul_i8 / bh_batch_matmul_f32 <- BATCH_MATMUL int8 / float32 (the arithmetic of
  *                        reference_integer_ops::FullyConnected without a bias, per batch slice)
  *   bh_dynquant_rows + bh_fc_hybrid <- FULLY_CONNECTED float32 with int8 weights (fully_connected.cc
@@ -851,6 +853,15 @@ typedef struct {
   int64_t in_offset;              /* elements */
   const void* input;              /* aligned to elem_bytes */
   void* output;                   /* aligned to elem_bytes */
+  /* GATHER as a map: with `indices` set (null: a plain map, everything above)
+   * the map is [outer][n_idx][inner] with in_stride {index_range * inner, inner,
+   * 1} and in_offset 0, and coordinate j of dim 1 reads input row indices[j]
+   * instead of row j: bh_reindex, bh_reindex_kernel and CpuReindex hand it to
+   * bh_gather / CpuGather (bh_gather_params below, where the out-of-range rule
+   * is); bh_reindex_canonical and bh_reindex_as(gather != 0) refuse it. */
+  const void* indices;            /* n_idx int32 / int64 values on the device, aligned to index_bytes */
+  int index_bytes;                /* 4 or 8 */
+  int64_t index_range;            /* axis_size: an index outside [0, index_range) gives a zero row */
 } bh_reindex_params;
 int bh_reindex(const bh_reindex_params* p, bh_stream_t s);
 /* the kernel bh_reindex dispatches to for this map ("" for a refused one) */
@@ -860,6 +871,34 @@ int bh_reindex_canonical(const bh_reindex_params* p, bh_reindex_params* canonica
  * reindex_gather_kernel, which takes any map, whatever bh_reindex would pick
  * (tools/reindex_profile.py times the forms side by side); 0 is bh_reindex. */
 int bh_reindex_as(const bh_reindex_params* p, int gather, bh_stream_t s);
+
+/* GATHER (batch_dims 0): params viewed as [outer][axis_size][inner] elements,
+ * `indices` a flat list of n_idx int32 / int64 values in device memory (a
+ * constant or an activation), output dense [outer][n_idx][inner] =
+ * np.take(params, indices, axis).  One kernel, gather_rows_kernel: a lane moves
+ * V = 16 / 8 / 4 / 1 bytes, the widest that divides inner * elem_bytes and both
+ * base addresses; no scratch, no atomics.  An index outside [0, axis_size)
+ * reads nothing and its output slice is zero bytes (TFLite fails the invoke on
+ * a negative index and leaves a too large one undefined; a replayed graph can
+ * do neither); the range check is band_hip_gather_shared.h's, shared with the
+ * host twin.  Refused (BH_EINVAL, bh_last_error names bh_gather and the
+ * reason): null pointers, elem_bytes not 1 or 4, index_bytes not 4 or 8, a
+ * count < 1, params / output not aligned to elem_bytes, indices not aligned to
+ * index_bytes, more than 2^31 - 1 output bytes (FastDiv index math). */
+typedef struct {
+  int elem_bytes;                 /* 1 or 4 */
+  int index_bytes;                /* 4 or 8 */
+  int64_t outer, axis_size, n_idx;
+  int64_t inner;                  /* elements */
+  const void* params;             /* aligned to elem_bytes */
+  const void* indices;            /* aligned to index_bytes */
+  void* output;                   /* aligned to elem_bytes */
+} bh_gather_params;
+int bh_gather(const bh_gather_params* p, bh_stream_t s);
+/* the kernel bh_gather dispatches to ("" for refused parameters) */
+const char* bh_gather_kernel(const bh_gather_params* p);
+/* the refusals above alone; pure host */
+int bh_gather_check(const bh_gather_params* p);
 
 /* BATCH_MATMUL: out[b0, b1] = lhs[b0, b1] x rhs[b0, b1], an [m, k] by [k, n]
  * product per batch index; both operands may be activations.  The output is
