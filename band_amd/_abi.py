@@ -249,14 +249,32 @@ class AttentionQuant(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("lhs_zp", "rhs_zp", "out_zp", "mult", "shift", "requant_fast")]
 
 
+CAST_U8, CAST_I32, CAST_I64, CAST_F32 = 1, 2, 3, 4
+
+
+class CastParams(ctypes.Structure):
+    """bh_cast_params: `count` elements of in_type (CAST_*) at input as out_type at output"""
+    _fields_ = [("in_type", c_int), ("out_type", c_int), ("count", ctypes.c_long), ("input", c_void_p),
+                ("output", c_void_p)]
+
+
+class AttentionAdd(ctypes.Structure):
+    """bh_attention_add: an int8 ADD's constants in EltwiseParams' order"""
+    _fields_ = [(n, c_int32) for n in ("a_off", "b_off", "o_off", "left_shift", "a_mult", "a_shift",
+                                       "b_mult", "b_shift", "o_mult", "o_shift", "act_min", "act_max")]
+
+
 class AttentionParams(ctypes.Structure):
-    """bh_attention_params: q, k, v and out by strides (elements); a batch stride of 0 broadcasts"""
+    """bh_attention_params: q, k, v and out by strides (elements); a batch stride of 0 broadcasts.  bias (NULL:
+    none) is ADDed to the scores before the softmax; add_scores_operand says which ADD operand the scores are"""
     _fields_ = [("batch", c_int32 * 2)] + [(n, c_int32) for n in ("rows", "keys", "head_dim", "out_dim")] + [
         (n, ctypes.c_int64 * 2) for n in ("q_bstride", "k_bstride", "v_bstride", "out_bstride")] + [
         (n, ctypes.c_int64) for n in ("q_row_stride", "k_row_stride", "v_row_stride", "out_row_stride",
                                       "q_inner_stride", "k_inner_stride", "v_inner_stride", "out_inner_stride")] + [
         ("qk", AttentionQuant), ("pv", AttentionQuant), ("table", c_void_p), ("sm_out_scale", ctypes.c_float),
-        ("sm_out_zp", c_int32), ("kernel_hint", c_int32)] + [(n, c_void_p) for n in ("q", "k", "v", "out")]
+        ("sm_out_zp", c_int32), ("kernel_hint", c_int32)] + [(n, c_void_p) for n in ("q", "k", "v", "out")] + [
+        ("bias", c_void_p), ("bias_bstride", ctypes.c_int64 * 2), ("bias_row_stride", ctypes.c_int64),
+        ("bias_key_stride", ctypes.c_int64), ("add", AttentionAdd), ("add_scores_operand", c_int32)]
 
 
 class ZeroInsertParams(ctypes.Structure):
@@ -386,6 +404,7 @@ KERNEL_SYMBOLS = {
     "bh_dwconv2d_hybrid_kernel": (ctypes.c_char_p, [ctypes.POINTER(ConvHybridParams)]),
     "bh_dwconv2d_hybrid_check": (c_int, [ctypes.POINTER(ConvHybridParams)]),
     "bh_softmax_i8": (c_int, [ctypes.POINTER(SoftmaxParams), c_void_p]),
+    "bh_cast": (c_int, [ctypes.POINTER(CastParams), c_void_p]),
     "bh_attention_i8": (c_int, [ctypes.POINTER(AttentionParams), c_void_p]),
     "bh_attention_i8_kernel": (ctypes.c_char_p, [ctypes.POINTER(AttentionParams)]),
     "bh_attention_i8_check": (c_int, [ctypes.POINTER(AttentionParams)]),

@@ -97,6 +97,8 @@ _abi.BACKEND_SYMBOLS.update({
     "bhx_cpu_unary_f32": (c_int, [c_int, c_void_p, c_void_p, ctypes.c_long]),
     "bhx_rsqrt_table": (c_int, [ctypes.c_float, c_int, ctypes.c_float, c_int, c_void_p]),
     "bhx_gelu_table": (c_int, [c_int, c_int, ctypes.c_float, c_int, ctypes.c_float, c_int, c_void_p]),
+    "bhx_cpu_cast": (c_int, [c_void_p]),
+    "bhx_tanh_table": (c_int, [c_int, ctypes.c_float, c_int, ctypes.c_float, c_int, c_void_p]),
     "bhx_squared_difference_params": (c_int, [ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                               ctypes.POINTER(ctypes.c_int32)]),
     "bhx_prepare_job_batches": (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.c_uint64, c_int]),

@@ -11,6 +11,7 @@
 #include "backend/hip/affinity.h"
 #include "backend/hip/backend.h"
 #include "band_hip_backend.h"
+#include "band_hip_cast_shared.h"
 
 using band::BackendFactory;
 using band::BackendType;
@@ -570,7 +571,7 @@ int bhx_cpu_eltwise(const void* eltwise_params) {
 }
 
 int bhx_cpu_unary_f32(int kind, const float* in, float* out, long n) {
-  if (!in || !out || n < 0 || kind < BH_UNARY_LOGISTIC || kind > BH_UNARY_GELU_TANH)
+  if (!in || !out || n < 0 || kind < BH_UNARY_LOGISTIC || (kind > BH_UNARY_GELU_TANH && kind != BH_UNARY_TANH))
     return Fail("CpuUnaryF32: invalid parameters");
   band::hip::CpuUnaryF32(kind, in, out, n, 0.f, 0.f);
   return 0;
@@ -585,6 +586,21 @@ int bhx_gelu_table(int is_signed, int approximate, float in_scale, int in_zp, fl
                    uint8_t* table) {
   if (!table) return Fail("null argument");
   band::hip::GeluTable(is_signed != 0, approximate != 0, in_scale, in_zp, out_scale, out_zp, table);
+  return 0;
+}
+
+int bhx_cpu_cast(const void* cast_params) {
+  const auto* p = static_cast<const bh_cast_params*>(cast_params);
+  if (!p || !p->input || !p->output || p->count < 0 || !bh_cast_type_bytes(p->in_type) ||
+      !bh_cast_type_bytes(p->out_type))
+    return Fail("CpuCast: invalid parameters");
+  band::hip::CpuCast(*p);
+  return 0;
+}
+
+int bhx_tanh_table(int is_signed, float in_scale, int in_zp, float out_scale, int out_zp, uint8_t* table) {
+  if (!table) return Fail("null argument");
+  band::hip::TanhTable(is_signed != 0, in_scale, in_zp, out_scale, out_zp, table);
   return 0;
 }
 

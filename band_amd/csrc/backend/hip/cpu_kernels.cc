@@ -3,6 +3,7 @@
 #include "backend/hip/affinity.h"
 
 #include "backend/hip/quant.h"
+#include "band_hip_cast_shared.h"
 #include "band_hip_gather_shared.h"
 
 #include <pthread.h>
@@ -666,6 +667,39 @@ void CpuPoolF32(const bh_pool_f32_params& p) {
       }
 }
 
+namespace {
+template <class S, class D>
+void CastRun(const bh_cast_params& p) {
+  const uint8_t* in = static_cast<const uint8_t*>(p.input);
+  uint8_t* out = static_cast<uint8_t*>(p.output);
+  for (long i = 0; i < p.count; ++i) {
+    S v;
+    std::memcpy(&v, in + i * sizeof(S), sizeof(S));
+    const D w = bh_cast_one<S, D>(v);
+    std::memcpy(out + i * sizeof(D), &w, sizeof(D));
+  }
+}
+template <class S>
+void CastFrom(const bh_cast_params& p) {
+  switch (p.out_type) {
+    case BH_CAST_U8: return CastRun<S, uint8_t>(p);
+    case BH_CAST_I32: return CastRun<S, int32_t>(p);
+    case BH_CAST_I64: return CastRun<S, int64_t>(p);
+    default: return CastRun<S, float>(p);
+  }
+}
+}  // namespace
+
+void CpuCast(const bh_cast_params& p) {
+  if (!p.input || !p.output || p.count <= 0 || !bh_cast_type_bytes(p.in_type) || !bh_cast_type_bytes(p.out_type)) return;
+  switch (p.in_type) {
+    case BH_CAST_U8: return CastFrom<uint8_t>(p);
+    case BH_CAST_I32: return CastFrom<int32_t>(p);
+    case BH_CAST_I64: return CastFrom<int64_t>(p);
+    default: return CastFrom<float>(p);
+  }
+}
+
 void CpuUnaryF32(int kind, const float* in, float* out, long n, float lo, float hi) {
   if (kind == BH_UNARY_GELU || kind == BH_UNARY_GELU_TANH) {
     for (long i = 0; i < n; ++i) {
@@ -674,6 +708,10 @@ void CpuUnaryF32(int kind, const float* in, float* out, long n, float lo, float 
                    ? 0.5f * x * (1.0f + std::erf(x * 0.70710678118654752440f))
                    : 0.5f * x * (1.0f + std::tanh(0.79788456080286535588f * x * (1.0f + 0.044715f * x * x)));
     }
+    return;
+  }
+  if (kind == BH_UNARY_TANH) {
+    for (long i = 0; i < n; ++i) out[i] = std::tanh(in[i]);
     return;
   }
   for (long i = 0; i < n; ++i)

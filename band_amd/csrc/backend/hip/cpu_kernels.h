@@ -58,6 +58,9 @@ void CpuEltwise(const bh_eltwise_params& p, CpuPool& pool);
 void CpuPool2D(const bh_pool_params& p, CpuPool& pool);
 void CpuLutU8(const void* in, void* out, long n, const uint8_t* table, CpuPool& pool);
 void CpuLutF32(const void* in, float* out, long n, const float* table, CpuPool& pool);
+// CAST: bh_cast's twin, the conversion of band_hip_cast_shared.h (never an undefined float -> integer conversion);
+// the pointers need no alignment here
+void CpuCast(const bh_cast_params& p);
 void CpuQuantizeF32(const float* in, void* out, long n, float scale, int32_t zp, int out_signed, CpuPool& pool);
 void CpuConcat(const bh_concat_params& p);
 void CpuPad(const bh_pad_params& p);

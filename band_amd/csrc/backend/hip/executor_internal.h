@@ -120,7 +120,7 @@ inline bool IsFloatOp(const TflModel& m, const TflOperator& op) {
     case kTflBatchMatMul:
     case kTflConv2D: case kTflDepthwiseConv2D: case kTflFullyConnected: case kTflAdd: case kTflSub: case kTflMul:
     case kTflAveragePool2D: case kTflMaxPool2D: case kTflRelu: case kTflRelu6: case kTflReluN1To1:
-    case kTflLogistic: case kTflSoftmax: case kTflSquaredDifference: case kTflRsqrt: case kTflGelu:
+    case kTflLogistic: case kTflSoftmax: case kTflSquaredDifference: case kTflRsqrt: case kTflGelu: case kTflTanh:
       return t == DataType::kFloat32;
     case kTflDequantize:
       return t == DataType::kFloat16;
@@ -177,6 +177,10 @@ inline bool FloatSupports(const TflModel& m, const TflOperator& op, std::string*
     case kTflBatchMatMul: {
       const char* w = "";
       return BatchMatMulArgs(m, op, nullptr, &w) ? true : no(w);
+    }
+    case kTflTanh: {
+      const char* w = "";
+      return TanhArgs(m, op, nullptr, &w) ? true : no(w);
     }
     default:
       return true;  // RELU / RELU6 / RELU_N1_TO_1 / LOGISTIC / RSQRT / GELU

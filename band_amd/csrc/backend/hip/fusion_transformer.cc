@@ -266,6 +266,15 @@ void HipModelExecutor::FoldLayerNormQuant(const HipModel& model, PreparedSubgrap
 // ctx's only reader is absorbed into the output strides, and the fused launch
 // then writes the TRANSPOSE's output tensor.  An operand that cannot be
 // absorbed stays the dense tensor it was.
+//   The masked pattern.  Four consecutive launches, with an int8 ADD between
+// the first product and the SOFTMAX: exactly one ADD operand is the scores
+// (either position); the scores and the ADD's output are private to the
+// pattern under the same rule.  The other operand, the bias, is int8, a
+// constant or a runtime tensor, and is only read, so it need not be private
+// (one padding mask feeds every block); after Shape4 it broadcasts to
+// [b0, b1, rows, keys], and its strides are 0 for extents of 1.  The fused
+// launch (attention_bias_i8_kernel) carries the ADD's block as lowered, and
+// the SOFTMAX's table is then the one of the ADD output's scale.
 void HipModelExecutor::FuseAttention(const HipModel& model, PreparedSubgraph* sg) {
   const TflModel& d = model.desc();
   std::vector<Launch>& ls = sg->launches;
@@ -320,22 +329,52 @@ void HipModelExecutor::FuseAttention(const HipModel& model, PreparedSubgraph* sg
     return -1;
   };
   for (size_t i = 0; i + 2 < ls.size(); ++i) {
-    const Launch &A = ls[i], &S = ls[i + 1], &B = ls[i + 2];
-    if (A.kind() != Launch::kBatchMatMul || S.kind() != Launch::kSoftmax || B.kind() != Launch::kBatchMatMul) continue;
-    if (A.op_index < 0 || S.op_index < 0 || B.op_index < 0) continue;
+    const Launch& A = ls[i];
+    if (A.kind() != Launch::kBatchMatMul) continue;
+    // the masked pattern: an int8 ADD of the scores and a bias between the first product and the SOFTMAX
+    const size_t e = ls[i + 1].kind() == Launch::kEltwise ? 1 : 0;
+    if (i + 2 + e >= ls.size()) continue;
+    const Launch* E = e ? &ls[i + 1] : nullptr;
+    const Launch &S = ls[i + 1 + e], &B = ls[i + 2 + e];
+    if (S.kind() != Launch::kSoftmax || B.kind() != Launch::kBatchMatMul) continue;
+    if (A.op_index < 0 || S.op_index < 0 || B.op_index < 0 || (E && E->op_index < 0)) continue;
     const TflOperator &oa = d.ops[A.op_index], &os = d.ops[S.op_index], &ob = d.ops[B.op_index];
     if (oa.builtin != kTflBatchMatMul || os.builtin != kTflSoftmax || ob.builtin != kTflBatchMatMul) continue;
     auto adj = [](const TflOperator& op, int k) { return op.options.valid() && op.options.Int8(k, 0) != 0; };
     if (adj(oa, 0) || !adj(oa, 1) || adj(ob, 0) || adj(ob, 1)) continue;
     const int sc = oa.outputs[0], pr = os.outputs[0], ctx = ob.outputs[0];
-    if (os.inputs[0] != sc || ob.inputs[0] != pr || ob.inputs[1] == pr || A.out_tensor != sc || S.out_tensor != pr ||
+    // what the SOFTMAX reads: the scores, or the ADD's output; exactly one ADD operand is the scores, the other
+    // (the bias: a constant or a runtime tensor, int8) is only read and may have other readers
+    int sm_in = sc, bias_t = -1, scores_operand = 0;
+    if (E) {
+      const TflOperator& oe = d.ops[E->op_index];
+      if (oe.builtin != kTflAdd || oe.inputs.size() != 2 || oe.outputs.size() != 1) continue;
+      if ((oe.inputs[0] == sc) == (oe.inputs[1] == sc)) continue;
+      scores_operand = oe.inputs[0] == sc ? 0 : 1;
+      bias_t = oe.inputs[1 - scores_operand];
+      sm_in = oe.outputs[0];
+      if (bias_t < 0 || E->out_tensor != sm_in || d.tensors[sm_in].type != DataType::kInt8 ||
+          d.tensors[bias_t].type != DataType::kInt8 || !PrivateTensor(d, *sg, sm_in, S.op_index))
+        continue;
+    }
+    if (os.inputs[0] != sm_in || ob.inputs[0] != pr || ob.inputs[1] == pr || A.out_tensor != sc || S.out_tensor != pr ||
         B.out_tensor != ctx)
       continue;
     if (d.tensors[sc].type != DataType::kInt8 || d.tensors[pr].type != DataType::kInt8) continue;
-    if (!PrivateTensor(d, *sg, sc, S.op_index) || !PrivateTensor(d, *sg, pr, B.op_index)) continue;
+    if (!PrivateTensor(d, *sg, sc, E ? E->op_index : S.op_index) || !PrivateTensor(d, *sg, pr, B.op_index)) continue;
     const bh_batch_matmul_params &a = A.as<bh_batch_matmul_params>(), &b = B.as<bh_batch_matmul_params>();
     const bh_softmax_params& s = S.as<bh_softmax_params>();
-    if (s.input != a.out || s.output != b.lhs || !s.is_signed || s.depth != a.n ||
+    const bh_eltwise_params* ep = E ? &E->as<bh_eltwise_params>() : nullptr;
+    if (ep) {
+      // the scores operand has the output's shape [b0, b1, rows, keys]; the bias broadcasts to it
+      const int so[4] = {a.batch[0], a.batch[1], a.m, a.n};
+      const int* ss = scores_operand == 0 ? ep->shape_a : ep->shape_b;
+      const int* sb = scores_operand == 0 ? ep->shape_b : ep->shape_a;
+      bool ok = ep->kind == BH_ELT_ADD && ep->in_signed && (scores_operand == 0 ? ep->a : ep->b) == a.out;
+      for (int k = 0; k < 4; ++k) ok = ok && ep->shape_o[k] == so[k] && ss[k] == so[k] && (sb[k] == 1 || sb[k] == so[k]);
+      if (!ok) continue;
+    }
+    if (s.input != (ep ? ep->out : a.out) || s.output != b.lhs || !s.is_signed || s.depth != a.n ||
         s.rows != static_cast<long>(a.batch[0]) * a.batch[1] * a.m)
       continue;
     if (b.batch[0] != a.batch[0] || b.batch[1] != a.batch[1] || b.m != a.m || b.k != a.n) continue;
@@ -370,6 +409,18 @@ void HipModelExecutor::FuseAttention(const HipModel& model, PreparedSubgraph* sg
     p.k = a.rhs;
     p.v = b.rhs;
     p.out = b.out;
+    if (ep) {
+      const int* sb = scores_operand == 0 ? ep->shape_b : ep->shape_a;
+      const int64_t st[4] = {static_cast<int64_t>(sb[1]) * sb[2] * sb[3], static_cast<int64_t>(sb[2]) * sb[3], sb[3], 1};
+      p.bias = scores_operand == 0 ? ep->b : ep->a;
+      p.bias_bstride[0] = sb[0] == 1 ? 0 : st[0];
+      p.bias_bstride[1] = sb[1] == 1 ? 0 : st[1];
+      p.bias_row_stride = sb[2] == 1 ? 0 : st[2];
+      p.bias_key_stride = sb[3] == 1 ? 0 : st[3];
+      p.add = bh_attention_add{ep->a_off,  ep->b_off,   ep->o_off,  ep->left_shift, ep->a_mult,  ep->a_shift,
+                               ep->b_mult, ep->b_shift, ep->o_mult, ep->o_shift,    ep->act_min, ep->act_max};
+      p.add_scores_operand = scores_operand;
+    }
     // the head TRANSPOSEs around the pattern
     const int jq = absorb_in(i, oa.inputs[0], A.op_index, a.lhs, p.q_bstride, &p.q_row_stride, &p.q);
     const int jk = oa.inputs[1] == oa.inputs[0] ? -1
@@ -378,7 +429,7 @@ void HipModelExecutor::FuseAttention(const HipModel& model, PreparedSubgraph* sg
                        ? -1
                        : absorb_in(i, ob.inputs[1], B.op_index, b.rhs, p.v_bstride, &p.v_row_stride, &p.v);
     int jo = -1;
-    for (size_t j = i + 3; j < ls.size() && jo < 0; ++j) {
+    for (size_t j = i + 3 + e; j < ls.size() && jo < 0; ++j) {
       const Launch& r = ls[j];
       if (r.kind() != Launch::kReindex || r.as<bh_reindex_params>().input != b.out) continue;
       const TflOperator& op = d.ops[r.op_index];
@@ -398,11 +449,16 @@ void HipModelExecutor::FuseAttention(const HipModel& model, PreparedSubgraph* sg
       F.out_tensor = r.out_tensor;
       jo = static_cast<int>(j);
     }
-    if (bh_attention_i8_check(&p) != 0) continue;  // over a limit: the three launches stay
+    if (bh_attention_i8_check(&p) != 0) continue;  // over a limit: the three (four) launches stay
     F.kernel = bh_attention_i8_kernel(&p);
     F.alg_ops = A.alg_ops + B.alg_ops;
     F.alg_bytes = static_cast<double>(meta_[oa.inputs[0]]->bytes + meta_[oa.inputs[1]]->bytes + meta_[ob.inputs[1]]->bytes +
                                       meta_[ctx]->bytes) + 1024.0;
+    if (E) {
+      F.alg_bytes += static_cast<double>(d.tensors[bias_t].num_elements());
+      sg->fused_ops.insert(E->op_index);
+      sg->fused_tensors.insert(sm_in);
+    }
     sg->fused_ops.insert(S.op_index);
     sg->fused_ops.insert(B.op_index);
     sg->fused_tensors.insert(sc);
@@ -418,9 +474,9 @@ void HipModelExecutor::FuseAttention(const HipModel& model, PreparedSubgraph* sg
       sg->fused_ops.insert(ls[jo].op_index);
       sg->fused_tensors.insert(ctx);
     }
-    dead[i + 1] = dead[i + 2] = true;
+    for (size_t j = i + 1; j <= i + 2 + e; ++j) dead[j] = true;
     ls[i] = F;
-    i += 2;
+    i += 2 + e;
   }
   DropDead(&ls, dead);
 }

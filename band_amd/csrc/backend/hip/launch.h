@@ -25,10 +25,15 @@ namespace band {
 namespace hip {
 
 // the payloads of the kinds whose launcher takes loose arguments
-struct CopyArgs {  // kCopy; nothing moves when src == dst
+// kCopy; nothing moves when src == dst.  cast_to != 0: a converting copy (CAST): `count` elements of BH_CAST_* type
+// cast_from at src are written as cast_to at dst (bh_cast / CpuCast), and `bytes` is the output's size.  CAST has no
+// kind of its own: it is a copy that changes the element type.
+struct CopyArgs {
   void* dst;
   const void* src;
   size_t bytes;
+  int cast_from = 0, cast_to = 0;
+  long count = 0;
 };
 struct LutArgs {  // kLutU8 / kLutF32: `count` bytes through a 256-entry device table of bytes / floats
   const void* src;
@@ -106,7 +111,7 @@ class Launch {
     kBatchMatMul,     // BATCH_MATMUL int8 (BatchMatMulArgs; never chained / grouped / blocked, no epilogue folds)
     kBatchMatMulF32,  // BATCH_MATMUL float32
     kLayerNorm,       // the ten ops of an int8 LayerNorm as one launch (FuseLayerNorm; kGPU)
-    kAttention,       // BATCH_MATMUL -> SOFTMAX -> BATCH_MATMUL (int8) as one launch (FuseAttention; kGPU, opt-in)
+    kAttention,       // BATCH_MATMUL -> [ADD of a mask / bias] -> SOFTMAX -> BATCH_MATMUL (int8) as one launch (FuseAttention; kGPU, opt-in)
     kDynQuantRows,    // hybrid FULLY_CONNECTED, first launch: the input's rows quantised into the subgraph's scratch
     kFcHybrid,        // hybrid FULLY_CONNECTED, second launch: int8 product, float epilogue
     kDynQuantItems,   // hybrid CONV_2D / DEPTHWISE_CONV_2D, first launch(es): each batch item quantised into the subgraph's scratch

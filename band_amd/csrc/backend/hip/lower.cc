@@ -245,6 +245,7 @@ absl::Status HipModelExecutor::LowerGlue(const HipModel& model, int oi, void* in
     case kTflLogistic:
     case kTflHardSwish:
     case kTflRsqrt:
+    case kTflTanh:
     case kTflGelu: {
       const long count = static_cast<long>(out.num_elements());
       if (op.builtin == kTflQuantize && in.type == DataType::kFloat32) {
@@ -264,6 +265,10 @@ absl::Status HipModelExecutor::LowerGlue(const HipModel& model, int oi, void* in
       } else if (op.builtin == kTflRsqrt) {
         if (!RsqrtTable(Scale(in), Zp(in), Scale(out), Zp(out), table))
           return absl::InternalError("RSQRT: output multiplier out of range");
+      } else if (op.builtin == kTflTanh) {
+        const char* why = "";
+        if (!TanhArgs(d, op, nullptr, &why)) return Refused(op, why);
+        TanhTable(i8, Scale(in), Zp(in), Scale(out), Zp(out), table);
       } else if (op.builtin == kTflGelu) {
         GeluTable(i8, op.options.valid() && op.options.Bool(0, false), Scale(in), Zp(in), Scale(out), Zp(out), table);
       } else {
@@ -659,11 +664,12 @@ absl::Status HipModelExecutor::LowerFloat(const HipModel& model, int oi, void* i
     }
     case kTflBatchMatMul:
       return LowerBatchMatMul(model, oi, in_ptr, out_ptr, sg, L);
-    default: {  // RELU / RELU6 / RELU_N1_TO_1 / LOGISTIC / RSQRT / GELU
+    default: {  // RELU / RELU6 / RELU_N1_TO_1 / LOGISTIC / RSQRT / GELU / TANH
       UnaryF32Args& a = L->Set<Launch::kUnaryF32>();
       L->kernel = "unary_f32_kernel";
       const bool approximate = op.builtin == kTflGelu && op.options.valid() && op.options.Bool(0, false);
       a.kind = op.builtin == kTflLogistic ? BH_UNARY_LOGISTIC
+               : op.builtin == kTflTanh   ? BH_UNARY_TANH
                : op.builtin == kTflRsqrt  ? BH_UNARY_RSQRT
                : op.builtin == kTflGelu   ? (approximate ? BH_UNARY_GELU_TANH : BH_UNARY_GELU)
                                           : BH_UNARY_CLAMP;
@@ -813,12 +819,15 @@ absl::Status HipModelExecutor::LowerGather(const HipModel& model, int oi, Prepar
   L.out_tensor = op.outputs[0];
   bh_gather_params p;
   const char* why = "";
-  if (!GatherArgs(d, op, &p, &why)) return Refused(op, why);
+  const bool lookup = op.builtin == kTflEmbeddingLookup;  // (ids, table): the operands exchanged, axis 0
+  if (!(lookup ? EmbeddingLookupArgs(d, op, &p, &why) : GatherArgs(d, op, &p, &why))) return Refused(op, why);
+  int pi = 0, ii = 1;
+  GatherOperands(op, &pi, &ii);
   void* params = nullptr;
   void* indices = nullptr;
   void* out_ptr = nullptr;
-  RETURN_STATUS_IF(DevicePtr(model, op.inputs[0], sg, &params));
-  RETURN_STATUS_IF(DevicePtr(model, op.inputs[1], sg, &indices));
+  RETURN_STATUS_IF(DevicePtr(model, op.inputs[pi], sg, &params));
+  RETURN_STATUS_IF(DevicePtr(model, op.inputs[ii], sg, &indices));
   RETURN_STATUS_IF(DevicePtr(model, op.outputs[0], sg, &out_ptr));
   p.params = params;
   p.indices = indices;
@@ -826,7 +835,7 @@ absl::Status HipModelExecutor::LowerGather(const HipModel& model, int oi, Prepar
   if (bh_gather_check(&p) != 0) return absl::InternalError(std::string("GATHER: ") + bh_last_error());
   const size_t bytes = meta_[op.outputs[0]]->bytes;
   std::vector<int64_t> idx;
-  bool identity = p.outer == 1 && p.n_idx == p.axis_size && ConstInts(d.tensors[op.inputs[1]], &idx);
+  bool identity = p.outer == 1 && p.n_idx == p.axis_size && ConstInts(d.tensors[op.inputs[ii]], &idx);
   for (size_t i = 0; identity && i < idx.size(); ++i) identity = idx[i] == static_cast<int64_t>(i);
   if (identity) {
     if (params == out_ptr) return absl::OkStatus();
@@ -1315,7 +1324,7 @@ absl::Status HipModelExecutor::Lower(const HipModel& model, int oi, PreparedSubg
     return absl::OkStatus();
   }
   if (IsReindexOp(op.builtin)) return LowerReindex(model, oi, sg);
-  if (op.builtin == kTflGather) return LowerGather(model, oi, sg);
+  if (op.builtin == kTflGather || op.builtin == kTflEmbeddingLookup) return LowerGather(model, oi, sg);
   void* in_ptr = nullptr;
   void* out_ptr = nullptr;
   RETURN_STATUS_IF(DevicePtr(model, op.inputs[0], sg, &in_ptr));
@@ -1338,6 +1347,23 @@ absl::Status HipModelExecutor::Lower(const HipModel& model, int oi, PreparedSubg
       case kTflBatchMatMul: return LowerBatchMatMul(model, oi, in_ptr, out_ptr, sg, &L);
       case kTflCustom:
         return cpu ? LowerDetectionHost(model, oi, in_ptr, sg, &L) : LowerDetectionGpu(model, oi, sg, &L);
+      case kTflCast: {  // equal types: a copy; else a converting copy (cast_kernel / CpuCast)
+        int from = 0, to = 0;
+        const char* why = "";
+        if (!CastArgs(d, op, &from, &to, &why)) return Refused(op, why);
+        const size_t bytes = meta_[op.outputs[0]]->bytes;
+        CopyArgs c{out_ptr, in_ptr, bytes};
+        if (from != to) {
+          c.cast_from = from;
+          c.cast_to = to;
+          c.count = static_cast<long>(d.tensors[op.outputs[0]].num_elements());
+        }
+        L.Set<Launch::kCopy>(c);
+        L.kernel = from == to ? "copy" : (cpu ? "cast_host" : "cast_kernel");
+        L.alg_bytes = static_cast<double>(meta_[op.inputs[0]]->bytes + bytes);
+        emit = from != to || in_ptr != out_ptr;
+        return absl::OkStatus();
+      }
       case kTflReshape: case kTflSqueeze:  // same bytes, new dims
         L.Set<Launch::kCopy>({out_ptr, in_ptr, meta_[op.outputs[0]]->bytes});
         L.kernel = "copy";

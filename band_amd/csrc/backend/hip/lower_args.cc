@@ -753,28 +753,27 @@ bool ReindexArgs(const TflModel& m, const TflOperator& op, int oi, bh_reindex_pa
   return true;
 }
 
-bool GatherArgs(const TflModel& m, const TflOperator& op, bh_gather_params* p, const char** why, bool* batch_ok) {
+// GATHER's map for params tensor `pt` and indices tensor `it` of op (axis and
+// batch_dims as given): the body of GatherArgs and of EmbeddingLookupArgs
+static bool GatherBody(const TflModel& m, const TflOperator& op, int pt, int it, int axis, int batch_dims,
+                       bh_gather_params* p, const char** why, bool* batch_ok) {
   auto no = [&](const char* w) {
     if (why) *why = w;
     return false;
   };
-  if (op.builtin != kTflGather || op.inputs.size() < 2 || op.inputs[0] < 0 || op.inputs[1] < 0 || op.outputs.empty() ||
-      op.outputs[0] < 0)
-    return no("GATHER needs params, indices and an output");
-  const TflTensor& in = m.tensors[op.inputs[0]];
-  const TflTensor& ix = m.tensors[op.inputs[1]];
+  const TflTensor& in = m.tensors[pt];
+  const TflTensor& ix = m.tensors[it];
   const TflTensor& out = m.tensors[op.outputs[0]];
   if (in.type != DataType::kInt8 && in.type != DataType::kUInt8 && in.type != DataType::kFloat32 &&
       in.type != DataType::kInt32)
     return no("GATHER params must be int8, uint8, float32 or int32");
   if (out.type != in.type) return no("GATHER output type differs from params'");
   if (ix.type != DataType::kInt32 && ix.type != DataType::kInt64) return no("GATHER indices must be int32 or int64");
-  if (op.options.valid() && op.options.Int(1, 0) != 0) return no("GATHER batch_dims != 0");
+  if (batch_dims != 0) return no("GATHER batch_dims != 0");
   if (IsQ8(in.type) && (in.scale != out.scale || in.zero_point != out.zero_point))
     return no("GATHER output quantization differs from params' (GATHER never requantises)");
   const int r = static_cast<int>(in.shape.size());
   if (r < 1 || r > 6) return no("GATHER params rank must be 1-6");
-  int axis = op.options.valid() ? op.options.Int(0, 0) : 0;
   if (axis < 0) axis += r;
   if (axis < 0 || axis >= r) return no("GATHER axis out of range");
   std::vector<int> expect(in.shape.begin(), in.shape.begin() + axis);
@@ -815,6 +814,70 @@ bool GatherArgs(const TflModel& m, const TflOperator& op, bh_gather_params* p, c
     *batch_ok = w == nullptr;
     if (w && why) *why = w;
   }
+  return true;
+}
+
+bool GatherArgs(const TflModel& m, const TflOperator& op, bh_gather_params* p, const char** why, bool* batch_ok) {
+  if (op.builtin != kTflGather || op.inputs.size() < 2 || op.inputs[0] < 0 || op.inputs[1] < 0 || op.outputs.empty() ||
+      op.outputs[0] < 0) {
+    if (why) *why = "GATHER needs params, indices and an output";
+    return false;
+  }
+  return GatherBody(m, op, op.inputs[0], op.inputs[1], op.options.valid() ? op.options.Int(0, 0) : 0,
+                    op.options.valid() ? op.options.Int(1, 0) : 0, p, why, batch_ok);
+}
+
+bool EmbeddingLookupArgs(const TflModel& m, const TflOperator& op, bh_gather_params* p, const char** why,
+                         bool* batch_ok) {
+  auto no = [&](const char* w) {
+    if (why) *why = w;
+    return false;
+  };
+  if (op.builtin != kTflEmbeddingLookup || op.inputs.size() < 2 || op.inputs[0] < 0 || op.inputs[1] < 0 ||
+      op.outputs.empty() || op.outputs[0] < 0)
+    return no("EMBEDDING_LOOKUP needs ids, a table and an output");
+  if (m.tensors[op.inputs[1]].type != m.tensors[op.outputs[0]].type)
+    return no("EMBEDDING_LOOKUP table type differs from the output's (the dequantising form)");
+  return GatherBody(m, op, op.inputs[1], op.inputs[0], 0, 0, p, why, batch_ok);
+}
+
+bool CastArgs(const TflModel& m, const TflOperator& op, int* in_type, int* out_type, const char** why) {
+  auto no = [&](const char* w) {
+    if (why) *why = w;
+    return false;
+  };
+  if (op.builtin != kTflCast || op.inputs.empty() || op.inputs[0] < 0 || op.outputs.empty() || op.outputs[0] < 0)
+    return no("CAST needs an input and an output");
+  const TflTensor& in = m.tensors[op.inputs[0]];
+  const TflTensor& out = m.tensors[op.outputs[0]];
+  auto code = [](DataType t) {
+    return t == DataType::kUInt8 ? BH_CAST_U8 : t == DataType::kInt32 ? BH_CAST_I32 : t == DataType::kInt64 ? BH_CAST_I64
+           : t == DataType::kFloat32 ? BH_CAST_F32 : 0;
+  };
+  if ((IsQ8(in.type) && HasQ(in)) || (IsQ8(out.type) && HasQ(out)))
+    return no("CAST of a quantized 8-bit tensor (QUANTIZE / DEQUANTIZE convert those)");
+  if (!code(in.type) || !code(out.type)) return no("CAST types must be uint8, int32, int64 or float32");
+  if (out.num_elements() != in.num_elements()) return no("CAST output size differs from the input's");
+  if (in_type) *in_type = code(in.type);
+  if (out_type) *out_type = code(out.type);
+  return true;
+}
+
+bool TanhArgs(const TflModel& m, const TflOperator& op, bool* is_float, const char** why) {
+  auto no = [&](const char* w) {
+    if (why) *why = w;
+    return false;
+  };
+  if (op.builtin != kTflTanh || op.inputs.empty() || op.inputs[0] < 0 || op.outputs.empty() || op.outputs[0] < 0)
+    return no("TANH needs an input and an output");
+  const TflTensor& in = m.tensors[op.inputs[0]];
+  const TflTensor& out = m.tensors[op.outputs[0]];
+  const bool f32 = in.type == DataType::kFloat32;
+  if (!f32 && !IsQ8(in.type)) return no("TANH: int8, uint8 and float32 only");
+  if (out.type != in.type) return no("TANH output type differs from the input's");
+  if (out.num_elements() != in.num_elements()) return no("TANH output size differs from the input's");
+  if (!f32 && (!HasQ(in) || !HasQ(out))) return no("TANH: missing quantization");
+  if (is_float) *is_float = f32;
   return true;
 }
 

@@ -223,6 +223,26 @@ bool ReindexArgs(const TflModel& m, const TflOperator& op, int oi, bh_reindex_pa
 // false, *why names what keeps it from batching.
 bool GatherArgs(const TflModel& m, const TflOperator& op, bh_gather_params* p, const char** why = nullptr,
                 bool* batch_ok = nullptr);
+// EMBEDDING_LOOKUP (embedding_lookup.cc): inputs (ids, table); GATHER's map
+// with axis 0 and the operands exchanged, through the same body - the same
+// refusals (their reasons say GATHER), the same out-of-range rule, the same
+// job-batch rule.  A table whose type differs from the output's (TFLite's
+// dequantising form) is refused.
+bool EmbeddingLookupArgs(const TflModel& m, const TflOperator& op, bh_gather_params* p, const char** why = nullptr,
+                         bool* batch_ok = nullptr);
+// (params, indices) operand positions of a GATHER / an EMBEDDING_LOOKUP
+inline void GatherOperands(const TflOperator& op, int* params, int* indices) {
+  *params = op.builtin == kTflEmbeddingLookup ? 1 : 0;
+  *indices = 1 - *params;
+}
+// CAST (cast.cc): the BH_CAST_* codes of the input and output tensors' types (uint8, int32, int64, float32; the
+// options are not read), equal element counts.  A quantised 8-bit tensor (one that has scales) is refused:
+// its values are QUANTIZE's / DEQUANTIZE's to convert.  Elementwise: job batching needs no rule of its own.
+bool CastArgs(const TflModel& m, const TflOperator& op, int* in_type = nullptr, int* out_type = nullptr,
+              const char** why = nullptr);
+// TANH (activations.cc): int8 / uint8 with quantisation (a 256-entry table,
+// TanhTable) or float32 (BH_UNARY_TANH); elementwise, equal sizes and types
+bool TanhArgs(const TflModel& m, const TflOperator& op, bool* is_float = nullptr, const char** why = nullptr);
 
 // PACK (pack.cc; np.stack): the bh_concat launch of its inputs - outer the
 // product of the dims before the axis, row[k] the bytes of one input's

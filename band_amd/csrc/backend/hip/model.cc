@@ -99,6 +99,12 @@ absl::Status HipModel::CloneWithJobBatch(int batch, std::unique_ptr<HipModel>* o
       if (ex::GatherArgs(desc_, op, nullptr, &why, &batch_ok) && !batch_ok)
         return absl::InternalError(std::string("job batching: GATHER with ") + why);
     }
+    if (op.builtin == kTflEmbeddingLookup) {  // GATHER's rule: a constant table, runtime ids
+      bool batch_ok = false;
+      const char* why = "";
+      if (ex::EmbeddingLookupArgs(desc_, op, nullptr, &why, &batch_ok) && !batch_ok)
+        return absl::InternalError(std::string("job batching: EMBEDDING_LOOKUP with ") + why);
+    }
     if (op.builtin == kTflPack) {
       int axis = -1;
       if (ex::PackArgs(desc_, op, nullptr, nullptr, &axis) && axis == 0)

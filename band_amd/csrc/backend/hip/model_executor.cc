@@ -239,6 +239,18 @@ bool HipModelExecutor::GpuSupports(const TflModel& m, const TflOperator& op, std
       const char* w = "";
       return GatherArgs(m, op, nullptr, &w) ? true : no(w);
     }
+    case kTflEmbeddingLookup: {
+      const char* w = "";
+      return EmbeddingLookupArgs(m, op, nullptr, &w) ? true : no(w);
+    }
+    case kTflTanh: {
+      const char* w = "";
+      return TanhArgs(m, op, nullptr, &w) ? true : no(w);
+    }
+    case kTflCast: {
+      const char* w = "";
+      return CastArgs(m, op, nullptr, nullptr, &w) ? true : no(w);
+    }
     case kTflPack: {
       const char* w = "";
       return PackArgs(m, op, nullptr, &w) ? true : no(w);
@@ -665,11 +677,16 @@ constexpr KindCalls kCalls[] = {
     {Launch::kCopy,
      [](const Launch& l, bh_stream_t s) {
        const CopyArgs& c = l.as<CopyArgs>();
+       if (c.cast_to) {
+         const bh_cast_params p{c.cast_from, c.cast_to, c.count, c.src, c.dst};
+         return bh_cast(&p, s);
+       }
        return c.src != c.dst ? bh_copy_d2d(c.dst, c.src, c.bytes, s) : 0;
      },
      [](const Launch& l, CpuPool&) {
        const CopyArgs& c = l.as<CopyArgs>();
-       if (c.src != c.dst) std::memmove(c.dst, c.src, c.bytes);
+       if (c.cast_to) CpuCast(bh_cast_params{c.cast_from, c.cast_to, c.count, c.src, c.dst});
+       else if (c.src != c.dst) std::memmove(c.dst, c.src, c.bytes);
      }},
     {Launch::kIrb, Dev<bh_irb_i8>, nullptr},
     {Launch::kChain, Dev<bh_chain_i8>, nullptr},

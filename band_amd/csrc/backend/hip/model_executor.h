@@ -230,8 +230,8 @@ class HipModelExecutor : public interface::IModelExecutor, public IJobBatching {
   // result folded into that launch's epilogue
   void FuseLayerNormF32(const HipModel& model, PreparedSubgraph* sg);
   void FoldLayerNormQuant(const HipModel& model, PreparedSubgraph* sg);
-  // int8 BATCH_MATMUL(adj_y) -> SOFTMAX -> BATCH_MATMUL into one bh_attention_i8
-  // launch that reads and writes through the head TRANSPOSEs around it
+  // int8 BATCH_MATMUL(adj_y) -> [ADD of an int8 mask / bias] -> SOFTMAX -> BATCH_MATMUL into one
+  // bh_attention_i8 launch that reads and writes through the head TRANSPOSEs around it
   void FuseAttention(const HipModel& model, PreparedSubgraph* sg);
   // independent small convs (detector / pose heads) deferred past later
   // launches that do not touch them and issued as one conv_group launch

@@ -184,6 +184,20 @@ void LogisticTable(bool is_signed, float in_scale, int32_t in_zp, float out_scal
   }
 }
 
+// activations.cc's 8-bit TANH as the LOGISTIC above: tanhf of the dequantised value, round, zero point, clamp
+// (restated from memory of PopulateLookupTable; unpinned against a TFLite build)
+void TanhTable(bool is_signed, float in_scale, int32_t in_zp, float out_scale, int32_t out_zp, uint8_t table[256]) {
+  const float inverse_scale = 1.0f / out_scale;
+  const int32_t minval = is_signed ? -128 : 0, maxval = is_signed ? 127 : 255;
+  for (int32_t val = minval; val <= maxval; ++val) {
+    const float dequantized = in_scale * static_cast<float>(val - in_zp);
+    const float transformed = std::tanh(dequantized);
+    const float rescaled = std::round(transformed * inverse_scale);
+    const int32_t quantized = static_cast<int32_t>(rescaled + static_cast<float>(out_zp));
+    table[static_cast<uint8_t>(val)] = static_cast<uint8_t>(Clamp(quantized, minval, maxval));
+  }
+}
+
 void GeluTable(bool is_signed, bool approximate, float in_scale, int32_t in_zp, float out_scale, int32_t out_zp,
                uint8_t table[256]) {
   const float inverse_scale = 1.0f / out_scale;

@@ -60,6 +60,7 @@ void RequantizeTable(bool in_signed, float in_scale, int32_t in_zp, bool out_sig
 void ReluTable(bool is_signed, float in_scale, int32_t in_zp, float out_scale, int32_t out_zp, float act_min,
                float act_max, bool act_max_inf, uint8_t table[256]);
 // activations.cc PopulateLookupTable<T> with 1 / (1 + exp(-x))
+void TanhTable(bool is_signed, float in_scale, int32_t in_zp, float out_scale, int32_t out_zp, uint8_t table[256]);
 void LogisticTable(bool is_signed, float in_scale, int32_t in_zp, float out_scale, int32_t out_zp,
                    uint8_t table[256]);
 // activations.cc PopulateLookupTable<T> with GELU (GeluOptions.approximate:

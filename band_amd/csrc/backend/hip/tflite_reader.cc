@@ -57,6 +57,9 @@ const char* TflBuiltinName(int c) {
     case kTflBatchMatMul: return "BATCH_MATMUL";
     case kTflGelu: return "GELU";
     case kTflGather: return "GATHER";
+    case kTflTanh: return "TANH";
+    case kTflCast: return "CAST";
+    case kTflEmbeddingLookup: return "EMBEDDING_LOOKUP";
     case kTflTile: return "TILE";
     case kTflPack: return "PACK";
     case kTflUnpack: return "UNPACK";

@@ -41,6 +41,12 @@ enum TflBuiltin : int {
   // GatherOptions: slots 0-1 axis, batch_dims; PackOptions: slots 0-1
   // values_count, axis; UnpackOptions: slots 0-1 num, axis; TILE has no fields
   kTflGather = 36, kTflTile = 69, kTflPack = 83, kTflUnpack = 88,
+  // TANH and EMBEDDING_LOOKUP (inputs: ids, table) have no option fields; the
+  // two codes are from memory of schema.fbs (parity-unpinned, as the four above)
+  kTflTanh = 28, kTflEmbeddingLookup = 7,
+  // CastOptions: slots 0-1 in_data_type, out_data_type (TensorType); unread, the tensors' types decide.  Code and
+  // slots from memory of schema.fbs (parity-unpinned)
+  kTflCast = 53,
 };
 
 const char* TflBuiltinName(int code);

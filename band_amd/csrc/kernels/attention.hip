@@ -43,15 +43,28 @@
 // zero point is not 0.  The epilogue stores through the output strides, a dword
 // per lane where out_dim % 4 == 0 and base and strides are multiples of 4.
 //
+// The masked form (BIAS, "attention_bias_i8_kernel"): an int8 bias read by
+// strides (a padding mask, a causal mask, a position bias) is ADDed to the
+// scores in phase 1, between attn_requant4 and the strip: the lane's four bias
+// bytes for its row and keys - one dword, four bytes or one byte replicated,
+// clamped to the last row and key like the Q and K reads - are loaded ahead of
+// the round's MFMAs and meet the four score bytes in TFLite's int8 ADD
+// (residual_add.hpp, the direct form: no table, no LDS, no barrier of its
+// own).  Phases 2 and 3 do not know of it; the stored bytes are those of the
+// four launches with bh_eltwise_i8 (BH_ELT_ADD) between the first two.
+//
 // LDS: the strip (64 pitch), V's staging (128 lines of kBmmPitch) and the exp
 // table (1 KB), sized per launch: 11 KB + 64 pitch, i.e. 28 KB at keys 196 and
 // 76 KB at keys 1024 (BH_ATTENTION_MAX_KEYS), above 64 KB with the dynamic-LDS
 // attribute set once per process and device.
 #include <climits>
+#include <type_traits>
 
+#include "band_hip_attention_shared.h"
 #include "bmm_frag.hpp"
 #include "common.hpp"
 #include "conv_epilogue.hpp"
+#include "residual_add.hpp"
 
 namespace bh {
 
@@ -91,9 +104,38 @@ struct AttnArgs {
   void* out;
 };
 
-// VEC: fragment unit of Q and K
-template <int VEC>
-__global__ __launch_bounds__(256) void attention_i8_kernel(AttnArgs p) {
+// the masked form's arguments: the bias by strides (0 broadcasts) and the ADD's constants
+struct AttnBiasArgs : AttnArgs {
+  const void* bias;
+  int32_t bias_bstride[2], bias_row_stride, bias_key_stride;
+  int32_t bias_vec4;  // dword loads: key stride 1, keys % 4 == 0, base and strides multiples of 4
+  int32_t add_scores_operand;
+  bh_attention_add add;
+};
+
+// the lane's four bias bytes for keys kb .. kb + 3 of its row, clamped to the last key as the K reads are
+__device__ __forceinline__ uint32_t attn_bias4(const AttnBiasArgs& p, const uint8_t* brow, int kb, int keys) {
+  if (p.bias_key_stride == 0) return splat_byte(brow[0]);
+  if (p.bias_vec4) return *(const uint32_t*)(brow + min(kb, keys - 4));
+  uint32_t w = 0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) w |= (uint32_t)brow[min(kb + r, keys - 1)] << (8 * r);
+  return w;
+}
+
+// ADD(score, bias) on the four bytes of a lane's dword
+__device__ __forceinline__ uint32_t attn_add4(const ResidualAdd& A, uint32_t scores, uint32_t bias) {
+  uint32_t packed = 0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    packed |= ((uint32_t)residual_add(A, sbyte(scores, r), sbyte(bias, r)) & 0xffu) << (8 * r);
+  return packed;
+}
+
+// VEC: fragment unit of Q and K; BIAS: the masked form, ADD(scores, bias) between the first product's
+// requantisation and the strip ("attention_bias_i8_kernel" in launch lists)
+template <int VEC, bool BIAS>
+__global__ __launch_bounds__(256) void attention_i8_kernel(std::conditional_t<BIAS, AttnBiasArgs, AttnArgs> p) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int keys = p.keys, D = p.head_dim, N = p.out_dim, M = p.rows;
   const int pitch = attn_pitch(keys);
@@ -132,8 +174,19 @@ __global__ __launch_bounds__(256) void attention_i8_kernel(AttnArgs p) {
     }
     const int32_t kzz = D * p.qk.lhs_zp * p.qk.rhs_zp;
     const ChanQ cq = chan_q(p.qk.mult, p.qk.shift, p.qk.out_zp);
+    const uint8_t* brow = nullptr;
+    if constexpr (BIAS)
+      brow = (const uint8_t*)p.bias + (long)b0 * p.bias_bstride[0] + (long)b1 * p.bias_bstride[1] +
+             (long)min(m0 + r16, M - 1) * p.bias_row_stride;
     for (int n0 = 0; n0 < keys; n0 += 16 * kAttnTiles) {
       v4i acc[kAttnTiles], cs[kAttnTiles];
+      uint32_t bw[kAttnTiles];
+      if constexpr (BIAS) {
+        // issued ahead of the round's K loads and MFMAs, met after them
+#pragma unroll
+        for (int t = 0; t < kAttnTiles; ++t)
+          bw[t] = n0 + 16 * t < keys ? attn_bias4(p, brow, n0 + 16 * t + 4 * q, keys) : 0u;
+      }
 #pragma unroll
       for (int t = 0; t < kAttnTiles; ++t) {
         acc[t] = zero;
@@ -153,8 +206,10 @@ __global__ __launch_bounds__(256) void attention_i8_kernel(AttnArgs p) {
       for (int t = 0; t < kAttnTiles; ++t) {
         if (n0 + 16 * t >= keys) continue;
         // keys past `keys` in the last tile hold a clamped column's score: phase 2 overwrites them with 0
-        *(uint32_t*)(myrow + n0 + 16 * t + 4 * q) = (p.fast & 1) ? attn_requant4<true>(acc[t], rs, cs[t], p.qk, kzz, cq)
-                                                               : attn_requant4<false>(acc[t], rs, cs[t], p.qk, kzz, cq);
+        uint32_t s4 = (p.fast & 1) ? attn_requant4<true>(acc[t], rs, cs[t], p.qk, kzz, cq)
+                                   : attn_requant4<false>(acc[t], rs, cs[t], p.qk, kzz, cq);
+        if constexpr (BIAS) s4 = attn_add4(residual_of(p.add, p.add_scores_operand), s4, bw[t]);
+        *(uint32_t*)(myrow + n0 + 16 * t + 4 * q) = s4;
       }
     }
   }
@@ -252,41 +307,15 @@ __global__ __launch_bounds__(256) void attention_i8_kernel(AttnArgs p) {
   }
 }
 
-// nullptr = runnable
-static const char* attn_check(const bh_attention_params* p) {
-  if (!p) return "null parameter block";
-  if (!p->q || !p->k || !p->v || !p->out || !p->table) return "null pointer";
-  if (p->rows <= 0 || p->keys <= 0 || p->head_dim <= 0 || p->out_dim <= 0 || p->batch[0] <= 0 || p->batch[1] <= 0)
-    return "non-positive extent";
-  if (p->keys > BH_ATTENTION_MAX_KEYS) return "keys above 1024 (the LDS strip of the scores)";
-  if (p->head_dim > BH_ATTENTION_MAX_DIM) return "head_dim above 128 (the q fragments a wave keeps)";
-  if (p->out_dim > BH_ATTENTION_MAX_DIM) return "out_dim above 128 (eight accumulator tiles per wave)";
-  if (p->batch[0] > 65535 || p->batch[1] > 65535) return "a batch dim above 65535 (grid y / z)";
-  const int64_t* bs[4] = {p->q_bstride, p->k_bstride, p->v_bstride, p->out_bstride};
-  const int64_t rstr[4] = {p->q_row_stride, p->k_row_stride, p->v_row_stride, p->out_row_stride};
-  const int64_t istr[4] = {p->q_inner_stride, p->k_inner_stride, p->v_inner_stride, p->out_inner_stride};
-  const int64_t nrow[4] = {p->rows, p->keys, p->keys, p->rows};
-  const int64_t ncol[4] = {p->head_dim, p->head_dim, p->out_dim, p->out_dim};
-  for (int i = 0; i < 4; ++i)
-    if (bs[i][0] < 0 || bs[i][1] < 0 || rstr[i] < 0 || istr[i] < 0) return "negative stride";
-  for (int i = 0; i < 4; ++i)
-    if (istr[i] != 1) return "non-unit inner stride";
-  for (int i = 0; i < 4; ++i) {
-    const long long span = (p->batch[0] - 1LL) * bs[i][0] + (p->batch[1] - 1LL) * bs[i][1] + (nrow[i] - 1LL) * rstr[i] +
-                           (ncol[i] - 1LL);
-    if (span >= INT32_MAX) return "a tensor of 2^31 or more elements";
-  }
-  if (((p->rows + kAttnRows - 1LL) / kAttnRows) > INT32_MAX) return "a tensor of 2^31 or more elements";
-  for (const bh_attention_quant* z : {&p->qk, &p->pv})
-    if (z->shift > 30 || z->shift < -31 || z->mult < 0) return "multiplier / shift out of range";
-  return nullptr;
-}
+// nullptr = runnable (band_hip_attention_shared.h: host code, also run under sanitizers on its own)
+static const char* attn_check(const bh_attention_params* p) { return bh_attention_why(p); }
+static_assert(kAttnRows == BH_ATTENTION_ROWS, "the check's rows per workgroup");
 
 static size_t attn_lds_bytes(int keys) { return (size_t)kAttnRows * attn_pitch(keys) + kAttnStageBytes + 256 * sizeof(float); }
 static_assert(kAttnRows * (BH_ATTENTION_MAX_KEYS + 16) + kAttnStageBytes + 1024 <= 160 * 1024,
               "the largest strip must fit the CU's LDS");
 
-template <int VEC>
+template <int VEC, bool BIAS>
 static void attn_launch(const bh_attention_params& p, int fast, hipStream_t s) {
   const size_t lds = attn_lds_bytes(p.keys);
   if (lds > 64 * 1024) {
@@ -294,13 +323,13 @@ static void attn_launch(const bh_attention_params& p, int fast, hipStream_t s) {
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (opted_device != dev) {
-      (void)hipFuncSetAttribute((const void*)attention_i8_kernel<VEC>, hipFuncAttributeMaxDynamicSharedMemorySize,
+      (void)hipFuncSetAttribute((const void*)attention_i8_kernel<VEC, BIAS>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 160 * 1024);
       opted_device = dev;
     }
   }
   const dim3 grid((unsigned)((p.rows + kAttnRows - 1) / kAttnRows), (unsigned)p.batch[1], (unsigned)p.batch[0]);
-  AttnArgs a{};
+  std::conditional_t<BIAS, AttnBiasArgs, AttnArgs> a{};
   a.rows = p.rows; a.keys = p.keys; a.head_dim = p.head_dim; a.out_dim = p.out_dim;
   for (int d = 0; d < 2; ++d) {
     const bool walk = p.batch[d] > 1;
@@ -316,7 +345,27 @@ static void attn_launch(const bh_attention_params& p, int fast, hipStream_t s) {
   a.qk = p.qk; a.pv = p.pv;
   a.sm_out_scale = p.sm_out_scale; a.sm_out_zp = p.sm_out_zp; a.fast = fast;
   a.table = p.table; a.q = p.q; a.k = p.k; a.v = p.v; a.out = p.out;
-  BH_LAUNCH((attention_i8_kernel<VEC>), grid, dim3(256), lds, s, a);
+  if constexpr (BIAS) {
+    a.bias = p.bias;
+    for (int d = 0; d < 2; ++d) a.bias_bstride[d] = p.batch[d] > 1 ? (int32_t)p.bias_bstride[d] : 0;
+    a.bias_row_stride = p.rows > 1 ? (int32_t)p.bias_row_stride : 0;
+    a.bias_key_stride = p.keys > 1 ? (int32_t)p.bias_key_stride : 0;
+    // a dword per lane and tile: keys % 4 == 0 keeps the clamped last dword inside the row
+    const uintptr_t al = (uintptr_t)p.bias | (uintptr_t)a.bias_bstride[0] | (uintptr_t)a.bias_bstride[1] |
+                         (uintptr_t)a.bias_row_stride | (uintptr_t)p.keys;
+    a.bias_vec4 = a.bias_key_stride == 1 && al % 4 == 0 && !(p.kernel_hint & BH_ATTN_BYTES);
+    a.add_scores_operand = p.add_scores_operand;
+    a.add = p.add;
+  }
+  BH_LAUNCH((attention_i8_kernel<VEC, BIAS>), grid, dim3(256), lds, s, a);
+}
+
+template <bool BIAS>
+static void attn_launch_vec(const bh_attention_params& p, int vec, int fast, hipStream_t s) {
+  if (vec == 16) attn_launch<16, BIAS>(p, fast, s);
+  else if (vec == 8) attn_launch<8, BIAS>(p, fast, s);
+  else if (vec == 4) attn_launch<4, BIAS>(p, fast, s);
+  else attn_launch<1, BIAS>(p, fast, s);
 }
 
 }  // namespace bh
@@ -331,7 +380,7 @@ extern "C" int bh_attention_i8_check(const bh_attention_params* p) {
 }
 
 extern "C" const char* bh_attention_i8_kernel(const bh_attention_params* p) {
-  return bh::attn_check(p) ? "" : "attention_i8_kernel";
+  return bh::attn_check(p) ? "" : (p->bias ? "attention_bias_i8_kernel" : "attention_i8_kernel");
 }
 
 extern "C" size_t bh_attention_i8_lds_bytes(const bh_attention_params* p) {
@@ -351,9 +400,7 @@ extern "C" int bh_attention_i8(const bh_attention_params* pp, bh_stream_t stream
   const int fast = (p.qk.requant_fast != 0 && bh_conv_requant_fast_ok(&p.qk.mult, &p.qk.shift, 1, p.head_dim, 0) ? 1 : 0) |
                    (p.pv.requant_fast != 0 && bh_conv_requant_fast_ok(&p.pv.mult, &p.pv.shift, 1, p.keys, 0) ? 2 : 0);
   hipStream_t s = (hipStream_t)stream;
-  if (vec == 16) attn_launch<16>(p, fast, s);
-  else if (vec == 8) attn_launch<8>(p, fast, s);
-  else if (vec == 4) attn_launch<4>(p, fast, s);
-  else attn_launch<1>(p, fast, s);
-  return bh_check_launch("attention_i8_kernel");
+  if (p.bias) attn_launch_vec<true>(p, vec, fast, s);
+  else attn_launch_vec<false>(p, vec, fast, s);
+  return bh_check_launch(p.bias ? "attention_bias_i8_kernel" : "attention_i8_kernel");
 }

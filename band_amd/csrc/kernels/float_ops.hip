@@ -204,6 +204,8 @@ __global__ __launch_bounds__(256) void unary_f32_kernel(int kind, const float* i
     out[i] = 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));
   } else if (kind == BH_UNARY_GELU_TANH) {
     out[i] = 0.5f * x * (1.0f + tanhf(0.79788456080286535588f * x * (1.0f + 0.044715f * x * x)));
+  } else if (kind == BH_UNARY_TANH) {
+    out[i] = tanhf(x);
   } else {
     out[i] = kind == BH_UNARY_LOGISTIC ? 1.0f / (1.0f + expf(-x)) : kind == BH_UNARY_RSQRT ? 1.0f / sqrtf(x)
                                                                                         : clampf(x, lo, hi);
@@ -308,7 +310,7 @@ extern "C" int bh_pool_f32(const bh_pool_f32_params* pp, bh_stream_t s) {
 }
 
 extern "C" int bh_unary_f32(int kind, const float* in, float* out, long n, float lo, float hi, bh_stream_t s) {
-  if (!in || !out || n < 0 || kind < BH_UNARY_CLAMP || kind > BH_UNARY_GELU_TANH) {
+  if (!in || !out || n < 0 || kind < BH_UNARY_CLAMP || (kind > BH_UNARY_GELU_TANH && kind != BH_UNARY_TANH)) {
     bh_set_last_error("bh_unary_f32: invalid parameters");
     return BH_EINVAL;
   }

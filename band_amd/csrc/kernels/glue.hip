@@ -16,6 +16,7 @@
 //   * SOFTMAX (8-bit, lookup-table path) -> host-built float exp table; the
 //     per-row sum runs sequentially in TFLite's order, so the float result is
 //     the same.
+#include "band_hip_cast_shared.h"
 #include "common.hpp"
 
 namespace bh {
@@ -60,6 +61,73 @@ __global__ __launch_bounds__(256) void quantize_f32_kernel(const float* __restri
                                                            long n, float scale, int32_t zp, int32_t lo, int32_t hi) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i < n) out[i] = (uint8_t)clamp_i32((int32_t)roundf(__fdiv_rn(in[i], scale)) + zp, lo, hi);
+}
+
+// ---- CAST ----------------------------------------------------------------------
+// element i of a pointer aligned to 4 bytes at least: the 8-byte types as two dwords
+template <class T>
+__device__ __forceinline__ T cast_ld(const void* p, long i) {
+  if constexpr (sizeof(T) == 8) {
+    const uint32_t* w = (const uint32_t*)p + 2 * i;
+    return (T)((uint64_t)w[0] | ((uint64_t)w[1] << 32));
+  } else {
+    return ((const T*)p)[i];
+  }
+}
+template <class T>
+__device__ __forceinline__ void cast_st(void* p, long i, T v) {
+  if constexpr (sizeof(T) == 8) {
+    uint32_t* w = (uint32_t*)p + 2 * i;
+    w[0] = (uint32_t)(uint64_t)v;
+    w[1] = (uint32_t)((uint64_t)v >> 32);
+  } else {
+    ((T*)p)[i] = v;
+  }
+}
+template <class T>
+struct alignas(sizeof(T) * 4 < 16 ? sizeof(T) * 4 : 16) CastVec4 {
+  T v[4];
+};
+
+// VEC4: both pointers aligned to four elements (at most 16 bytes): a lane converts four elements through one
+// 4- / 16-byte unit a side (two 16-byte units for int64), the n % 4 elements of the tail one per lane of the
+// first workgroup; else one element per lane
+template <class S, class D, bool VEC4>
+__global__ __launch_bounds__(256) void cast_kernel(const void* __restrict__ in, void* __restrict__ out, long n) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if constexpr (VEC4) {
+    const long n4 = n >> 2;
+    if (i < n4) {
+      const CastVec4<S> s = ((const CastVec4<S>*)in)[i];
+      CastVec4<D> d;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) d.v[k] = bh_cast_one<S, D>(s.v[k]);
+      ((CastVec4<D>*)out)[i] = d;
+    }
+    const long t = 4 * n4 + i;  // (i < 4 here only in the first workgroup)
+    if (i < 4 && t < n) cast_st<D>(out, t, bh_cast_one<S, D>(cast_ld<S>(in, t)));
+  } else {
+    if (i < n) cast_st<D>(out, i, bh_cast_one<S, D>(cast_ld<S>(in, i)));
+  }
+}
+
+template <class S, class D>
+static void cast_launch(const bh_cast_params& p, hipStream_t s) {
+  const uintptr_t as = sizeof(S) * 4 < 16 ? sizeof(S) * 4 : 16, ad = sizeof(D) * 4 < 16 ? sizeof(D) * 4 : 16;
+  const bool vec4 = p.count >= 4 && (uintptr_t)p.input % as == 0 && (uintptr_t)p.output % ad == 0;
+  if (vec4)
+    BH_LAUNCH((cast_kernel<S, D, true>), dim3((unsigned)(((p.count >> 2) + 255) / 256)), dim3(256), 0, s, p.input, p.output, p.count);
+  else
+    BH_LAUNCH((cast_kernel<S, D, false>), dim3((unsigned)((p.count + 255) / 256)), dim3(256), 0, s, p.input, p.output, p.count);
+}
+template <class S>
+static void cast_launch_from(const bh_cast_params& p, hipStream_t s) {
+  switch (p.out_type) {
+    case BH_CAST_U8: return cast_launch<S, uint8_t>(p, s);
+    case BH_CAST_I32: return cast_launch<S, int32_t>(p, s);
+    case BH_CAST_I64: return cast_launch<S, int64_t>(p, s);
+    default: return cast_launch<S, float>(p, s);
+  }
 }
 
 // ---- concatenation -----------------------------------------------------------
@@ -522,6 +590,27 @@ extern "C" int bh_quantize_f32(const float* in, void* out, long n, float scale, 
   BH_LAUNCH(bh::quantize_f32_kernel, dim3(bh::blocks(n)), dim3(256), 0, (hipStream_t)s, in, (uint8_t*)out,
                      n, scale, zp, out_signed ? -128 : 0, out_signed ? 127 : 255);
   return bh_check_launch("quantize_f32_kernel");
+}
+
+extern "C" int bh_cast(const bh_cast_params* pp, bh_stream_t s) {
+  if (const char* why = bh_cast_why(pp)) {
+    static thread_local char msg[160];
+    snprintf(msg, sizeof(msg), "bh_cast: %s", why);
+    bh_set_last_error(msg);
+    return BH_EINVAL;
+  }
+  if (pp->count == 0) return 0;
+  if (pp->count >= (1L << 31) * 256) {
+    bh_set_last_error("bh_cast: count above 2^39");
+    return BH_EINVAL;
+  }
+  switch (pp->in_type) {
+    case BH_CAST_U8: bh::cast_launch_from<uint8_t>(*pp, (hipStream_t)s); break;
+    case BH_CAST_I32: bh::cast_launch_from<int32_t>(*pp, (hipStream_t)s); break;
+    case BH_CAST_I64: bh::cast_launch_from<int64_t>(*pp, (hipStream_t)s); break;
+    default: bh::cast_launch_from<float>(*pp, (hipStream_t)s); break;
+  }
+  return bh_check_launch("cast_kernel");
 }
 
 extern "C" int bh_concat(const bh_concat_params* pp, bh_stream_t s) {

@@ -4,8 +4,8 @@
 // byte).  Each operand is rescaled on its own,
 //   s = MultiplyByQuantizedMultiplierSmallerThanOneExp((q + off) << left_shift, mult, shift)
 // and the sum is requantised, offset and clamped.  Every kernel that folds
-// the ADD states it through this header; the two constructors below are the
-// only places that name the parameter blocks' add_* fields.
+// the ADD states it through this header; the constructors below are the only
+// places that name the parameter blocks' add fields.
 #pragma once
 
 #include "common.hpp"
@@ -27,6 +27,15 @@ __device__ __forceinline__ ResidualAdd residual_of(const bh_conv_params& p) {
 __device__ __forceinline__ ResidualAdd residual_of(const bh_irb_params& p) {
   return {p.add_p_off,  p.add_x_off,   p.add_o_off,  p.add_left_shift, p.add_p_mult,  p.add_p_shift,
           p.add_x_mult, p.add_x_shift, p.add_o_mult, p.add_o_shift,    p.add_act_min, p.add_act_max};
+}
+// the attention core's masked form: y is the score, r the bias byte; the block names the ADD's operands a and
+// b in the order the op lists them, and scores_operand says which of the two the scores are
+__device__ __forceinline__ ResidualAdd residual_of(const bh_attention_add& p, int scores_operand) {
+  if (scores_operand == 0)
+    return {p.a_off,  p.b_off,   p.o_off,  p.left_shift, p.a_mult,  p.a_shift,
+            p.b_mult, p.b_shift, p.o_mult, p.o_shift,    p.act_min, p.act_max};
+  return {p.b_off,  p.a_off,   p.o_off,  p.left_shift, p.b_mult,  p.b_shift,
+          p.a_mult, p.a_shift, p.o_mult, p.o_shift,    p.act_min, p.act_max};
 }
 
 // the rescaling of y / of r

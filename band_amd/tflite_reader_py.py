@@ -39,6 +39,7 @@ OPTION_FIELDS = {
     51: [],                                                                     # Tile
     59: [(0, "i"), (1, "i")],                                                   # Pack (values_count, axis)
     64: [(0, "i"), (1, "i")],                                                   # Unpack (num, axis)
+    37: [(0, "b"), (1, "b")],                                                   # Cast (in_data_type, out_data_type)
 }
 
 

@@ -31,7 +31,9 @@ OPC = dict(ADD=0, AVERAGE_POOL_2D=1, CONCATENATION=2, CONV_2D=3, DEPTHWISE_CONV_
            DEPTH_TO_SPACE=5, SPACE_TO_DEPTH=26, TRANSPOSE=39, STRIDED_SLICE=45, SPLIT=49, SLICE=65, SPLIT_V=102,
            BATCH_MATMUL=126,
            MEAN=40, RSQRT=76, SQUARED_DIFFERENCE=99, GELU=150,
-           GATHER=36, TILE=69, PACK=83, UNPACK=88)
+           GATHER=36, TILE=69, PACK=83, UNPACK=88,
+           # from memory of schema.fbs, like the four above; neither has an options table
+           TANH=28, EMBEDDING_LOOKUP=7, CAST=53)
 # BuiltinOptions union indices
 OPT = dict(Conv2DOptions=1, DepthwiseConv2DOptions=2, Pool2DOptions=5, FullyConnectedOptions=8,
            SoftmaxOptions=9, ConcatenationOptions=10, AddOptions=11, ReshapeOptions=17,
@@ -45,7 +47,9 @@ OPT = dict(Conv2DOptions=1, DepthwiseConv2DOptions=2, Pool2DOptions=5, FullyConn
            # ... and so are these three
            ReducerOptions=27, SquaredDifferenceOptions=76, GeluOptions=116,
            # ... and these four
-           GatherOptions=23, TileOptions=51, PackOptions=59, UnpackOptions=64)
+           GatherOptions=23, TileOptions=51, PackOptions=59, UnpackOptions=64,
+           # ... and this one (slots 0-1 in_data_type, out_data_type)
+           CastOptions=37)
 
 
 # ---------------------------------------------------------------------------
@@ -424,6 +428,23 @@ class _ReindexOps:
                    Table().set(0, "i", axis).set(1, "i", batch_dims))
         return y
 
+    def cast(self, x, dtype):
+        """CAST to dtype (uint8, int32, int64 or float32) of a tensor without quantisation; the output has none"""
+        shp = list(self.meta[x][0])
+        y = self.mb.tensor(self._name("cast"), shp, dtype)
+        self.meta[y] = (shp, None, None)
+        src = self.mb.tensors[x]["type"]
+        self.mb.op("CAST", [x], [y], OPT["CastOptions"], Table().set(0, "b", src).set(1, "b", NP_TO_SCHEMA[np.dtype(dtype)]))
+        return y
+
+    def embedding_lookup(self, ids, table):
+        """EMBEDDING_LOOKUP: np.take(table, ids, 0) with the operands in TFLite's order (ids first); the output
+        inherits the table's quantisation"""
+        shp = self.meta[table][0]
+        y = self._re_out(table, list(self.meta[ids][0]) + list(shp[1:]))
+        self.mb.op("EMBEDDING_LOOKUP", [ids, table], [y])
+        return y
+
     def pack(self, xs, axis=0):
         """np.stack(xs, axis); the inputs share one shape and, 8-bit, one quantisation"""
         shp = list(self.meta[xs[0]][0])
@@ -697,6 +718,12 @@ class QGraph(_ReindexOps):
         self.mb.op("LOGISTIC", [x], [y])
         return y
 
+    def tanh(self, x):
+        """TANH; the output covers [-1, 1): scale 1 / 128 around the middle of the range"""
+        y = self._like(x, scale=1.0 / 128.0, zp=0 if self.dtype == np.int8 else 128)
+        self.mb.op("TANH", [x], [y])
+        return y
+
     def softmax(self, x, beta=1.0):
         zp = -128 if self.dtype == np.int8 else 0
         y = self._like(x, scale=1.0 / 256.0, zp=zp)
@@ -806,6 +833,15 @@ class QGraph(_ReindexOps):
         q = np.clip(np.round(v / scale) + zp, qmin, qmax).astype(self.dtype)
         t = self.mb.tensor(self._name(kind), list(v.shape), self.dtype, scale=[scale], zero_point=[zp], data=q)
         self.meta[t] = (list(v.shape), scale, zp)
+        return t
+
+    def const_at(self, values, scale, zp, kind="const"):
+        """a constant 8-bit tensor holding the real `values` at a given scale and zero point (saturating)"""
+        v = np.asarray(values, np.float64)
+        qmin, qmax = (-128, 127) if self.dtype == np.int8 else (0, 255)
+        q = np.clip(np.round(v / scale) + zp, qmin, qmax).astype(self.dtype)
+        t = self.mb.tensor(self._name(kind), list(v.shape), self.dtype, scale=[float(scale)], zero_point=[int(zp)], data=q)
+        self.meta[t] = (list(v.shape), float(scale), int(zp))
         return t
 
     def _binary(self, kind, options, a, b, scale, zp, act="NONE"):
@@ -1111,6 +1147,11 @@ class FGraph(_ReindexOps):
         self.mb.op("LOGISTIC", [x], [y])
         return y
 
+    def tanh(self, x):
+        y = self._act(self.meta[x][0])
+        self.mb.op("TANH", [x], [y])
+        return y
+
     def softmax(self, x, beta=1.0):
         y = self._act(self.meta[x][0])
         self.mb.op("SOFTMAX", [x], [y], OPT["SoftmaxOptions"], Table().set(0, "f", float(beta)))
@@ -1291,10 +1332,19 @@ def shufflenet_v1(dtype=np.int8, seed=5, size=224, groups=3, width=1.0, batch=1,
 # BASELINE C3 mix: detection / segmentation / pose heads on MobileNet trunks
 # (synthetic weights, 224x224 inputs - "synthetic 224x224 batches", §8(d))
 # ---------------------------------------------------------------------------
-def _attention(g, x, heads, residual=None):
+MASKED = -10000.0  # what an attention mask adds to the score of a key that must not be seen
+
+
+def _attention(g, x, heads, residual=None, bias=None):
     """One multi-head self-attention block on x [B, T, C] (no LayerNorm): Q, K, V
     projections, per-head softmax(Q K^T / sqrt(D)) V, output projection,
-    residual ADD (with x, or with `residual`: a pre-norm block's input).  The float model's 1 / sqrt(D) leaves no op: it is folded
+    residual ADD (with x, or with `residual`: a pre-norm block's input).
+    `bias`: a tensor that broadcasts to the scores [B, H, T, T] (a padding mask
+    [B, 1, 1, T], a causal mask [1, 1, T, T], a position bias [1, H, T, T]), or
+    a function (g, scores) -> such a tensor; it is ADDed to the scores before
+    the SOFTMAX, and in the 8-bit model the sum keeps the scores' quantisation,
+    so a masked key saturates at the bottom of the range.
+    The float model's 1 / sqrt(D) leaves no op: it is folded
     into the Q projection (its output scale, so its filter scale, is the
     input's over sqrt(D); the fp16 model scales the Q weights), and the scores'
     scale then stands for Q K^T / sqrt(D)."""
@@ -1311,6 +1361,9 @@ def _attention(g, x, heads, residual=None):
     v = g.fully_connected(x, c, keep_num_dims=True)
     q, k, v = [g.transpose(g.reshape(z, [b, t, heads, d]), (0, 2, 1, 3)) for z in (q, k, v)]
     scores = g.batch_matmul(q, k, adj_y=True)            # [B, H, T, T]
+    if bias is not None:
+        bt = bias(g, scores) if callable(bias) else bias
+        scores = g.add_q(scores, bt, g.meta[scores][1], g.meta[scores][2]) if quant else g.add(scores, bt)
     p = g.softmax(scores, beta=1.0)                      # scale 1 / 256, zero point -128
     # a row of P sums to ~256 LSBs, so at V's scale the context is V's weighted mean
     ctx = g.batch_matmul(p, v, out_scale=g.meta[v][1] if quant else None)  # [B, H, T, D]
@@ -1319,8 +1372,37 @@ def _attention(g, x, heads, residual=None):
     return g.add(y, x if residual is None else residual)
 
 
-def attention_block(dtype=np.int8, seed=6, tokens=196, dim=192, heads=3, batch=1, hybrid=None):
-    """One self-attention block on [batch, tokens, dim]: three FULLY_CONNECTED
+def _mask_const(g, values, kind):
+    """an additive attention mask of 0 / MASKED as a constant: 8-bit at scale -MASKED / 255 with 0 at the top of
+    the range, so the two values are the range's two ends"""
+    if isinstance(g, QGraph):
+        return g.const_at(values, -MASKED / 255.0, 127 if g.dtype == np.int8 else 255, kind)
+    return g.const(values, kind)
+
+
+def _attention_bias(kind, tokens, heads):
+    """attention_block's attention_bias as _attention's bias function"""
+    if kind == "causal":
+        # key j is seen from row i when j <= i
+        return lambda g, scores: _mask_const(g, np.triu(np.full((1, 1, tokens, tokens), MASKED), 1), "causal_mask")
+
+    def relative(g, scores):
+        # drawn over the whole 8-bit range at the scores' quantisation (Swin, T5: a learnt table, gathered at
+        # conversion time)
+        if not isinstance(g, QGraph):
+            return g.const(g.rng.normal(0.0, 1.0, (1, heads, tokens, tokens)), "position_bias")
+        _, s, z = g.meta[scores]
+        qmin, qmax = (-128, 127) if g.dtype == np.int8 else (0, 255)
+        q = g.rng.integers(qmin, qmax + 1, (1, heads, tokens, tokens))
+        return g.const_at((q - z) * s, s, z, "position_bias")
+    assert kind == "relative", kind
+    return relative
+
+
+def attention_block(dtype=np.int8, seed=6, tokens=196, dim=192, heads=3, batch=1, hybrid=None, attention_bias=None):
+    """attention_bias: None, "causal" (a constant [1, 1, T, T] mask, 0 on and below the diagonal and MASKED above
+    it) or "relative" (a constant [1, H, T, T] position bias), ADDed to the scores before the SOFTMAX.
+    One self-attention block on [batch, tokens, dim]: three FULLY_CONNECTED
     (keep_num_dims), RESHAPE / TRANSPOSE to [batch, heads, tokens, dim / heads],
     BATCH_MATMUL(adj_y) -> SOFTMAX -> BATCH_MATMUL, TRANSPOSE / RESHAPE back,
     FULLY_CONNECTED, ADD with the input.  dtype float32 (or float16) builds the
@@ -1332,14 +1414,15 @@ def attention_block(dtype=np.int8, seed=6, tokens=196, dim=192, heads=3, batch=1
     else:
         g = QGraph(dtype, seed, "attention_block_%s" % np.dtype(dtype).name)
     x = g.input([batch, tokens, dim], scale=0.05)
-    g.output(_attention(g, x, heads))
+    g.output(_attention(g, x, heads, bias=_attention_bias(attention_bias, tokens, heads) if attention_bias else None))
     return g.build()
 
 
-def _encoder(g, x, heads, hidden, layer_norm=True, mlp=True):
+def _encoder(g, x, heads, hidden, layer_norm=True, mlp=True, bias=None):
     """The pre-norm transformer block on x [B, T, C]: x + attention(LN(x)),
-    then the same around the MLP (FULLY_CONNECTED -> GELU -> FULLY_CONNECTED)."""
-    y = _attention(g, g.layer_norm(x) if layer_norm else x, heads, residual=x)
+    then the same around the MLP (FULLY_CONNECTED -> GELU -> FULLY_CONNECTED).
+    `bias`: _attention's."""
+    y = _attention(g, g.layer_norm(x) if layer_norm else x, heads, residual=x, bias=bias)
     if mlp:
         y = g.mlp(g.layer_norm(y) if layer_norm else y, hidden, residual=y)
     return y
@@ -1388,8 +1471,31 @@ def vit_tiny(dtype=np.int8, seed=7, size=224, dim=192, heads=3, blocks=2, batch=
     return g.build()
 
 
+def _padding_mask(g, batch, tokens):
+    """A BERT attention mask as the converter leaves it: a second int32 input [batch, tokens] (1: a token, 0:
+    padding), CAST to float32, SUB (1 - m), MUL by MASKED; in the 8-bit model a QUANTIZE to 8 bits at scale -MASKED /
+    255 with 0 at the top of the range; RESHAPE to [batch, 1, 1, tokens].  The float32 ops of the 8-bit model are
+    written here by hand (QGraph's SUB / MUL are the 8-bit ones)."""
+    m = g.input([batch, tokens], dtype=np.int32)
+    f = g.cast(m, np.float32)
+    if not isinstance(g, QGraph):
+        y = g.mul(g.sub(g.const([1.0], "one"), f), g.const([MASKED], "masked"))
+        return g.reshape(y, [batch, 1, 1, tokens])
+
+    def f32(kind, options, a, value, swap):
+        c = g.mb.tensor(g._name("mask_const"), [1], np.float32, data=np.array([value], np.float32))
+        y = g.mb.tensor(g._name("mask_f32"), [batch, tokens], np.float32)
+        g.meta[y] = ([batch, tokens], None, None)
+        g.mb.op(kind, [c, a] if swap else [a, c], [y], OPT[options], act_options("NONE"))
+        return y
+    y = f32("MUL", "MulOptions", f32("SUB", "SubOptions", f, 1.0, True), MASKED, False)
+    q = g.act_tensor([batch, tokens], -MASKED / 255.0, 127 if g.dtype == np.int8 else 255)
+    g.mb.op("QUANTIZE", [y], [q], OPT["QuantizeOptions"], Table())
+    return g.reshape(q, [batch, 1, 1, tokens])
+
+
 def text_encoder(dtype=np.int8, seed=9, tokens=128, dim=192, heads=3, hidden=768, blocks=2, vocab=1000, classes=2,
-                 batch=1, hybrid=None):
+                 batch=1, hybrid=None, pooler=False, embedding_lookup=False, mask=False):
     """A BERT-style classifier on token ids [batch, tokens] int32: GATHER of a
     constant [vocab, dim] embedding table (axis 0), ADD of a constant
     [1, tokens, dim] position embedding, LayerNorm, `blocks` pre-norm encoder
@@ -1398,7 +1504,12 @@ def text_encoder(dtype=np.int8, seed=9, tokens=128, dim=192, heads=3, hidden=768
     model, or with `hybrid` ("symmetric" | "asymmetric") the dynamic-range one;
     the table is then a float32 constant either way (GATHER reads it as it is
     stored).  Keep vocab > 99: the benchmark tool fills int32 inputs with
-    0 .. 99."""
+    0 .. 99.  embedding_lookup: the table is read by EMBEDDING_LOOKUP instead
+    of GATHER; pooler: BERT's pooler, FULLY_CONNECTED(dim) -> TANH on token 0 in
+    front of the classifier (8-bit: the TANH output at 1 / 128 around the
+    middle of the range); mask: a second int32 input [batch, tokens], 1 for a
+    token and 0 for padding, turned into an additive mask (_padding_mask) that
+    every block ADDs to its attention scores."""
     assert hybrid is None or np.dtype(dtype) == np.dtype(np.float32), "hybrid is a form of the float32 model"
     quant = np.dtype(dtype) not in (np.dtype(np.float32), np.dtype(np.float16))
     if quant:
@@ -1406,18 +1517,21 @@ def text_encoder(dtype=np.int8, seed=9, tokens=128, dim=192, heads=3, hidden=768
     else:
         g = FGraph(seed, "text_encoder_f32" + ("_hybrid" if hybrid else ""), hybrid=hybrid)
     ids = g.input([batch, tokens], dtype=np.int32)
+    bias = _padding_mask(g, batch, tokens) if mask else None
     table = g.rng.normal(0.0, 1.0, (vocab, dim))
     if quant:
         tab = g.const(table, "embedding")
     else:
         tab = g.mb.tensor(g._name("embedding"), [vocab, dim], np.float32, data=table.astype(np.float32))
         g.meta[tab] = ([vocab, dim], None, None)
-    y = g.gather(tab, ids, axis=0)
+    y = g.embedding_lookup(ids, tab) if embedding_lookup else g.gather(tab, ids, axis=0)
     y = g.add(y, g.const(g.rng.normal(0.0, 0.5, (1, tokens, dim)), "position"))
     y = g.layer_norm(y)
     for _ in range(blocks):
-        y = _encoder(g, y, heads, hidden)
+        y = _encoder(g, y, heads, hidden, bias=bias)
     y = g.strided_slice(y, [0, 0, 0], [0, 1, 0], [1, 1, 1], begin_mask=0b101, end_mask=0b101, shrink_axis_mask=0b010)
+    if pooler:
+        y = g.tanh(g.fully_connected(y, dim))
     g.output(g.fully_connected(y, classes))
     return g.build()
 

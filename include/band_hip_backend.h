@@ -228,6 +228,10 @@ int bhx_cpu_dwconv_hybrid(const void* conv_hybrid_params);
 int bhx_rsqrt_table(float in_scale, int in_zp, float out_scale, int out_zp, uint8_t* table);
 int bhx_gelu_table(int is_signed, int approximate, float in_scale, int in_zp, float out_scale, int out_zp,
                    uint8_t* table);
+/* CpuCast on a bh_cast_params (host pointers, any alignment) */
+int bhx_cpu_cast(const void* cast_params);
+/* the 256-entry table of an 8-bit TANH (TanhTable, quant.cc), indexed by the input byte */
+int bhx_tanh_table(int is_signed, float in_scale, int in_zp, float out_scale, int out_zp, uint8_t* table);
 int bhx_squared_difference_params(float s1, float s2, float so, int32_t* out7);
 
 /* --- job batching (extension, backend/hip/job_batching.h) -------------
